@@ -9,8 +9,13 @@ A "step" is one frame of the full chain (BASELINE.json configs[3]): PBR GGX+IBL 
 TAA -> Bloom -> ToneMap at 3840x2160 per GPU, steady state (temporal history warmed up).  Inputs (the G-buffers of a pre-rendered camera
 orbit of consecutive frames -- tiling.TiledChain.build_inputs -- and the IBL maps) are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times --steps frames and prints the line (value, ms_per_step).  `--full` also runs what the headline does not need, after the
+timed region unless noted: the per-kernel sweep in front of it and `roofline`, overlap_verified, config.stage_lines, cpu_baseline (N > 1: the exchange timing,
+single_gpu_same_frame_ms, shard_verified).  `--dump-outputs DIR` (N = 1) writes what the last timed step computed; on one GPU the timed steps start from a history
+reset behind the clock warm-up, then a fixed number of frames (--warmup, at least SETTLE_FRAMES), so that the same arguments give the same outputs on every run.
+
 `--config ssao1080` / `--config pbr4k` run BASELINE configs[1] / [2] instead (SSAO alone on a 1920x1080 depth + normal G-buffer; the PBR shade alone at 3840x2160) and print the
-same line for them: value, roofline of that configuration's dominant kernel, cpu_baseline of the checker on the same configuration.
+same line for them: value; with --full the roofline of that configuration's dominant kernel and cpu_baseline of the checker on the same configuration.
 
 Roofline accounting: algorithmic bytes = every distinct input texel read once + every output texel written
 once per reference pass in fp32 storage; 874.3 B/px for the whole chain.  `roofline` reports the dominant kernel of the frame (longest
@@ -637,6 +642,11 @@ def parse_args(argv=None):
     p.add_argument("--layers-line", action="store_true", help="also time the PBR shade with all five material layers (config.stage_lines.pbr4k_layers; out of SURVEY section 8's scope)")
     p.add_argument("--no-pass-breakdown", action="store_true")
     p.add_argument("--no-kernel-sweep", action="store_true", help="profiling runs (rocprofv3 counts frames): skip the untimed per-kernel sweep; the line then carries no `roofline`")
+    p.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the per-kernel sweep and `roofline` (with the per-pass "
+                   "breakdown), overlap_verified, config.stage_lines, cpu_baseline; N > 1: the exchange timing, single_gpu_same_frame_ms and shard_verified.  The --no-* options "
+                   "above switch single parts of it off; without --full the run only sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="N = 1: after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; a fixed, "
+                   "seeded sample of pixels with DIR/pixels.npy, their flat row-major indices, when the whole output is over 64 MB)")
     return p.parse_args(argv)
 
 
@@ -692,6 +702,51 @@ def cpu_baseline_stage(mode, size, device, budget_s=15.0):
                       f"OMP_NUM_THREADS={os.environ.get('OMP_NUM_THREADS')} OMP_PROC_BIND={os.environ.get('OMP_PROC_BIND')}; host: {host_cores()[1]})"}
 
 
+def restart(runner, torch):
+    """Back to a fresh run's state: the effects' histories reset (mifx_chain_reset_history; SSAO's own for --config ssao1080) and the orbit at its first position.  The
+    time-based warm-up runs as many frames as the device needs for its clock, a number that changes from run to run; restarting behind it and then stepping a fixed number
+    of frames makes what the timed steps compute depend on the arguments alone."""
+    from diligentfx_amd import tiling
+
+    torch.cuda.synchronize()
+    if isinstance(runner, tiling.StageRunner):
+        if runner.ssao is not None:
+            runner.ssao.reset_history()
+    else:
+        runner.chain.reset_history()
+    runner.t = 0
+
+
+# Frames stepped behind restart() before the timed steps: the history-dependent work is settled by then, as it is behind the time-based warm-up (SSAO's history
+# length saturates at 16 frames; the pixels below it take the history fix and the denoising passes)
+SETTLE_FRAMES = 64
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, seed=0):
+    """Writes {name: (H, W[, C]) device tensor} as path/<name>.npy in float32.  Over DUMP_BYTES in all: the same fixed, seeded sample of pixels from every array, with their flat
+    row-major indices as path/pixels.npy (float64)."""
+    import numpy as np
+    import torch
+
+    from diligentfx_amd.api import widen
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: widen(a) for name, a in arrays.items()}  # (the native-storage build's planes as float32 values)
+    h, w = next(iter(arrays.values())).shape[:2]
+    per_px = sum(4 * a[0, 0].numel() for a in arrays.values())
+    n = min(h * w, (DUMP_BYTES - 4096) // (per_px + 8))  # (4096: the .npy headers)
+    idx = None
+    if n < h * w:
+        pick = np.sort(np.random.default_rng(seed).choice(h * w, size=n, replace=False))
+        np.save(os.path.join(path, "pixels.npy"), pick.astype(np.float64))
+        idx = torch.from_numpy(pick).to(next(iter(arrays.values())).device)
+    for name, a in arrays.items():
+        flat = a.reshape(h * w, -1)
+        a = flat[idx] if idx is not None else a
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+
+
 def kernel_sweep(runner, names, frames=3):
     """Untimed: every bracketed kernel in turn is timed with HIP events over `frames` consecutive frames -> {kernel: average ms per launch}."""
     times = {}
@@ -743,7 +798,7 @@ def main(argv=None):
         KERNEL_BPP, ALGO_BPP = KERNEL_BPP_H4, ALGO_BPP_H4
         CHAIN_BPP = sum(ALGO_BPP.values())
         # (the CPU baseline of this configuration is the checker with format emulation: every image a reference pass writes is rounded to its target format on the host)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         pin_host_threads()  # before any OpenMP runtime is loaded
     import numpy as np
     import torch
@@ -792,6 +847,10 @@ def main(argv=None):
         if world > 1:
             dist.destroy_process_group()
         return 0
+    if args.dump_outputs and world > 1:
+        if rank == 0:
+            error_line(args, "--dump-outputs: one GPU only (a rank of the shared frame holds its own band of the output)")
+        return 2
     if not args.single_gpu and torch.cuda.device_count() < world:
         if rank == 0:
             error_line(args, f"{world} ranks but {torch.cuda.device_count()} GPU(s) visible: refusing to put two ranks on one GPU (--single-gpu does that, for tests)")
@@ -872,7 +931,8 @@ def main(argv=None):
     if shared_frame and not args.no_calibrate and not args.verify_shard and args.cuts is None:
         calibration = runner.calibrate_cuts(rounds=2, frames=6)
     warmup_frames = args.warmup
-    if world == 1 and not args.exact_warmup:
+    timed_warmup = world == 1 and not args.exact_warmup
+    if timed_warmup:
         # at least --warmup frames, and at least 0.3 s of device work: the inputs were just rendered and the IBL maps precomputed -- seconds of host-side work during which the
         # device's clock has dropped (warm_up; the stage configurations are a few hundred microseconds per frame, five of them are over before the clock is back)
         warmup_frames = warm_up(runner.step, torch, args.warmup)
@@ -883,12 +943,19 @@ def main(argv=None):
     # number of frames: the sharded mode exchanges data inside step())
     if overlap and not shared_frame:
         runner.chain.set_overlap(0)  # the sweep times every kernel with nothing beside it
-    ktimes = kernel_sweep(runner, kernels) if not args.no_kernel_sweep else {}
+    ktimes = kernel_sweep(runner, kernels) if args.full and not args.no_kernel_sweep else {}
     if overlap and not shared_frame:
         runner.chain.set_overlap(overlap)
         if ktimes:
             for i in range(4):
                 runner.step()  # (the two streams back in their steady state)
+    if timed_warmup:
+        # (the device is warm now): from a fresh history, a fixed number of frames in front of the timed steps, so that they compute the same on every run
+        restart(runner, torch)
+        settle = max(args.warmup, SETTLE_FRAMES)
+        for i in range(settle):
+            runner.step()
+        warmup_frames += settle
     dominant = max(ktimes, key=ktimes.get) if ktimes else None
     if rank == 0 and dominant:
         runner.arm_kernel_timing(dominant, args.steps)  # HIP events around every launch of the dominant kernel inside the timed region
@@ -910,6 +977,13 @@ def main(argv=None):
 
     elapsed = max_over_ranks(elapsed, side_dev)  # the slowest rank defines the step time (covered by tests/test_dist_gloo.py)
     comm1 = lib_comm.stats() if lib_comm is not None else None
+    if args.dump_outputs:  # (before anything below steps the runner again)
+        if stage and runner.mode == "pbr":
+            dump_outputs(args.dump_outputs, {"radiance": runner.radiance, "specular_ibl": runner.spec})
+        elif stage:
+            dump_outputs(args.dump_outputs, {"ambient_occlusion": runner.ssao.get_ambient_occlusion()})
+        else:
+            dump_outputs(args.dump_outputs, {"ldr": runner.out})
 
     total_px = float(W) * H * (1 if shared_frame else world) * args.steps
     value = total_px / elapsed / 1e6
@@ -1008,7 +1082,7 @@ def main(argv=None):
             result["roofline"]["per_pass_frac"] = {k: round(v["algo_bytes"] / (v["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for k, v in passes.items() if v["algo_bytes"]}
 
     # ---------------------------------------------------------------- the run's own stream mode against the one-stream chain, bit for bit, at the run's own size
-    if world == 1 and not stage and overlap and not args.no_overlap_check:
+    if args.full and world == 1 and not stage and overlap and not args.no_overlap_check:
         try:
             n_cmp = 6
             n_bad = runner.verify_overlap_against_one_stream(n_cmp, fusion_mask=args.fusion_mask)
@@ -1019,14 +1093,14 @@ def main(argv=None):
             result["overlap_verified"] = {"mode": overlap, "failed": repr(e)}
 
     # ---------------------------------------------------------------- BASELINE configs[1] and [2] inside the default line (measured after the timed region, ~1 s each)
-    if rank == 0 and world == 1 and not stage and not shared_frame and not args.no_stage_lines and args.storage == "fp32":
+    if args.full and rank == 0 and world == 1 and not stage and not shared_frame and not args.no_stage_lines and args.storage == "fp32":
         try:
             result["config"]["stage_lines"] = stage_lines(local_rank, tables, torch, with_cpu=not args.no_cpu_baseline, layers=args.layers_line)
         except Exception as e:  # extra information, never a reason to lose the bench line
             result["config"]["stage_lines"] = {"failed": repr(e)}
 
     # ---------------------------------------------------------------- CPU baseline: the oracle / reference on the host cores, bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline_stage("ssao" if args.config == "ssao1080" else "pbr", (W, H), dev) if stage else cpu_baseline(budget_s=20.0, size=(W, H), device=dev)
         except Exception as e:  # the baseline is a reported number, never a reason to lose the bench line
@@ -1043,6 +1117,7 @@ def main(argv=None):
             comm["bytes_sent_per_frame"] = (comm1["bytes_sent"] - comm0["bytes_sent"]) // args.steps
             comm["bytes_received_per_frame"] = (comm1["bytes_received"] - comm0["bytes_received"]) // args.steps
             comm["exchange_groups_per_frame"] = (comm1["groups"] - comm0["groups"]) / args.steps
+        if lib_comm is not None and args.full:
             lib_comm.set_timing(True)
             for _ in range(3):
                 runner.step()
@@ -1057,27 +1132,30 @@ def main(argv=None):
         # ---- the same frame, whole, on ONE GPU (rank 0's, the others wait): what the sharded frame time compares with -- the N = 1 line of this bench times a 3840x2160
         # frame, a quarter of the pixels, and is not that reference
         single_ms = None
-        if rank == 0 and not args.no_single_gpu_reference:
+        if args.full and rank == 0 and not args.no_single_gpu_reference:
             try:
                 single_ms = runner.time_unsharded_same_frame(frames=max(6, min(args.steps, 20)), warm=6)
             except Exception as e:  # noqa: BLE001 -- extra information, never a reason to lose the line
                 result["single_gpu_same_frame_failed"] = repr(e)
-        barrier()
+        if args.full:
+            barrier()
         if single_ms is not None:
             result["single_gpu_same_frame_ms"] = round(single_ms, 4)
             result["speedup_vs_single_gpu_same_frame"] = round(single_ms / ms_per_step, 3)
             result["single_gpu_same_frame_how"] = (f"the unsharded chain (mifx_chain_execute, three lanes with two frames in flight: mifx_chain_set_overlap 5) on the whole {W}x{H} frame of the same orbit on rank 0's GPU "
                                                    "after the timed region, the other ranks idle" + ("; with --single-gpu every rank shares that GPU, so the ratio is not a scaling figure" if args.single_gpu else ""))
         # the sharded frame against the unsharded chain, bit for bit: every frame of the run with --verify-shard, else three frames after the timed region
+        n_cmp = None
         if args.verify_shard and runner.mifx_comm is None:
             n_cmp, n_bad = args.warmup + args.steps, runner.mismatches
-        else:
+        elif args.full:
             n_cmp = 3
             n_bad = runner.verify_against_unsharded(n_cmp)
-        bad = torch.tensor([n_bad], dtype=torch.int64, device=side_dev)
-        dist.all_reduce(bad)
-        result["shard_verified"] = {"frames_compared": n_cmp, "bands_that_differed": int(bad.item()),
-                                    "how": "every rank also runs the unsharded chain from the same history reset and compares its band of the output bit for bit"}
+        if n_cmp is not None:
+            bad = torch.tensor([n_bad], dtype=torch.int64, device=side_dev)
+            dist.all_reduce(bad)
+            result["shard_verified"] = {"frames_compared": n_cmp, "bands_that_differed": int(bad.item()),
+                                        "how": "every rank also runs the unsharded chain from the same history reset and compares its band of the output bit for bit"}
     if rank == 0:
         print(json.dumps(result), flush=True)
     if watchdog is not None:

@@ -187,3 +187,39 @@ def test_bench_arguments_of_round_6():
     assert a.cuts == [0, 1358, 1919, 2380, 2750, 3140, 3536, 3917, 4320] and a.backend is None and a.comm == "rccl" and a.watchdog_s == 900.0 and not a.exact_warmup
     assert bench.parse_args(["--exact-warmup", "--watchdog-s", "0"]).exact_warmup
     assert bench.rank_environment() is None or "WORLD_SIZE" in os.environ
+
+
+def test_plain_run_and_its_options():
+    """A plain run times the headline alone; the extra measurements and checks are opt-in with --full, the output dump with --dump-outputs DIR."""
+    bench = load_bench()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """dump_outputs: float32 .npy files; the whole arrays while they fit the budget, else the same seeded pixel sample from every array with its flat indices."""
+    import numpy as np
+    import torch
+
+    bench = load_bench()
+    g = torch.Generator().manual_seed(1)
+    ldr = torch.rand(48, 64, 4, generator=g, dtype=torch.float64).to(torch.float16)
+    ao = torch.rand(48, 64, generator=g)
+    bench.dump_outputs(str(tmp_path / "whole"), {"ldr": ldr, "ao": ao})
+    assert sorted(os.listdir(tmp_path / "whole")) == ["ao.npy", "ldr.npy"]
+    got = np.load(tmp_path / "whole" / "ldr.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, ldr.float().numpy()) and np.array_equal(np.load(tmp_path / "whole" / "ao.npy"), ao.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 28 * 250)  # 250 pixels of 4 + 1 float32 channels and a float64 index
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"ldr": ldr, "ao": ao})
+    pix = np.load(tmp_path / "a" / "pixels.npy")
+    assert pix.dtype == np.float64 and len(pix) == 250 and np.all(np.diff(pix) > 0) and pix[-1] < 48 * 64
+    i = pix.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "ldr.npy"), ldr.float().reshape(-1, 4).numpy()[i])
+    assert np.array_equal(np.load(tmp_path / "a" / "ao.npy"), ao.reshape(-1, 1).numpy()[i])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
