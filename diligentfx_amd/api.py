@@ -406,6 +406,68 @@ def composite(ctx: "PostFXContext", color, specular_ibl, ssr, ssao, normal, base
     return out
 
 
+def composite_selection(ctx: "PostFXContext", color, specular_ibl, ssr, ssao, normal, base_color, material, lut, camera, depth, selection_depth, closest_location,
+                        selection: "B.SelectionAttribs", ssr_scale=1.0, ssao_scale=1.0, tone_mapping=None, ave_log_lum=0.3, out=None):
+    """The composite with the selection tail (mifx_composite_execute_selection), Hydrogent/shaders/HnPostProcess.psh:145-185 + 211-241.  The outline colours of
+    `selection` are used as given (ProcessSelection.hdr_colors converts them the way the reference's host does when TAA follows a tone-mapped frame)."""
+    if out is None:
+        out = torch.empty_like(color)
+    imgs = [B.image(t) for t in (color, specular_ibl, ssr, ssao, normal, base_color, material, lut)]
+    a = B.CompositeAttribs(*[ctypes.pointer(i) for i in imgs], ctypes.pointer(camera), ssr_scale, ssao_scale,
+                           ctypes.pointer(tone_mapping) if tone_mapping is not None else None, ave_log_lum)
+    si = [B.image(t) for t in (depth, selection_depth, closest_location)]
+    inputs = B.SelectionCompositeInputs(*[ctypes.pointer(i) for i in si], ctypes.pointer(selection))
+    o = B.image(out)
+    ctx.sync_stream()
+    B.check(ctx.lib.mifx_composite_execute_selection(ctx.handle, ctypes.byref(a), ctypes.byref(inputs), ctypes.byref(o)))
+    return out
+
+
+class ProcessSelection:
+    """== Diligent::USD::HnProcessSelectionTask (Hydrogent/src/Tasks/HnProcessSelectionTask.cpp:302-369): the closest-selected-location plane (F32X2, the encoding of
+    HnClosestSelectedLocation.fxh) by jump flooding a selection depth plane."""
+
+    def __init__(self, ctx: "PostFXContext"):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.handle = ctypes.c_void_p()
+        B.check(self.lib.mifx_selection_create(ctx.handle, ctypes.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            self.lib.mifx_selection_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def execute(self, selection_depth, attribs: "B.SelectionAttribs"):
+        d = B.image(selection_depth)
+        self.ctx.sync_stream()
+        return B.check(self.lib.mifx_selection_execute(self.handle, ctypes.byref(d), ctypes.byref(attribs)))
+
+    def get_output(self):
+        d = B.Image2D()
+        B.check(self.lib.mifx_selection_get_output(self.handle, ctypes.byref(d)))
+        return _view(d, self.ctx.device)
+
+    @staticmethod
+    def hdr_colors(attribs: "B.SelectionAttribs", tone_mapping: "B.ToneMappingAttribs | None", ave_log_lum):
+        """A copy of `attribs` with the outline colours as HnPostProcessTask.cpp:843-850 hands them to the composite when TAA follows: ReverseExpToneMap of the rgb
+        (fMiddleGray, AverageLogLum) when the tone mapping mode is not NONE, alpha as given."""
+        out = B.SelectionAttribs.from_buffer_copy(bytes(attribs))
+        if tone_mapping is not None and tone_mapping.iToneMappingMode != 0:
+            lib = B.load()
+            for name in ("outline_color", "occluded_outline_color"):
+                src = getattr(attribs, name)
+                ldr, hdr = (ctypes.c_float * 3)(*src[:3]), (ctypes.c_float * 3)()
+                B.check(lib.mifx_reverse_exp_tone_map(ldr, ctypes.c_float(tone_mapping.fMiddleGray), ctypes.c_float(ave_log_lum), hdr))
+                getattr(out, name)[:3] = list(hdr)
+        return out
+
+
 def _export_history(fx, channel_shapes):
     """mifx_<effect>_export_history into fresh tensors of the prepared size; returns (*planes, frame_index)."""
     # (a plane of the prepared size; not the SSR output: inside a chain that plane may be deferred, mifx_ssr_run_deferred_cleanup)
@@ -806,8 +868,9 @@ class Chain:
         B.check(self.lib.mifx_chain_set_fusion(self.handle, ctypes.c_int32(1 if tone_map_into_bloom else 0), ctypes.c_int32(1 if ssr_mask_into_shade else 0)))
 
     def effect(self, name):
-        """Non-owning view of one of the chain's own effect objects ("ssao", "ssr", "taa", "bloom"): intermediates, history export / import."""
-        cls = {"ssao": ScreenSpaceAmbientOcclusion, "ssr": ScreenSpaceReflection, "taa": TemporalAntiAliasing, "bloom": Bloom}[name]
+        """Non-owning view of one of the chain's own effect objects ("ssao", "ssr", "taa", "bloom", "selection" once set_selection turned it on): intermediates,
+        history export / import, the closest-selected-location plane."""
+        cls = {"ssao": ScreenSpaceAmbientOcclusion, "ssr": ScreenSpaceReflection, "taa": TemporalAntiAliasing, "bloom": Bloom, "selection": ProcessSelection}[name]
         h = ctypes.c_void_p()
         B.check(self.lib.mifx_chain_get_effect(self.handle, name.encode(), ctypes.byref(h)))
         fx = cls.__new__(cls)
@@ -843,6 +906,17 @@ class Chain:
                 rows[i] = r if isinstance(r, B.PBRShadowMapInfo) else B.PBRShadowMapInfo.from_buffer_copy(r.astype("float32").tobytes())
             sh = B.PBRShadows(ctypes.pointer(arr), ctypes.cast(rows, ctypes.POINTER(B.PBRShadowMapInfo)), len(infos), pcf)
         B.check(self.lib.mifx_chain_set_material_layers(self.handle, ctypes.byref(ly) if ly is not None else None, ctypes.byref(sh) if sh is not None else None))
+
+    def set_selection(self, attribs: "B.SelectionAttribs | None", selection_depth=None):
+        """Selection highlighting (mifx_chain_set_selection): the jump flood of `selection_depth` and the composite's selection tail on every frame from now on; None
+        turns it off.  The tensor is kept alive here (the library borrows it)."""
+        if attribs is None:
+            self._selection_keep = None
+            B.check(self.lib.mifx_chain_set_selection(self.handle, None, None))
+            return
+        d = B.image(selection_depth)
+        self._selection_keep = (selection_depth, attribs)
+        B.check(self.lib.mifx_chain_set_selection(self.handle, ctypes.byref(attribs), ctypes.byref(d)))
 
     def auto_exposure_average(self):
         h = ctypes.c_void_p()

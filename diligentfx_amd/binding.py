@@ -247,6 +247,20 @@ class CompositeAttribs(ctypes.Structure):
                 ("tone_mapping", ctypes.POINTER(ToneMappingAttribs)), ("ave_log_lum", c_f)]
 
 
+class SelectionAttribs(ctypes.Structure):
+    """mifx_selection_attribs -- HnPostProcessTaskParams (HnPostProcessTask.hpp:79-85), HnProcessSelectionTaskParams::MaximumDistance (HnProcessSelectionTask.hpp:49)"""
+    _fields_ = [("outline_color", c_f * 4), ("occluded_outline_color", c_f * 4), ("nonselection_desaturation", c_f), ("clear_depth", c_f),
+                ("outline_width", c_f), ("max_distance", c_f), ("selection_id", ctypes.c_uint64)]
+
+    @classmethod
+    def default(cls, selection_id=0, clear_depth=1.0):
+        return cls((c_f * 4)(1.0, 0.675, 0.25, 0.5), (c_f * 4)(0.375, 0.375, 0.125, 0.5), 0.0, clear_depth, 4.0, 4.0, selection_id)
+
+
+class SelectionCompositeInputs(ctypes.Structure):  # mifx_selection_composite_inputs
+    _fields_ = [("depth", PImage), ("selection_depth", PImage), ("closest_location", PImage), ("attribs", ctypes.POINTER(SelectionAttribs))]
+
+
 class ChainFrame(ctypes.Structure):
     _fields_ = [("frame", FrameDesc), ("gbuffer", GBuffer), ("motion", PImage), ("prev_depth", PImage),
                 ("curr_camera", ctypes.POINTER(CameraAttribs)), ("prev_camera", ctypes.POINTER(CameraAttribs)),
@@ -261,6 +275,7 @@ SIZEOF_NAMES = {
     "ssao_attribs": SSAOAttribs, "ssr_attribs": SSRAttribs, "bloom_attribs": BloomAttribs, "dof_attribs": DOFAttribs, "taa_attribs": TAAAttribs,
     "pbr_light_attribs": PBRLightAttribs, "pbr_shade_attribs": PBRShadeAttribs, "frame_desc": FrameDesc, "chain_frame": ChainFrame,
     "composite_attribs": CompositeAttribs, "gbuffer": GBuffer, "ibl": IBL, "pbr_shadow_map_info": PBRShadowMapInfo,
+    "selection_attribs": SelectionAttribs, "selection_composite_inputs": SelectionCompositeInputs,
 }
 
 _lib = None

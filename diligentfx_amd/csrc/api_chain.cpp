@@ -4,11 +4,14 @@
 // SSR reads the un-composited scene colour of the current frame (FEATURE_FLAG_PREVIOUS_FRAME off), tone mapping is applied by the
 // final copy-frame pass because TAA is on (HnPostProcessTask.cpp:172, :920-927).  Everything is recorded on the context stream.
 #include "mifx_objects.h"
+#include "mifx_selection_host.h"
 #include <cstdlib>
 #include <cmath>
 #include <string>
 
 using namespace mifx;
+
+const SelectionHooks* mifx::selection_hooks = nullptr; // (set by selection.hip when the library is loaded)
 
 mifx_chain::~mifx_chain()
 {
@@ -27,6 +30,7 @@ mifx_chain::~mifx_chain()
     if (lane_x) (void)hipStreamDestroy(lane_x);
     if (lane_h) (void)hipStreamDestroy(lane_h);
     mifx::chain_detach_comm(this);
+    if (selection && selection_hooks) selection_hooks->destroy(selection);
     mifx_autoexposure_destroy(auto_exposure);
     mifx_bloom_destroy(bloom);
     mifx_dof_destroy(dof);
@@ -91,6 +95,7 @@ mifx_status mifx_chain_get_effect(mifx_chain* chain, const char* name, void** ou
     else if (n == "taa") *out = chain->taa;
     else if (n == "bloom") *out = chain->bloom;
     else if (n == "dof") *out = chain->dof; // NULL until mifx_chain_set_depth_of_field enabled it
+    else if (n == "selection") *out = chain->selection; // NULL until mifx_chain_set_selection turned it on
     else
     {
         set_error("mifx_chain_get_effect: unknown effect '%s'", name);
@@ -157,6 +162,20 @@ static mifx_status chain_check_workflow(const mifx_chain_frame* f)
     return MIFX_OK;
 }
 
+// mifx_chain_set_selection: HnProcessSelectionTask's jump flood, then the composite with the selection tail of HnPostProcess.psh:211-241, both on the composite's stream and rows.
+// TAA follows the composite in the chain, so a tone-mapped frame gets the outline colours in HDR: ReverseExpToneMap(colour, fMiddleGray, AverageLogLum), alpha as given
+// (HnPostProcessTask.cpp:843-850).
+static mifx_status chain_selection_composite(mifx_chain* chain, const mifx_chain_frame* f, const mifx_composite_attribs& ca, const mifx_image2d* comp, const SsrCleanupIn* r7)
+{
+    mifx_selection_attribs a = chain->selection_attribs;
+    if (f->tone_mapping != nullptr && f->tone_mapping->iToneMappingMode != MIFX_TONE_MAPPING_MODE_NONE)
+    {
+        MIFX_CHECK(mifx_reverse_exp_tone_map(chain->selection_attribs.outline_color, f->tone_mapping->fMiddleGray, f->ave_log_lum, a.outline_color));
+        MIFX_CHECK(mifx_reverse_exp_tone_map(chain->selection_attribs.occluded_outline_color, f->tone_mapping->fMiddleGray, f->ave_log_lum, a.occluded_outline_color));
+    }
+    return selection_hooks->chain_composite(chain->selection, a, &chain->selection_depth, ca, f->gbuffer.depth, comp, r7);
+}
+
 // The composite draw (HnPostProcess.psh:145-185).  With fuse_ssr_cleanup the kernel evaluates SSR's last pass (R7, the bilateral cleanup) for its own pixel from the
 // effect's accumulated radiance instead of reading the plane R7 would have written (mifx_ssr_execute stopped after R6: mifx_objects.h `defer_cleanup`).
 // With fuse_composite_taa on top of that (round 5) nothing is launched here: the TAA kernel of this frame evaluates the composite for the texels of its colour tile
@@ -172,6 +191,7 @@ static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f,
     if (!fused) MIFX_CHECK(mifx_ssr_get_output(ssr, &ssr_out));
     mifx_composite_attribs ca{radiance, spec, fused ? radiance /* not read */ : &ssr_out, ssao_out, f->gbuffer.normal, f->gbuffer.base_color, f->gbuffer.material, f->ibl->brdf_lut,
                               f->curr_camera, f->ssr_scale, f->ssao_scale, nullptr, f->ave_log_lum};
+    if (chain->has_selection) return chain_selection_composite(chain, f, ca, comp, fused ? &ssr->cleanup_in : nullptr); // (a pass of its own, also with fuse_composite_taa)
     if (!fused) return mifx_composite_execute(ctx, &ca, comp);
     if (chain->fuse_composite_taa && chain->taa->technique_ready)
     {
@@ -187,7 +207,15 @@ static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f,
 // TemporalAntiAliasing::Execute on the jittered composite (:871-897) -- on the plane, or with the composite evaluated in place (above)
 static mifx_status chain_taa(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* comp)
 {
-    mifx_taa_render_attribs ta{chain->ctx, comp, f->taa};
+    // a selected prim other than the previous frame's resets the accumulation (HnProcessSelectionTask.cpp:293-300)
+    mifx_taa_attribs taa_attribs{};
+    if (chain->has_selection && f->taa != nullptr)
+    {
+        taa_attribs = *f->taa;
+        if (chain->selection_attribs.selection_id != chain->last_selection_id) taa_attribs.ResetAccumulation = 1;
+        chain->last_selection_id = chain->selection_attribs.selection_id;
+    }
+    mifx_taa_render_attribs ta{chain->ctx, comp, chain->has_selection && f->taa != nullptr ? &taa_attribs : f->taa};
     const mifx::TaaFusedComposite fused = chain->pending_fused; // (a per-frame request: cleared whatever the call returns)
     chain->pending_fused = mifx::TaaFusedComposite{nullptr, nullptr};
     chain->taa->fused_composite = fused.attribs ? &fused : nullptr;
@@ -865,6 +893,29 @@ mifx_status mifx_chain_set_depth_of_field(mifx_chain* chain, const mifx_dof_attr
     if (!chain->dof) MIFX_CHECK(mifx_dof_create(chain->ctx, &chain->dof));
     chain->dof_attribs = *attribs;
     chain->dof_flags   = feature_flags;
+    return MIFX_OK;
+}
+
+mifx_status mifx_chain_set_selection(mifx_chain* chain, const mifx_selection_attribs* attribs, const mifx_image2d* selection_depth)
+{
+    MIFX_REQUIRE(chain != nullptr, "mifx_chain_set_selection: null chain");
+    if (attribs == nullptr)
+    {
+        chain->has_selection     = false;
+        chain->last_selection_id = 0; // (turning selection off forgets the selected prim)
+        return MIFX_OK;
+    }
+    MIFX_REQUIRE(selection_depth != nullptr && selection_depth->data != nullptr, "mifx_chain_set_selection: the selection depth image is missing");
+    MIFX_REQUIRE(attribs->outline_width > 0.0f, "mifx_chain_set_selection: outline_width %g must be positive", double(attribs->outline_width));
+    if (selection_hooks == nullptr)
+    {
+        set_error("mifx_chain_set_selection: this build of the library has no selection kernels");
+        return MIFX_ERR_NOT_IMPLEMENTED;
+    }
+    if (chain->selection == nullptr) MIFX_CHECK(selection_hooks->create(chain->ctx, &chain->selection));
+    chain->selection_attribs = *attribs;
+    chain->selection_depth   = *selection_depth;
+    chain->has_selection     = true;
     return MIFX_OK;
 }
 

@@ -5,14 +5,17 @@
 #include "mifx_effects.h"
 #include "mifx_tonemap.h"
 #include "mifx_ssr_cleanup.h"
+#include "mifx_selection.h"
 
 namespace mifx
 {
 // FUSE_R7: the reflection is SSR's bilateral cleanup (pass R7) evaluated here for this pixel from the effect's accumulated radiance / variance instead of a load of
 // the plane R7 would have written -- this kernel is that plane's only consumer in the chain (mifx_ssr_cleanup.h; `ssr` is not read).  outW / outH: the size of the target.
-template <int TM_MODE, bool FUSE_R7>
+// SELECTION: after the optional tone map, the selection tail of HnPostProcess.psh:211-241 (mifx_selection.h) with the planes and colours of `sel` (not read otherwise).
+template <int TM_MODE, bool FUSE_R7, bool SELECTION = false>
 MIFX_D void composite_pixel(v4& result, int x, int y, const Img& color, const Img& specIBL, const Img& ssr, const Img& ssao, const Img& normalTex, const Img& baseColor, const Img& material,
-                          const LutK& lut, int outW, int outH, const CamK& cam, float ssrScaleAttr, float ssaoScaleAttr, const ToneMapK& tm, const SsrCleanupIn& r7)
+                          const LutK& lut, int outW, int outH, const CamK& cam, float ssrScaleAttr, float ssaoScaleAttr, const ToneMapK& tm, const SsrCleanupIn& r7,
+                          const SelectionK& sel = SelectionK{})
 {
     // (loads grouped by what they depend on: the colour -- whose alpha decides whether anything else is read -- with the reflection mask; then every other plane of
     //  the pixel at once, the inputs of the fused cleanup included; then the LUT taps, which need the roughness and the normal)
@@ -43,6 +46,15 @@ MIFX_D void composite_pixel(v4& result, int x, int y, const Img& color, const Im
     }
     if (ssaoScale > 0.0f) rgb = rgb * lerpf(1.0f, ao, ssaoScale);
     if (TM_MODE != MIFX_TONE_MAPPING_MODE_NONE) rgb = tone_map<TM_MODE>(rgb, tm);
+    if (SELECTION)
+    {
+        const float depth = ld<float>(sel.depth, x, y), selDepth = ld<float>(sel.selectionDepth, x, y);
+        const v2    enc   = ld<v2>(sel.closest, x, y);
+        rgb = selection_tail(rgb, x, y, outW, outH, depth, selDepth, enc, sel, [&](int lx, int ly, float& d, float& sd) __attribute__((always_inline)) {
+            d  = ld<float>(sel.depth, lx, ly);
+            sd = ld<float>(sel.selectionDepth, lx, ly);
+        });
+    }
     result = mk4(rgb, c.w);
 }
 } // namespace mifx

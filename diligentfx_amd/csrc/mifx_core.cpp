@@ -237,6 +237,8 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("frame_desc", mifx_frame_desc);
     MIFX_SZ("chain_frame", mifx_chain_frame);
     MIFX_SZ("composite_attribs", mifx_composite_attribs);
+    MIFX_SZ("selection_attribs", mifx_selection_attribs);
+    MIFX_SZ("selection_composite_inputs", mifx_selection_composite_inputs);
     MIFX_SZ("gbuffer", mifx_gbuffer);
     MIFX_SZ("ibl", mifx_ibl);
     MIFX_SZ("shard_info", mifx_shard_info);

@@ -370,6 +370,13 @@ struct mifx_chain
     mifx_pbr_shadows         shadows{};
     mifx_shadow_map_array    shadow_array{};
     mifx_pbr_shadow_map_info shadow_infos[MIFX_PBR_MAX_SHADOW_MAPS]{};
+    // mifx_chain_set_selection: the jump flood + the selection composite in place of the composite (selection.hip, reached through mifx::selection_hooks); the attribs and the
+    // image descriptor are copies, the selection depth plane is borrowed
+    bool                   has_selection = false;
+    mifx_selection*        selection = nullptr;
+    mifx_selection_attribs selection_attribs{};
+    mifx_image2d           selection_depth{};
+    uint64_t               last_selection_id = 0; // the selected prim of the previous frame executed with selection on (a change resets TAA)
     mifx_autoexposure* auto_exposure = nullptr; // optional: fAveLogLum of the final tone map from the average luminance of the Bloom output
     float        ae_elapsed = 0.0f;
     bool         ae_adapt   = true;

@@ -755,6 +755,43 @@ typedef struct mifx_composite_attribs
 MIFX_API mifx_status mifx_pbr_specgloss_to_material(mifx_postfx* ctx, const mifx_image2d* base_color, const mifx_image2d* physical_desc, const mifx_image2d* out_material);
 MIFX_API mifx_status mifx_composite_execute(mifx_postfx* ctx, const mifx_composite_attribs* attribs, const mifx_image2d* out);
 
+/* ------------------------------------------------------------------------------------------------ selection (HnProcessSelectionTask + HnPostProcess.psh:211-241) */
+/* What the selection outline needs: HnPostProcessTaskParams (Hydrogent/interface/Tasks/HnPostProcessTask.hpp:79-85), HnProcessSelectionTaskParams::MaximumDistance
+ * (HnProcessSelectionTask.hpp:49) and the selected prim (HnRenderParam::GetSelectedPrimId). */
+typedef struct mifx_selection_attribs
+{
+    float    outline_color[4];          /* SelectionColor {1.0, 0.675, 0.25, 0.5}: rgb drawn where the selected pixel is visible (a is not used) */
+    float    occluded_outline_color[4]; /* OccludedSelectionColor {0.375, 0.375, 0.125, 0.5}: where it is occluded */
+    float    nonselection_desaturation; /* NonselectionDesaturationFactor 0: every pixel that is not selected is lerped toward its luminance by this */
+    float    clear_depth;               /* 1.0 (0.0 with reversed depth): the selection depth of a pixel that is not selected, and the depth of the background */
+    float    outline_width;             /* SelectionOutlineWidth 4.0, in pixels */
+    float    max_distance;              /* MaximumDistance 4.0: ceil(log2(max(d, 1))) + 1 jump-flood steps (HnProcessSelectionTask.cpp:71) */
+    uint64_t selection_id;              /* the selected prim, 0 = nothing selected (no jump flood runs, the plane is cleared: HnProcessSelectionTask.cpp:329-335) */
+} mifx_selection_attribs;
+/* HnProcessSelectionTask (HnProcessSelectionTask.cpp:302-369): the closest selected location of every pixel by jump flooding the selection depth
+ * (HnInitClosestSelectedLocation.psh, then HnUpdateClosestSelectedLocation.psh with SampleRange = 1 << (n - 1 - i)), bit for bit the reference's multi-pass result.
+ * The trailing steps whose reach fits a 7-pixel halo (the default's three: ranges 4, 2, 1) run as ONE launch that reads the selection depth once; the steps of larger
+ * ranges (max_distance > 4) run one launch each in front of it.  The output is an F32X2 plane in the reference's encoding (HnClosestSelectedLocation.fxh: (x, y / 2 + 1 / 2)
+ * for a location, (0, 0) for none). */
+typedef struct mifx_selection mifx_selection;
+MIFX_API mifx_status mifx_selection_create(mifx_postfx* ctx, mifx_selection** out);
+MIFX_API void        mifx_selection_destroy(mifx_selection* sel);
+/* selection_depth: F32, the depth of the selected prim where it was rendered and attribs->clear_depth elsewhere */
+MIFX_API mifx_status mifx_selection_execute(mifx_selection* sel, const mifx_image2d* selection_depth, const mifx_selection_attribs* attribs);
+MIFX_API mifx_status mifx_selection_get_output(mifx_selection* sel, mifx_image2d* out); /* the final closest-selected-location plane (F32X2) */
+/* The composite with the selection tail of HnPostProcess.psh:211-241 after the optional tone map: the pixels that are not selected desaturated, the outline drawn in
+ * outline_color where the closest selected pixel is visible and occluded_outline_color where it is not.  Alpha is untouched.  The colours are taken as given (the reference's
+ * host converts them with ReverseExpToneMap when TAA follows a tone-mapped frame, HnPostProcessTask.cpp:843-850: mifx_reverse_exp_tone_map). */
+typedef struct mifx_selection_composite_inputs
+{
+    const mifx_image2d*           depth;            /* F32 scene depth */
+    const mifx_image2d*           selection_depth;  /* F32 */
+    const mifx_image2d*           closest_location; /* F32X2: mifx_selection_get_output */
+    const mifx_selection_attribs* attribs;          /* colours, desaturation, clear depth, outline width (max_distance and selection_id are not read) */
+} mifx_selection_composite_inputs;
+MIFX_API mifx_status mifx_composite_execute_selection(mifx_postfx* ctx, const mifx_composite_attribs* attribs, const mifx_selection_composite_inputs* selection,
+                                                      const mifx_image2d* out);
+
 /* ------------------------------------------------------------------------------------------------ whole chain (the caller: HnPostProcessTask::Execute, Hydrogent/src/Tasks/HnPostProcessTask.cpp:743-948) */
 typedef struct mifx_autoexposure mifx_autoexposure; /* auto exposure, declared below */
 typedef struct mifx_chain mifx_chain;
@@ -784,7 +821,8 @@ MIFX_API void        mifx_chain_destroy(mifx_chain* chain);
 /* PBR shade -> prep -> SSR -> SSAO -> composite -> TAA -> Bloom -> ToneMap, recorded on the context stream. */
 MIFX_API mifx_status mifx_chain_execute(mifx_chain* chain, const mifx_chain_frame* frame, const mifx_image2d* out_ldr);
 MIFX_API mifx_status mifx_chain_get_postfx(mifx_chain* chain, mifx_postfx** out);
-/* the effect objects the chain owns, by name: "ssao" (mifx_ssao*), "ssr" (mifx_ssr*), "taa" (mifx_taa*), "bloom" (mifx_bloom*), "dof" (mifx_dof*, NULL while off) -- for their outputs and intermediates */
+/* the effect objects the chain owns, by name: "ssao" (mifx_ssao*), "ssr" (mifx_ssr*), "taa" (mifx_taa*), "bloom" (mifx_bloom*), "dof" (mifx_dof*, NULL while off),
+ * "selection" (mifx_selection*, NULL until mifx_chain_set_selection turned it on) -- for their outputs and intermediates */
 MIFX_API mifx_status mifx_chain_get_effect(mifx_chain* chain, const char* name, void** out);
 /* mifx_chain_execute with the final image in the copy-frame target's own format (e.g. MIFX_NATIVE_FORMAT_RGBA8_UNORM_SRGB), see mifx_tonemap_execute_native.
  * Not available with a row band or together with mifx_chain_set_auto_exposure (MIFX_ERR_INVALID_ARG). */
@@ -812,6 +850,14 @@ MIFX_API mifx_status mifx_chain_set_depth_of_field(mifx_chain* chain, const mifx
  * shade kernel writes its two planes as a by-product, this one does not).  With a row band the sharded SSR's hit fetch shades its pixels with the same layers and shadow maps
  * (every rank holds the planes whole, as it holds the G-buffer). */
 MIFX_API mifx_status mifx_chain_set_material_layers(mifx_chain* chain, const mifx_pbr_layers* layers, const mifx_pbr_shadows* shadows);
+/* Selection highlighting in the chain (off by default): every frame executed from now on runs the jump flood of mifx_selection_execute on `selection_depth` and the
+ * composite with the selection tail (mifx_composite_execute_selection).  The attribs are copied, the image descriptor too; the device plane is borrowed for every frame
+ * until the next call (like the G-buffer: whole on every rank of a row band, so a band needs no exchange for it).  TAA follows, so with a tone mapping mode other than NONE
+ * the outline colours are converted with ReverseExpToneMap (frame.ave_log_lum, fMiddleGray) as HnPostProcessTask.cpp:843-850 does.  A frame whose selection_id differs from
+ * the previous selection frame's runs TAA with ResetAccumulation (HnProcessSelectionTask.cpp:293-300; turning selection off forgets the id).  With
+ * MIFX_CHAIN_FUSE_COMPOSITE_INTO_TAA the selection composite still runs as a pass of its own (TAA reads its plane).  attribs == NULL: off -- the chain launches exactly
+ * what it launches without this call.  The effect object is mifx_chain_get_effect(chain, "selection") (NULL until selection was first turned on). */
+MIFX_API mifx_status mifx_chain_set_selection(mifx_chain* chain, const mifx_selection_attribs* attribs /* NULL = off */, const mifx_image2d* selection_depth);
 /* Row-band sharding of one frame across the GPUs of a node. A chain with a row band [row_begin, row_end) produces those
  * rows of the output; every pass runs on the rows its consumers need (the band grown by the reach of everything downstream), the caller
  * moves two kinds of data (three with auto exposure) between the phases of mifx_chain_execute_phase (diligentfx_amd/tiling.py does it with RCCL):

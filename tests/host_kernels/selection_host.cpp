@@ -1,0 +1,63 @@
+// TEST INFRASTRUCTURE ONLY.  The selection outline's per-pixel bodies (diligentfx_amd/csrc/mifx_selection.h) compiled for the HOST (see layers_host.cpp for the method):
+//   * the jump flood as the reference defines it -- the init pass, then one whole-frame step per SampleRange (jf_init / jf_step: the bodies of selection.hip's kernels);
+//   * the composite's selection tail (selection_tail: the body composite_kernel's selection instance appends after the tone map).
+// Nothing in diligentfx_amd/ builds, loads or calls this.
+#include <hip/hip_runtime.h>
+#undef __device__
+#define __device__ __attribute__((host)) __attribute__((device))
+#include "mifx.h"
+#include "mifx_selection.h"
+#include <vector>
+
+using namespace mifx;
+
+extern "C" {
+// selection_depth: w x h floats; out: w x h float2 (the final plane)
+int mifx_host_jump_flood(const float* selection_depth, float* out, int w, int h, float clear_depth, float max_distance)
+{
+    const int n = jf_iterations(max_distance);
+    std::vector<v2> a(size_t(w) * h), b(size_t(w) * h);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) a[size_t(y) * w + x] = jf_init(x, y, selection_depth[size_t(y) * w + x], clear_depth, w, h);
+    for (int i = 0; i < n; ++i)
+    {
+        const int range = 1 << (n - 1 - i);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) b[size_t(y) * w + x] = jf_step(x, y, range, w, h, [&](int tx, int ty) { return a[size_t(ty) * w + tx]; });
+        a.swap(b);
+    }
+    for (size_t i = 0; i < a.size(); ++i)
+    {
+        out[2 * i]     = a[i].x;
+        out[2 * i + 1] = a[i].y;
+    }
+    return n;
+}
+
+// rgba_in / rgba_out: w x h float4; depth / selection_depth: w x h floats; closest: w x h float2
+int mifx_host_selection_tail(const float* rgba_in, const float* depth, const float* selection_depth, const float* closest, float* rgba_out, int w, int h,
+                             const mifx_selection_attribs* a)
+{
+    SelectionK k{};
+    for (int i = 0; i < 3; ++i)
+    {
+        k.outline[i]  = a->outline_color[i];
+        k.occluded[i] = a->occluded_outline_color[i];
+    }
+    k.desaturation = a->nonselection_desaturation;
+    k.clearDepth   = a->clear_depth;
+    k.outlineWidth = a->outline_width;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x)
+        {
+            const size_t i = size_t(y) * w + x;
+            const v3 rgb = selection_tail(v3{rgba_in[4 * i], rgba_in[4 * i + 1], rgba_in[4 * i + 2]}, x, y, w, h, depth[i], selection_depth[i], v2{closest[2 * i], closest[2 * i + 1]}, k,
+                                          [&](int lx, int ly, float& d, float& sd) {
+                                              d  = depth[size_t(ly) * w + lx];
+                                              sd = selection_depth[size_t(ly) * w + lx];
+                                          });
+            rgba_out[4 * i] = rgb.x; rgba_out[4 * i + 1] = rgb.y; rgba_out[4 * i + 2] = rgb.z; rgba_out[4 * i + 3] = rgba_in[4 * i + 3];
+        }
+    return 0;
+}
+}
