@@ -1,0 +1,63 @@
+"""Coverage guard (no GPU): every mifx_*_execute* entry point of include/mifx.h that takes a caller image -- directly or through its argument struct -- is run at
+the boundary frame sizes (tests/test_gpu_frame_edges.py SIZE_MATRIX) and in every caller-plane layout (tests/test_gpu_plane_layouts.py LAYOUT_MATRIX), or is
+listed below with the reason it is not.  A pass added to the ABI fails here until it has that coverage."""
+import ast
+import os
+import re
+
+from util import ROOT
+
+# entry point -> why it is not in the matrices
+EXCLUDED = {
+    "mifx_pbr_shade_execute_with_shadows": "the G-buffer and output addressing of mifx_pbr_shade_execute (the same kernel, one more shadow-map argument)",
+    "mifx_pbr_shade_execute_layers": "the G-buffer and output addressing of mifx_pbr_shade_execute; the layer planes are held to the checker by test_gpu_pbr_layers.py",
+    "mifx_pbr_shade_execute_frame_attribs": "mifx_pbr_shade_execute after a host-side conversion of the attribute block",
+    "mifx_pbr_shade_execute_native": "native-format G-buffer planes (mifx_native_image), pitched by test_gpu_pbr.py::test_pbr_shade_on_native_gbuffer",
+    "mifx_tonemap_execute_native": "mifx_tonemap_execute with a native-format target (mifx_native_image), pitched by test_formats.py",
+    "mifx_chain_execute_native": "mifx_chain_execute with a native-format target (mifx_native_image), pitched by test_formats.py",
+    "mifx_chain_execute_phase": "one row band of mifx_chain_execute's frame; test_gpu_sharded.py holds every band to the whole frame",
+    "mifx_chain_execute_sharded": "row bands of mifx_chain_execute's frame over a communicator; test_gpu_sharded.py",
+    "mifx_chain_execute_band": "one row band of mifx_chain_execute's frame without exchanges; test_gpu_sharded.py",
+}
+
+
+def _header():
+    with open(os.path.join(ROOT, "include", "mifx.h")) as f:
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+
+
+def image_taking_executes():
+    src = _header()
+    structs = {m.group(2): m.group(1) for m in re.finditer(r"typedef struct \w*\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S)}
+    holds = {"mifx_image2d"}
+    for _ in range(4):  # structs that hold an image, or a struct that does
+        holds |= {name for name, body in structs.items() if any(re.search(rf"\b{t}\b", body) for t in holds)}
+    found = set()
+    for m in re.finditer(r"MIFX_API\s+mifx_status\s+(mifx_\w*_execute\w*)\s*\((.*?)\)\s*;", src, flags=re.S):
+        if any(re.search(rf"\b{t}\b", m.group(2)) for t in holds):
+            found.add(m.group(1))
+    return found
+
+
+def _matrix(module, name):
+    with open(os.path.join(ROOT, "tests", module)) as f:
+        tree = ast.parse(f.read())
+    for node in tree.body:
+        if isinstance(node, ast.Assign) and any(isinstance(t, ast.Name) and t.id == name for t in node.targets):
+            return ast.literal_eval(node.value), {n.name for n in tree.body if isinstance(n, ast.FunctionDef)}
+    raise AssertionError(f"{module} has no {name}")
+
+
+def test_every_image_pass_has_edge_and_layout_coverage():
+    entries = image_taking_executes()
+    assert {"mifx_ssao_execute", "mifx_ssr_execute", "mifx_chain_execute", "mifx_tonemap_execute", "mifx_selection_execute"} <= entries  # (the parser sees them)
+    assert set(EXCLUDED) <= entries, f"stale exclusions: {sorted(set(EXCLUDED) - entries)}"
+    for module, name in (("test_gpu_frame_edges.py", "SIZE_MATRIX"), ("test_gpu_plane_layouts.py", "LAYOUT_MATRIX")):
+        matrix, tests = _matrix(module, name)
+        missing = sorted(entries - set(matrix) - set(EXCLUDED))
+        assert not missing, f"{module}: no {name} entry for {missing} (add the pass to the matrix, or to EXCLUDED with a reason)"
+        assert not set(matrix) & set(EXCLUDED), f"{module}: both covered and excluded: {sorted(set(matrix) & set(EXCLUDED))}"
+        for entry, names in matrix.items():
+            assert entry in entries, f"{module}: {entry} is not an image-taking execute of include/mifx.h"
+            for t in names.split(", "):
+                assert t in tests, f"{module}: {name}[{entry!r}] names {t}, which the module does not define"

@@ -116,12 +116,16 @@ def test_bloom_temporal_upscaling_output_size(mifx_lib):
 
 @pytest.mark.parametrize("flags", list(range(8)))
 def test_taa_multi_frame(mifx_lib, flags):
+    taa_multi_frame(flags)
+
+
+def taa_multi_frame(flags, size=(176, 100)):
     """Five frames; each frame's HIP output is compared with the checker fed with the HIP history (per-pass isolation),
     and the checker's independent history is compared end to end."""
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker(f"taa_flags{flags}")
-    w, h = 176, 100
+    w, h = size
     sobol, tile = blue_noise_tables()
     ctx = api.PostFXContext(0, sobol, tile)
     taa = api.TemporalAntiAliasing(ctx)

@@ -44,11 +44,16 @@ def test_ibl_precompute_parity(mifx_lib):
 def test_chain_vs_cpu_chain(mifx_lib):
     """6 frames of the full chain.  Every stochastic / temporal stage runs independently on both sides, so flipped SSR rays and
     thresholded decisions accumulate: the final LDR image must agree on all but a small fraction of texel-channels."""
+    chain_vs_cpu_chain()
+
+
+def chain_vs_cpu_chain(size=(224, 128), frames=6):
+    """test_chain_vs_cpu_chain at any frame size and frame count (tests/test_gpu_frame_edges.py: the smallest frames the chain accepts)."""
     import chain_util
     from diligentfx_amd import api, synth
 
     lib, pfx = checker("pbr_shade")
-    w, h = 224, 128
+    w, h = size
     sobol, tile = blue_noise_tables()
     chain = api.Chain(0, sobol, tile)
     ibl_np = chain_util.make_ibl(lib, pfx)
@@ -59,7 +64,7 @@ def test_chain_vs_cpu_chain(mifx_lib):
     sa = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
     out = torch.zeros(h, w, 4, device=chain.device)
     fracs = []
-    for frame in range(6):
+    for frame in range(frames):
         f = synth.make_frame(scene, frame, w, h, chain.device)
         chain.execute(chain.bind_frame(frame, f, ibl, sa, out))
         want = chain_util.run_frame(cpu, scene, frame, w, h, ibl_np)

@@ -95,6 +95,12 @@ def read(dof, names):
 # 256x144: all three dilation levels in one launch; 100x60: two fused + one from an odd source; 202x118: odd first level (three-texel footprints)
 @pytest.mark.parametrize("size,flags,rings", [((256, 144), 0, (5, 7)), ((256, 144), 3, (5, 7)), ((202, 118), 1, (3, 4)), ((100, 60), 2, (2, 2)), ((202, 118), 0, (4, 6))])
 def test_dof_per_pass_and_output(mifx_lib, size, flags, rings):
+    dof_per_pass_and_output(size, flags, rings)
+
+
+def dof_per_pass_and_output(size, flags, rings, frames=(7, 8, 9), edge=False):
+    """The per-pass comparison at any frame size (tests/test_gpu_frame_edges.py runs it at the boundary sizes).  edge: the frame may be too small to hold a
+    visibly blurred texel; every comparison stays as it is."""
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker()
@@ -110,7 +116,7 @@ def test_dof_per_pass_and_output(mifx_lib, size, flags, rings):
     e2e_chain = cpu_chain.CpuChain(lib, pfx)
     prev_temporal = np.zeros((h, w), np.float32)
     worst = {}
-    for frame in (7, 8, 9):
+    for frame in frames:
         f = synth.make_frame(scene, frame, w, h, ctx.device)
         cam = lens_camera(f["camera"])
         color = hdr_colour(f, ctx.device)
@@ -169,7 +175,7 @@ def test_dof_per_pass_and_output(mifx_lib, size, flags, rings):
         want = e2e_chain.dof(pf, cnp, dnp, attribs, flags)
         # (measured on an MI355X: not one value beyond rtol, profiles/r03_parity_outliers_strict_vs_shipped.txt)
         assert_close(got, want, max_outlier_frac=0.0, what=f"DOF end to end frame {frame}")
-        assert np.isfinite(got).all() and np.abs(got[..., :3] - cnp[..., :3]).max() > 0.05
+        assert np.isfinite(got).all() and (edge or np.abs(got[..., :3] - cnp[..., :3]).max() > 0.05)
     print("max rel err per pass:", {k: f"{v:.1e}" for k, v in worst.items()})
     dof.close()
     ctx.close()

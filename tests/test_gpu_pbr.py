@@ -40,6 +40,11 @@ def ibl_to_device(ibl_np, device):
 @pytest.mark.parametrize("size", [(160, 96), (131, 77)])
 @pytest.mark.parametrize("extras", [False, True])
 def test_pbr_shade(mifx_lib, ibl_np, size, extras):
+    pbr_shade(ibl_np, size, extras)
+
+
+def pbr_shade(ibl_np, size, extras, edge=False):
+    """The shade against the checker at any frame size (edge: the frame may hold no lit texel; every comparison stays)."""
     import chain_util
     from diligentfx_amd import api, synth
 
@@ -69,7 +74,7 @@ def test_pbr_shade(mifx_lib, ibl_np, size, extras):
     # cube-face selection and the nearest-texel re-projection at face edges are discontinuous in the direction
     assert_close(to_np(rad), wr, max_outlier_frac=0.0, what="radiance")
     assert_close(to_np(spec), ws, max_outlier_frac=0.0, what="specular IBL")
-    assert float(to_np(rad)[..., :3].max()) > 0.5 and np.isfinite(to_np(rad)).all()
+    assert (edge or float(to_np(rad)[..., :3].max()) > 0.5) and np.isfinite(to_np(rad)).all()
     # no specular-IBL target requested: same radiance
     rad2, none = api.pbr_shade(ctx, g, f["camera"], sa, ibl_to_device(ibl_np, ctx.device), background=bg, want_specular_ibl=False)
     assert none is None and torch.allclose(rad2, rad, rtol=1e-5, atol=1e-6)
@@ -178,10 +183,14 @@ def test_pbr_shade_argument_errors(mifx_lib, ibl_np):
 
 @pytest.mark.parametrize("tm_mode", [0, 4, 8])
 def test_composite(mifx_lib, ibl_np, tm_mode):
+    composite(ibl_np, tm_mode)
+
+
+def composite(ibl_np, tm_mode, size=(150, 90)):
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker("composite")
-    w, h = 150, 90
+    w, h = size
     ctx = api.PostFXContext(0)
     f = synth.make_frame(synth.Scene(), 2, w, h, ctx.device)
     gen = torch.Generator(device="cpu").manual_seed(11)

@@ -107,11 +107,16 @@ def test_native_storage_build_gives_the_same_plane(mifx_lib, tmp_path):
 
 @pytest.mark.parametrize("tm_mode", [0, 4])
 def test_selection_composite_equals_the_restatement_on_the_composite(mifx_lib, tm_mode):
+    selection_composite(tm_mode)
+
+
+def selection_composite(tm_mode, size=(150, 90), edge=False):
+    """The composite with the selection tail against the restatement at any frame size (edge: the frame may be too small for the tail to change a texel)."""
     import torch
 
     from diligentfx_amd import api, binding as B, synth
 
-    w, h = 150, 90
+    w, h = size
     ctx = api.PostFXContext(0)
     f = synth.make_frame(synth.Scene(), 2, w, h, ctx.device)
     ibl = api.precompute_ibl(ctx, synth.make_sky_cube(16, ctx.device), lut_size=32, irradiance_size=8, prefiltered_size=16, lut_samples=32, diffuse_samples=64,
@@ -135,7 +140,7 @@ def test_selection_composite_equals_the_restatement_on_the_composite(mifx_lib, t
     cl = closest.cpu().numpy()
     want = S.composite_tail(plain, depth, sel, cl, list(a.outline_color)[:3], list(a.occluded_outline_color)[:3], 0.4, 1.0, 5.0)
     assert_close(got, want, what=f"selection composite tm={tm_mode}")
-    assert not np.array_equal(got, plain)
+    assert edge or not np.array_equal(got, plain)
     fx.close()
     ctx.close()
 

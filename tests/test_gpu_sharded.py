@@ -16,7 +16,8 @@ SHAPES = [(2, 640, 768, None, 0), (3, 640, 768, None, 0), (4, 512, 1536, None, 0
           (3, 640, 768, None, 2), (2, 600, 750, (0, 350, 750), 2), (3, 640, 768, None, "ae"), (2, 600, 750, (0, 350, 750), "ae"),
           (4, 640, 768, (0, 340, 372, 410, 768), 0),  # two bands of 32 / 38 rows: thinner than every history halo, ghost rows come from two ranks away
           (3, 640, 768, None, "dof"), (2, 600, 750, (0, 350, 750), "dof"),  # depth of field (temporal smoothing + Karis weights) between TAA and Bloom
-          (3, 640, 768, (0, 330, 520, 768), "layers")]  # mifx_chain_set_material_layers: all five layers + two shadow-mapped lights in the shade and in the SSR hit fetch
+          (3, 640, 768, (0, 330, 520, 768), "layers"),  # mifx_chain_set_material_layers: all five layers + two shadow-mapped lights in the shade and in the SSR hit fetch
+          (3, 640, 768, (0, 376, 392, 768), 0)]  # a band of 16 rows (the band setters take any non-empty band): its whole halo comes from its neighbours
 
 
 class LocalComm:
@@ -299,16 +300,41 @@ def test_execute_band_is_the_phases_without_the_exchanges(mifx_lib, overlap, ae)
     """mifx_chain_execute_band (what tools/shard_cost.py and TiledChain.calibrate_cuts time): one rank's band through the phases -- and with overlap >= 2 the two lanes across
     frames -- of mifx_chain_execute_sharded, exchanges left out.  Against a second chain object on the same band driven phase by phase: the band's rows of every frame and all five
     history planes (whole: both hold the same stale ghost rows) are equal bit for bit, frames queued back to back."""
-    from diligentfx_amd import api, synth
-
     dev = torch.device("cuda", 0)
+    band_against_phases(dev, overlap, ae, _band_ibl(dev))
+
+
+@pytest.mark.parametrize("overlap,ae", [(0, False), (3, True)])
+def test_execute_band_on_cuts_at_multiples_of_16(mifx_lib, overlap, ae):
+    """test_execute_band_is_the_phases_without_the_exchanges with band cuts on multiples of 16 rows (0, 256, 512, 768): the rows a band's pyramid levels start on then fall
+    on the levels' own block boundaries, which the cuts above (0, 250, 520, 768) never do."""
+    dev = torch.device("cuda", 0)
+    band_against_phases(dev, overlap, ae, _band_ibl(dev), cuts=(0, 256, 512, H))
+
+
+def _band_ibl(dev):
+    from diligentfx_amd import api, synth
 
     def make_ibl(chain):
         ibl = api.precompute_ibl(chain.postfx, synth.make_sky_cube(32, dev).clamp(max=200.0), lut_size=32, irradiance_size=8, prefiltered_size=32,
                                  lut_samples=32, diffuse_samples=32, specular_samples=16)
         return ibl, len(ibl.pre)
 
-    band_against_phases(dev, overlap, ae, make_ibl)
+    return make_ibl
+
+
+def test_empty_row_band_is_refused(mifx_lib):
+    """The thinnest band the chain takes is one row (tests above: 16); an empty or inverted band is a clean INVALID_ARG, before any launch."""
+    from diligentfx_amd import api, binding as B
+    from util import blue_noise_tables
+
+    sobol, tile = blue_noise_tables()
+    c = api.Chain(0, sobol, tile)
+    with pytest.raises(B.MifxError, match="INVALID_ARG"):
+        c.set_row_band(40, 39, MAX_MOTION_ROWS)
+    with pytest.raises(B.MifxError, match="INVALID_ARG"):
+        c.set_row_band(-1, 16, MAX_MOTION_ROWS)
+    c.close()
 
 
 def _fake_rccl(tmp_path):

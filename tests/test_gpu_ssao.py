@@ -29,6 +29,12 @@ def checker():
                                                           ((160, 96), "vbao", False, False, True), ((152, 90), "gtao", True, False, True), ((144, 88), "gtao", False, True, True),
                                                           ((160, 96), "gtao", False, False, False), ((135, 70), "gtao", False, False, False)])
 def test_ssao_per_pass_parity(mifx_lib, size, algo, rev, halfprec, fused):
+    ssao_per_pass(size, algo, rev, halfprec, fused)
+
+
+def ssao_per_pass(size, algo, rev, halfprec, fused, frames=4, edge=False):
+    """The per-pass comparison at any frame size (tests/test_gpu_frame_edges.py runs it at the boundary sizes).  edge: the frame may be too small to
+    contain a texel that takes the walk path of A7; every comparison stays as it is."""
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker()
@@ -46,7 +52,7 @@ def test_ssao_per_pass_parity(mifx_lib, size, algo, rev, halfprec, fused):
     chain = cpu_chain.CpuChain(lib, pfx, algorithm=algo)
     worst = {}
     walked = 0
-    for frame in range(4):
+    for frame in range(frames):
         f = synth.make_frame(scene, frame, w, h, ctx.device, reversed_depth=rev)
         ctx.prepare_resources(frame, w, h, feature_flags=(1 if rev else 0) | (2 if halfprec else 0))
         ssao.prepare_resources(feature_flags=1 if halfprec else 0)
@@ -107,7 +113,7 @@ def test_ssao_per_pass_parity(mifx_lib, size, algo, rev, halfprec, fused):
         cmp("A8", out, want)
         assert np.array_equal(g("history_ao"), out)  # the history write-back of the resolve
         prev_ao, prev_len = out.copy(), g("history_len").copy()
-    assert walked > 0  # the walk path was exercised
+    assert walked > 0 or edge  # the walk path was exercised
     print("worst outlier fractions:", {k: v for k, v in worst.items() if v > 0})
     ssao.close()
     ctx.close()
@@ -227,7 +233,11 @@ def test_ssao_full_size_parity(mifx_lib):
 
 @pytest.mark.parametrize("size,algorithm,first", [((160, 96), "gtao", 0), ((150, 92), "gtao", 0), ((160, 96), "hbao", 0), ((150, 92), "vbao", 0), ((70, 36), "gtao", 47)])
 def test_ssao_half_resolution(mifx_lib, size, algorithm, first):
-    """FEATURE_FLAG_HALF_RESOLUTION: A1 checkerboard depth (bit-exact), pyramid + GTAO at half size, A4 bilateral upsampling, the full-size tail;
+    ssao_half_resolution(size, algorithm, first)
+
+
+def ssao_half_resolution(size, algorithm, first, frames=3, edge=False):
+    """FEATURE_FLAG_HALF_RESOLUTION at any frame size (edge: the frame may be too small to hold an occluded texel): A1 checkerboard depth (bit-exact), pyramid + GTAO at half size, A4 bilateral upsampling, the full-size tail;
     every new pass against the checker on the HIP path's own inputs, the result against the checker's own run of the effect.
     The case that starts at camera position 47 (found by the random sequences of test_gpu_host_sequence.py) has a floor at a glancing angle at
     position 48: the nine depth weights of A4 are exp(-103.8) on whole rows, 0.6 of the smallest denormal number (ssao.hip, the comment in A4)."""
@@ -243,7 +253,7 @@ def test_ssao_half_resolution(mifx_lib, size, algorithm, first):
     scene = synth.Scene()
     attribs = B.SSAOAttribs.default()
     attribs.Algorithm = {"gtao": 0, "hbao": 1, "vbao": 2}[algorithm]
-    for frame in range(first, first + 3):
+    for frame in range(first, first + frames):
         f = synth.make_frame(scene, frame, w, h, ctx.device)
         ctx.prepare_resources(frame, w, h)
         ssao.prepare_resources(feature_flags=2)
@@ -288,6 +298,6 @@ def test_ssao_half_resolution(mifx_lib, size, algorithm, first):
         assert out.shape == (h, w)
         # (measured 1.95e-4 on an MI355X in both the shipped and the strict build: profiles/r03_parity_outliers_strict_vs_shipped.txt)
         assert_close(out, want, max_outlier_frac=4e-4, what=f"half-res SSAO end to end frame {frame}")  # (measured 1.95e-4)
-        assert out.min() < 0.9 and np.isfinite(out).all()
+        assert (edge or out.min() < 0.9) and np.isfinite(out).all()
     ssao.close()
     ctx.close()

@@ -31,6 +31,12 @@ def scene_color(f):
 # flags 1: FEATURE_FLAG_PREVIOUS_FRAME; rev: PostFXContext::FEATURE_FLAG_REVERSED_DEPTH (SSR_OPTION_INVERTED_DEPTH)
 @pytest.mark.parametrize("size,mdm,flags,rev", [((192, 112), 0, 0, False), ((150, 85), 1, 0, False), ((192, 112), 0, 1, False), ((176, 100), 0, 0, True)])
 def test_ssr_per_pass_parity(mifx_lib, size, mdm, flags, rev):
+    ssr_per_pass(size, mdm, flags, rev)
+
+
+def ssr_per_pass(size, mdm, flags, rev, frames=3, edge=False):
+    """The per-pass comparison at any frame size (tests/test_gpu_frame_edges.py runs it at the boundary sizes).  edge: the frame may be too small for the content
+    checks (a mix of reflective and rough texels, rays that hit, a hit that moves); every comparison stays as it is."""
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker()
@@ -49,7 +55,7 @@ def test_ssr_per_pass_parity(mifx_lib, size, mdm, flags, rev):
     res_before = [np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)]
     slot_before = {0: (np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32)), 1: (np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32))}
     worst = {}
-    for frame in range(3):
+    for frame in range(frames):
         f = synth.make_frame(scene, frame, w, h, ctx.device, reversed_depth=rev)
         color = scene_color(f)
         ctx.prepare_resources(frame, w, h, feature_flags=1 if rev else 0)
@@ -75,7 +81,7 @@ def test_ssr_per_pass_parity(mifx_lib, size, mdm, flags, rev):
         cc.call("ssr_mask_roughness", [material, depth], [wr, wm], attribs=ab)
         rough, mask = g("roughness"), g("mask")
         assert np.array_equal(rough, wr) and np.array_equal(mask, wm)
-        assert 0.05 < mask.mean() < 0.95
+        assert edge or 0.05 < mask.mean() < 0.95
         # R4: a data-dependent ray march -- single-ulp differences can change a tile-crossing decision and the ray then lands on another
         # texel; such rays are rare and show up as outliers of the per-pixel comparison
         ws, wd = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
@@ -87,10 +93,10 @@ def test_ssr_per_pass_parity(mifx_lib, size, mdm, flags, rev):
         if flags & 1:  # the variant really reads another texel for moving hits
             w0s, w0d = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
             lib.call(pfx + "ssr_intersection", r4_in, [w0s, w0d], cam0=cam, attribs=ab, **({} if pfx == "ref_" else {"ival": [0]}))
-            assert np.array_equal(w0d, wd) and (frame == 0 or not np.array_equal(w0s, ws))
+            assert np.array_equal(w0d, wd) and (frame == 0 or edge or not np.array_equal(w0s, ws))
         cmp("R4 specular", g("ray_radiance"), ws)
         cmp("R4 dir/pdf", g("ray_dir_pdf"), wd)
-        assert (g("ray_radiance")[..., 3] > 0).mean() > 0.01  # some rays hit
+        assert edge or (g("ray_radiance")[..., 3] > 0).mean() > 0.01  # some rays hit
         # R5
         w0, w1, w2 = (a.copy() for a in res_before)
         cc.call("ssr_spatial_reconstruction", [rough, normal, depth, g("ray_dir_pdf"), g("ray_radiance"), mask], [w0, w1, w2], cam0=cam, attribs=ab)
@@ -165,7 +171,11 @@ def test_ssr_protocol_errors(mifx_lib):
 
 @pytest.mark.parametrize("size", [(192, 112), (151, 89)])
 def test_ssr_half_resolution(mifx_lib, size):
-    """FEATURE_FLAG_HALF_RESOLUTION: R3 half-size mask (bit-exact), R4 at half size (one pixel of every 2x2 block, ComputeHalfResolutionOffset), R5 on the half-size ray
+    ssr_half_resolution(size)
+
+
+def ssr_half_resolution(size, frames=3, edge=False):
+    """FEATURE_FLAG_HALF_RESOLUTION at any frame size (edge: as ssr_per_pass): R3 half-size mask (bit-exact), R4 at half size (one pixel of every 2x2 block, ComputeHalfResolutionOffset), R5 on the half-size ray
     textures; every changed pass against the checker on the HIP path's own inputs, the effect against the checker's own run."""
     from diligentfx_amd import api, binding as B, synth
 
@@ -180,7 +190,7 @@ def test_ssr_half_resolution(mifx_lib, size):
     attribs = B.SSRAttribs.default()
     ab = bytes(attribs)
     res_before = [np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)]  # (R5's targets keep their content outside the mask: ssr.hip)
-    for frame in range(3):
+    for frame in range(frames):
         f = synth.make_frame(scene, frame, w, h, ctx.device)
         color = scene_color(f)
         ctx.prepare_resources(frame, w, h)
@@ -196,7 +206,7 @@ def test_ssr_half_resolution(mifx_lib, size):
         want = np.zeros((hh, hw), np.float32)
         cc.call("ssr_downsampled_mask", [rough, depth], [want], attribs=ab)
         half_mask = g("mask_half")
-        assert np.array_equal(half_mask, want) and 0.05 < half_mask.mean() < 0.95
+        assert np.array_equal(half_mask, want) and (edge or 0.05 < half_mask.mean() < 0.95)
         # R4 at half size
         ws, wd = np.zeros((hh, hw, 4), np.float32), np.zeros((hh, hw, 4), np.float32)
         r4_in = [to_np(color), normal, rough, to_np(ctx.get_2d_blue_noise(0)), hiz, half_mask, motion]
@@ -207,7 +217,7 @@ def test_ssr_half_resolution(mifx_lib, size):
         assert g("ray_radiance").shape == (hh, hw, 4)
         assert_close(g("ray_radiance"), ws, max_outlier_frac=0.0, what=f"half-res R4 specular frame {frame}")
         assert_close(g("ray_dir_pdf"), wd, max_outlier_frac=0.0, what=f"half-res R4 dir/pdf frame {frame}")
-        assert (g("ray_radiance")[..., 3] > 0).mean() > 0.01
+        assert edge or (g("ray_radiance")[..., 3] > 0).mean() > 0.01
         # R5 on the half-size ray textures
         w0, w1, w2 = (a.copy() for a in res_before)
         r5_in = [rough, normal, depth, g("ray_dir_pdf"), g("ray_radiance"), mask]
