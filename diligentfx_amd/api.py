@@ -156,6 +156,19 @@ class PostFXContext:
                                               ctypes.c_uint32(flags)))
         return out
 
+    def copy_frame(self, color, depth, camera: B.CameraAttribs, tone_mapping: B.ToneMappingAttribs, ave_log_lum, tonemap_flags=0, grid: "B.CoordinateGridAttribs | None" = None,
+                   grid_feature_flags=0, out=None):
+        """The copy-frame draw with the coordinate grid (mifx_copy_frame_render, Hydrogent/shaders/HnCopyFrame.psh:27-63): ToneMap, the grid and axes over the 3x3 depth
+        range, optional sRGB.  grid None or no plane / axis flag: the plain tone map."""
+        if out is None:
+            out = torch.empty_like(color)
+        c, o = B.image(color), B.image(out)
+        d = B.image(depth) if depth is not None else None
+        B.check(self.lib.mifx_copy_frame_render(self.handle, ctypes.byref(c), ctypes.byref(d) if d is not None else None, ctypes.byref(camera) if camera is not None else None,
+                                                ctypes.byref(tone_mapping), ctypes.c_float(ave_log_lum), ctypes.c_uint32(tonemap_flags),
+                                                ctypes.byref(grid) if grid is not None else None, ctypes.c_uint32(grid_feature_flags), ctypes.byref(o)))
+        return out
+
     def tone_map_native(self, hdr, attribs: B.ToneMappingAttribs, ave_log_lum, fmt: str, flags=0, pitch_bytes=None):
         """ToneMap() stored in the target's own format (mifx_tonemap_execute_native): torch.uint8 (H, pitch_bytes), bit-identical to
         image_export(tone_map(...), fmt) without the fp32 intermediate."""
@@ -404,6 +417,29 @@ def composite(ctx: "PostFXContext", color, specular_ibl, ssr, ssao, normal, base
     ctx.sync_stream()
     B.check(ctx.lib.mifx_composite_execute(ctx.handle, ctypes.byref(a), ctypes.byref(o)))
     return out
+
+
+class CoordinateGridRenderer:
+    """Components/CoordinateGridRenderer: the world-space grid planes and the X / Y / Z axes over a depth buffer (mifx_coordinate_grid_render)."""
+
+    def __init__(self, ctx: "PostFXContext"):
+        self.ctx = ctx
+
+    def render(self, depth, camera: B.CameraAttribs, attribs: "B.CoordinateGridAttribs | None", feature_flags, color_target=None, raw=False):
+        """CoordinateGridRenderer::Render.  color_target: blended in place (rgb; its alpha is left as it is).  raw: also return the shader's own RGBA as a float32
+        (H, W, 4) tensor (the only output when there is no colour target)."""
+        out = None
+        if raw or color_target is None:
+            out = torch.empty((depth.shape[0], depth.shape[1], 4), dtype=torch.float32, device=depth.device)
+        d = B.image(depth)
+        t = B.image(color_target) if color_target is not None else None
+        o = B.image(out) if out is not None else None
+        if o is not None:
+            o.format = B.FORMAT_F32X4  # (fp32 texels in every build of the library)
+        B.check(self.ctx.lib.mifx_coordinate_grid_render(self.ctx.handle, ctypes.byref(d), ctypes.byref(camera), ctypes.byref(attribs) if attribs is not None else None,
+                                                         ctypes.c_uint32(feature_flags), ctypes.byref(t) if t is not None else None,
+                                                         ctypes.byref(o) if o is not None else None))
+        return out if out is not None else color_target
 
 
 def composite_selection(ctx: "PostFXContext", color, specular_ibl, ssr, ssao, normal, base_color, material, lut, camera, depth, selection_depth, closest_location,
@@ -917,6 +953,10 @@ class Chain:
         d = B.image(selection_depth)
         self._selection_keep = (selection_depth, attribs)
         B.check(self.lib.mifx_chain_set_selection(self.handle, ctypes.byref(attribs), ctypes.byref(d)))
+
+    def set_coordinate_grid(self, attribs: "B.CoordinateGridAttribs | None", grid_feature_flags=0):
+        """The coordinate grid and axes in the frame's last pass (mifx_chain_set_coordinate_grid; HnPostProcessTaskParams::Grid / GridFeatureFlags); None turns it off."""
+        B.check(self.lib.mifx_chain_set_coordinate_grid(self.handle, ctypes.byref(attribs) if attribs is not None else None, ctypes.c_uint32(grid_feature_flags)))
 
     def auto_exposure_average(self):
         h = ctypes.c_void_p()

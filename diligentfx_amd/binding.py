@@ -261,6 +261,33 @@ class SelectionCompositeInputs(ctypes.Structure):  # mifx_selection_composite_in
     _fields_ = [("depth", PImage), ("selection_depth", PImage), ("closest_location", PImage), ("attribs", ctypes.POINTER(SelectionAttribs))]
 
 
+class CoordinateGridAttribs(ctypes.Structure):
+    """mifx_coordinate_grid_attribs -- CoordinateGridAttribs (Shaders/Common/public/CoordinateGridStructures.fxh:6-29), 192 bytes"""
+    _fields_ = [("PositiveXAxisColor", c_f * 4), ("PositiveYAxisColor", c_f * 4), ("PositiveZAxisColor", c_f * 4), ("NegativeXAxisColor", c_f * 4),
+                ("NegativeYAxisColor", c_f * 4), ("NegativeZAxisColor", c_f * 4), ("XAxisWidth", c_f), ("YAxisWidth", c_f), ("ZAxisWidth", c_f), ("Padding0", c_f),
+                ("GridMajorColor", c_f * 4), ("GridMinorColor", c_f * 4), ("GridScale", c_f * 4), ("GridSubdivision", c_f * 4), ("GridLineWidth", c_f),
+                ("GridMinCellWidth", c_f), ("GridMinCellSize", c_f), ("Padding1", c_f)]
+
+    @classmethod
+    def default(cls):
+        """The reference's DEFAULT_VALUEs (what mifx_coordinate_grid_default_attribs writes)."""
+        return cls((c_f * 4)(1, 0, 0, 1), (c_f * 4)(0, 1, 0, 1), (c_f * 4)(0, 0, 1, 1), (c_f * 4)(0.40, 0.15, 0.15, 1), (c_f * 4)(0.15, 0.40, 0.15, 1),
+                   (c_f * 4)(0.15, 0.15, 0.40, 1), 3.0, 3.0, 3.0, 0.0, (c_f * 4)(0.4, 0.4, 0.4, 1), (c_f * 4)(0.1, 0.1, 0.1, 1), (c_f * 4)(1, 1, 1, 0),
+                   (c_f * 4)(10, 10, 10, 0), 2.0, 4.0, 0.0001, 0.0)
+
+
+# CoordinateGridRenderer::FEATURE_FLAGS (CoordinateGridRenderer.hpp:59-71)
+COORDINATE_GRID_FEATURE_FLAG_NONE = 0
+COORDINATE_GRID_FEATURE_FLAG_CONVERT_TO_SRGB = 1
+COORDINATE_GRID_FEATURE_FLAG_RENDER_PLANE_YZ = 2
+COORDINATE_GRID_FEATURE_FLAG_RENDER_PLANE_XZ = 4
+COORDINATE_GRID_FEATURE_FLAG_RENDER_PLANE_XY = 8
+COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_X = 16
+COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_Y = 32
+COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_Z = 64
+COORDINATE_GRID_DEBUG_FLAG_COORD = 256  # (not in the reference: the raw output holds Coord and fwidth(Coord))
+
+
 class ChainFrame(ctypes.Structure):
     _fields_ = [("frame", FrameDesc), ("gbuffer", GBuffer), ("motion", PImage), ("prev_depth", PImage),
                 ("curr_camera", ctypes.POINTER(CameraAttribs)), ("prev_camera", ctypes.POINTER(CameraAttribs)),
@@ -275,7 +302,7 @@ SIZEOF_NAMES = {
     "ssao_attribs": SSAOAttribs, "ssr_attribs": SSRAttribs, "bloom_attribs": BloomAttribs, "dof_attribs": DOFAttribs, "taa_attribs": TAAAttribs,
     "pbr_light_attribs": PBRLightAttribs, "pbr_shade_attribs": PBRShadeAttribs, "frame_desc": FrameDesc, "chain_frame": ChainFrame,
     "composite_attribs": CompositeAttribs, "gbuffer": GBuffer, "ibl": IBL, "pbr_shadow_map_info": PBRShadowMapInfo,
-    "selection_attribs": SelectionAttribs, "selection_composite_inputs": SelectionCompositeInputs,
+    "selection_attribs": SelectionAttribs, "selection_composite_inputs": SelectionCompositeInputs, "coordinate_grid_attribs": CoordinateGridAttribs,
 }
 
 _lib = None

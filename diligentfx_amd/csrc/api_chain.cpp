@@ -5,6 +5,7 @@
 // final copy-frame pass because TAA is on (HnPostProcessTask.cpp:172, :920-927).  Everything is recorded on the context stream.
 #include "mifx_objects.h"
 #include "mifx_selection_host.h"
+#include "mifx_grid_host.h"
 #include <cstdlib>
 #include <cmath>
 #include <string>
@@ -562,6 +563,15 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
     return MIFX_OK;
 }
 
+// mifx_chain_set_coordinate_grid: the copy-frame draw with the grid (HnCopyFrame.psh:27-63) on the Bloom output, the G-buffer depth and the frame's camera, on the rows the
+// context needs; fAveLogLum from the auto-exposure object when the chain has one.  Whole-frame pixel coordinates and a depth plane every rank holds whole: a row band
+// equals the rows of the unsharded frame.
+static mifx_status chain_copy_frame_grid(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* bloom_out, const mifx_image2d* out_ldr)
+{
+    return copy_frame_grid_run(chain->ctx, bloom_out, f->gbuffer.depth, f->curr_camera, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->auto_exposure, chain->grid_attribs,
+                               chain->grid_flags, out_ldr, "mifx_chain_execute");
+}
+
 // Bloom::Execute on the TAA (or depth-of-field) output (HnPostProcessTask.cpp:911-918) and the copy-frame draw = ToneMap (+ sRGB) (:920-926)
 static mifx_status chain_bloom_and_tone_map(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d& taa_out, const mifx_image2d* out_ldr, const mifx_native_image* out_native,
                                             hipEvent_t between)
@@ -571,7 +581,8 @@ static mifx_status chain_bloom_and_tone_map(mifx_chain* chain, const mifx_chain_
     mifx_bloom_render_attribs ba{ctx, &taa_out, f->bloom};
     // With a plain fp32 target and a constant average luminance the copy-frame ToneMap() (:920-926) is the tail of Bloom's final up-sample: the Bloom output
     // is written as always, the LDR frame in the same pass (bit-identical to the two passes; the "tonemap" stage time is then part of "bloom").
-    const bool fuse_tone_map = out_native == nullptr && chain->auto_exposure == nullptr && chain->fuse_tone_map;
+    // (with the coordinate grid the frame's last pass is the copy-frame draw with the grid, which reads the Bloom output and the depth: not fused either)
+    const bool fuse_tone_map = out_native == nullptr && chain->auto_exposure == nullptr && chain->fuse_tone_map && !chain->has_grid;
     const mifx_bloom::FusedToneMap ftm{out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->fuse_bloom_output};
     MIFX_REQUIRE(chain->bloom->prepared, "mifx_chain_execute: bloom resources are not prepared");
     MIFX_CHECK(chain->bloom->run(&ba, 0, fuse_tone_map ? &ftm : nullptr));
@@ -583,13 +594,17 @@ static mifx_status chain_bloom_and_tone_map(mifx_chain* chain, const mifx_chain_
     {
         // the copy-frame target in its own format (the swap chain's in the reference): the conversion is the tail of the tone-map kernel
         MIFX_REQUIRE(chain->auto_exposure == nullptr, "mifx_chain_execute_native: not combined with auto exposure");
+        MIFX_REQUIRE(!chain->has_grid, "mifx_chain_execute_native: not combined with the coordinate grid");
         MIFX_CHECK(mifx_tonemap_execute_native(ctx, &bloom_out, out_native, f->tone_mapping, f->ave_log_lum, f->tonemap_flags));
     }
     else if (chain->auto_exposure)
     {
         MIFX_CHECK(mifx_autoexposure_execute(chain->auto_exposure, &bloom_out, chain->ae_elapsed, chain->ae_adapt ? 1 : 0));
-        MIFX_CHECK(mifx_tonemap_execute_auto(ctx, &bloom_out, out_ldr, f->tone_mapping, chain->auto_exposure, f->tonemap_flags));
+        if (chain->has_grid) MIFX_CHECK(chain_copy_frame_grid(chain, f, &bloom_out, out_ldr));
+        else MIFX_CHECK(mifx_tonemap_execute_auto(ctx, &bloom_out, out_ldr, f->tone_mapping, chain->auto_exposure, f->tonemap_flags));
     }
+    else if (chain->has_grid)
+        MIFX_CHECK(chain_copy_frame_grid(chain, f, &bloom_out, out_ldr));
     else
         MIFX_CHECK(mifx_tonemap_execute(ctx, &bloom_out, out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags));
     return MIFX_OK;
@@ -604,6 +619,7 @@ extern "C" mifx_status mifx_chain_execute(mifx_chain* chain, const mifx_chain_fr
 extern "C" mifx_status mifx_chain_execute_native(mifx_chain* chain, const mifx_chain_frame* f, const mifx_native_image* out_native)
 {
     MIFX_REQUIRE(out_native != nullptr, "mifx_chain_execute_native: null output");
+    MIFX_REQUIRE(chain == nullptr || !chain->has_grid, "mifx_chain_execute_native: not combined with the coordinate grid (mifx_chain_set_coordinate_grid)");
     if (chain != nullptr && (chain->halo_ssao_pending || chain->halo_rest_pending)) chain->join_halos();
     return chain_execute_impl(chain, f, nullptr, out_native);
 }
@@ -774,13 +790,14 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
         MIFX_CHECK(launch_autoexposure_reduce(ctx->stream, ae->low_res.view(), static_cast<float*>(ae->average.data), chain->ae_elapsed, chain->ae_adapt ? 1 : 0));
         MIFX_CHECK(mifx_bloom_get_output(chain->bloom, &bloom_out));
         ctx->need = r.band;
+        if (chain->has_grid) return chain_copy_frame_grid(chain, f, &bloom_out, out_ldr);
         return mifx_tonemap_execute_auto(ctx, &bloom_out, out_ldr, f->tone_mapping, ae, f->tonemap_flags);
     }
     MIFX_CHECK(mifx_taa_get_output(chain->taa, 0, &taa_out));
     if (chain->dof) MIFX_CHECK(mifx_dof_get_output(chain->dof, &taa_out)); // (computed in phase 2)
     ctx->need = r.need;
     ba.color  = &taa_out;
-    const bool fuse_tone_map = chain->fuse_tone_map && ae == nullptr;
+    const bool fuse_tone_map = chain->fuse_tone_map && ae == nullptr && !chain->has_grid;
     const mifx_bloom::FusedToneMap ftm{out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->fuse_bloom_output};
     MIFX_CHECK(chain->bloom->run(&ba, 2, fuse_tone_map ? &ftm : nullptr));
     if (fuse_tone_map) return MIFX_OK;
@@ -793,6 +810,7 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
         const Rows rows = mifx_autoexposure::sample_rows(r.band, int(H));
         return launch_autoexposure_rows(ctx->stream, color, ae->low_res.view(), rows.b, rows.e, packed);
     }
+    if (chain->has_grid) return chain_copy_frame_grid(chain, f, &bloom_out, out_ldr);
     return mifx_tonemap_execute(ctx, &bloom_out, out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags);
 }
 

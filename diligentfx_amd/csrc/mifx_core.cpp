@@ -239,6 +239,7 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("composite_attribs", mifx_composite_attribs);
     MIFX_SZ("selection_attribs", mifx_selection_attribs);
     MIFX_SZ("selection_composite_inputs", mifx_selection_composite_inputs);
+    MIFX_SZ("coordinate_grid_attribs", mifx_coordinate_grid_attribs);
     MIFX_SZ("gbuffer", mifx_gbuffer);
     MIFX_SZ("ibl", mifx_ibl);
     MIFX_SZ("shard_info", mifx_shard_info);

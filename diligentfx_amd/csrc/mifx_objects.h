@@ -377,6 +377,10 @@ struct mifx_chain
     mifx_selection_attribs selection_attribs{};
     mifx_image2d           selection_depth{};
     uint64_t               last_selection_id = 0; // the selected prim of the previous frame executed with selection on (a change resets TAA)
+    // mifx_chain_set_coordinate_grid: the copy-frame draw with the grid as the frame's last pass (grid.hip, reached through mifx::grid_hooks); the attribs are a copy
+    bool                         has_grid = false;
+    mifx_coordinate_grid_attribs grid_attribs{};
+    uint32_t                     grid_flags = 0;
     mifx_autoexposure* auto_exposure = nullptr; // optional: fAveLogLum of the final tone map from the average luminance of the Bloom output
     float        ae_elapsed = 0.0f;
     bool         ae_adapt   = true;

@@ -792,6 +792,59 @@ typedef struct mifx_selection_composite_inputs
 MIFX_API mifx_status mifx_composite_execute_selection(mifx_postfx* ctx, const mifx_composite_attribs* attribs, const mifx_selection_composite_inputs* selection,
                                                       const mifx_image2d* out);
 
+/* ------------------------------------------------------------------------------------------------ coordinate grid and axes (Components/CoordinateGridRenderer, HnCopyFrame.psh) */
+/* CoordinateGridAttribs -- Shaders/Common/public/CoordinateGridStructures.fxh:6-29 (192 bytes, byte-identical; defaults: mifx_coordinate_grid_default_attribs) */
+typedef struct mifx_coordinate_grid_attribs
+{
+    float PositiveXAxisColor[4]; /* (1, 0, 0, 1) */
+    float PositiveYAxisColor[4]; /* (0, 1, 0, 1) */
+    float PositiveZAxisColor[4]; /* (0, 0, 1, 1) */
+    float NegativeXAxisColor[4]; /* (0.40, 0.15, 0.15, 1) */
+    float NegativeYAxisColor[4]; /* (0.15, 0.40, 0.15, 1) */
+    float NegativeZAxisColor[4]; /* (0.15, 0.15, 0.40, 1) */
+    float XAxisWidth, YAxisWidth, ZAxisWidth; /* 3, in pixels */
+    float Padding0;
+    float GridMajorColor[4];  /* (0.4, 0.4, 0.4, 1) */
+    float GridMinorColor[4];  /* (0.1, 0.1, 0.1, 1) */
+    float GridScale[4];       /* (1, 1, 1, 0): YZ, XZ, XY */
+    float GridSubdivision[4]; /* (10, 10, 10, 0): YZ, XZ, XY */
+    float GridLineWidth;      /* 2, in pixels */
+    float GridMinCellWidth;   /* 4, in pixels */
+    float GridMinCellSize;    /* 0.0001 */
+    float Padding1;
+} mifx_coordinate_grid_attribs;
+/* CoordinateGridRenderer::FEATURE_FLAGS (Components/interface/CoordinateGridRenderer.hpp:59-71), the COORDINATE_GRID_* macros of CoordinateGrid.fxh:183-220 */
+enum
+{
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_NONE            = 0,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_CONVERT_TO_SRGB = 1,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_RENDER_PLANE_YZ = 2,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_RENDER_PLANE_XZ = 4,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_RENDER_PLANE_XY = 8,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_X   = 16,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_Y   = 32,
+    MIFX_COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_Z   = 64,
+    /* not in the reference, mifx_coordinate_grid_render with out_grid only: the texel is (Coord.x, Coord.y, fwidth(Coord).x, fwidth(Coord).y) of ComputeGrid
+     * (CoordinateGrid.fxh:50-51) for the first plane whose flag is set -- what a device-against-host comparison holds bit for bit */
+    MIFX_COORDINATE_GRID_DEBUG_FLAG_COORD             = 256
+};
+MIFX_API mifx_status mifx_coordinate_grid_default_attribs(mifx_coordinate_grid_attribs* out);
+/* CoordinateGridRenderer::Render (Components/src/CoordinateGridRenderer.cpp:221-284, Shaders/Common/private/CoordinateGridPS.psh:24-38): ComputeCoordinateGrid at
+ * NDC + camera->f2Jitter with MinDepth = MaxDepth = the pixel's depth, LinearToSRGB of its rgb with CONVERT_TO_SRGB.  depth: F32.  out_grid (F32X4 in every build of the
+ * library, may be NULL): the shader's result as it is.  color_target (the 4-channel texel of the build, may be NULL): the result blended as the renderer's
+ * BS_AlphaBlend state does, dst.rgb = grid.rgb * grid.a + dst.rgb * (1 - grid.a), dst.a left as it is.  Without a plane or axis flag out_grid is cleared to 0 and the
+ * colour target is left alone.  Pixel coordinates are those of the whole depth image; with a row band set on the context only its rows are written. */
+MIFX_API mifx_status mifx_coordinate_grid_render(mifx_postfx* ctx, const mifx_image2d* depth, const mifx_camera_attribs* camera, const mifx_coordinate_grid_attribs* attribs,
+                                                 uint32_t feature_flags, const mifx_image2d* color_target, const mifx_image2d* out_grid);
+/* The copy-frame draw of HnPostProcessTask.cpp:920-925 with the grid (Hydrogent/shaders/HnCopyFrame.psh:27-63), one launch: colour load, ToneMap, the minimum and
+ * maximum of the depth over the 3x3 neighbourhood (start values 1 / 0; a texel outside the frame reads 0), ComputeCoordinateGrid at NDC + camera->f2Jitter,
+ * lerp(colour, grid.rgb, grid.a), LinearToSRGB with MIFX_TONEMAP_FLAG_CONVERT_OUTPUT_TO_SRGB.  ave_log_lum goes to ToneMap as given, as for mifx_tonemap_execute.
+ * grid == NULL or no plane / axis flag in grid_feature_flags: mifx_tonemap_execute (depth and camera are then not read).  CONVERT_TO_SRGB in grid_feature_flags is
+ * not read: the frame's conversion is tonemap_flags'. */
+MIFX_API mifx_status mifx_copy_frame_render(mifx_postfx* ctx, const mifx_image2d* color, const mifx_image2d* depth, const mifx_camera_attribs* camera,
+                                            const mifx_tone_mapping_attribs* tone_mapping, float ave_log_lum, uint32_t tonemap_flags,
+                                            const mifx_coordinate_grid_attribs* grid, uint32_t grid_feature_flags, const mifx_image2d* out);
+
 /* ------------------------------------------------------------------------------------------------ whole chain (the caller: HnPostProcessTask::Execute, Hydrogent/src/Tasks/HnPostProcessTask.cpp:743-948) */
 typedef struct mifx_autoexposure mifx_autoexposure; /* auto exposure, declared below */
 typedef struct mifx_chain mifx_chain;
@@ -825,7 +878,7 @@ MIFX_API mifx_status mifx_chain_get_postfx(mifx_chain* chain, mifx_postfx** out)
  * "selection" (mifx_selection*, NULL until mifx_chain_set_selection turned it on) -- for their outputs and intermediates */
 MIFX_API mifx_status mifx_chain_get_effect(mifx_chain* chain, const char* name, void** out);
 /* mifx_chain_execute with the final image in the copy-frame target's own format (e.g. MIFX_NATIVE_FORMAT_RGBA8_UNORM_SRGB), see mifx_tonemap_execute_native.
- * Not available with a row band or together with mifx_chain_set_auto_exposure (MIFX_ERR_INVALID_ARG). */
+ * Not available with a row band, together with mifx_chain_set_auto_exposure or with mifx_chain_set_coordinate_grid (MIFX_ERR_INVALID_ARG). */
 MIFX_API mifx_status mifx_chain_execute_native(mifx_chain* chain, const mifx_chain_frame* f, const mifx_native_image* out_native);
 MIFX_API mifx_status mifx_chain_reset_history(mifx_chain* chain); /* SSAO, SSR, TAA: their own reset rules; depth of field: its temporal circle of confusion cleared (mifx_dof_reset_history); auto exposure: the adapted average back at 0.1 (mifx_autoexposure_reset) */
 /* Per-stage timing of the chain with HIP events recorded on the launch stream between the stages of mifx_chain_execute (the analogue of
@@ -858,6 +911,12 @@ MIFX_API mifx_status mifx_chain_set_material_layers(mifx_chain* chain, const mif
  * MIFX_CHAIN_FUSE_COMPOSITE_INTO_TAA the selection composite still runs as a pass of its own (TAA reads its plane).  attribs == NULL: off -- the chain launches exactly
  * what it launches without this call.  The effect object is mifx_chain_get_effect(chain, "selection") (NULL until selection was first turned on). */
 MIFX_API mifx_status mifx_chain_set_selection(mifx_chain* chain, const mifx_selection_attribs* attribs /* NULL = off */, const mifx_image2d* selection_depth);
+/* The coordinate grid in the chain (off by default; HnPostProcessTaskParams::Grid / GridFeatureFlags, HnPostProcessTask.cpp:181, 397, 856): the frame's last pass is
+ * the copy-frame draw with the grid (mifx_copy_frame_render) on the Bloom output, the G-buffer depth and frame.curr_camera; the tone map is then not fused into Bloom's
+ * last pass (as with auto exposure, whose average that pass reads from the device).  Works with every overlap mode, depth of field, selection, auto exposure and a row
+ * band (the G-buffer depth is whole on every rank: no exchange).  mifx_chain_execute_native with a grid set returns MIFX_ERR_INVALID_ARG.  The attribs are copied.
+ * attribs == NULL or no plane / axis flag: off -- the chain launches exactly what it launches without this call. */
+MIFX_API mifx_status mifx_chain_set_coordinate_grid(mifx_chain* chain, const mifx_coordinate_grid_attribs* attribs /* NULL = off */, uint32_t grid_feature_flags);
 /* Row-band sharding of one frame across the GPUs of a node. A chain with a row band [row_begin, row_end) produces those
  * rows of the output; every pass runs on the rows its consumers need (the band grown by the reach of everything downstream), the caller
  * moves two kinds of data (three with auto exposure) between the phases of mifx_chain_execute_phase (diligentfx_amd/tiling.py does it with RCCL):

@@ -1,0 +1,114 @@
+// TEST INFRASTRUCTURE ONLY.  The coordinate grid's per-pixel body (diligentfx_amd/csrc/mifx_coordinate_grid.h) compiled for the HOST (see layers_host.cpp for the method):
+//   * the stand-alone renderer's pixel (coordinate_grid_kernel's body) over a whole depth plane and at a list of pixels of a larger frame;
+//   * the copy-frame pass with the grid (copy_frame_grid_kernel's body: tone map, 3x3 depth range, grid, lerp, sRGB);
+//   * the intermediate terms that involve no transcendental (plane alpha, axis distances), for a bit-for-bit comparison with tests/grid_util.py.
+// Nothing in diligentfx_amd/ builds, loads or calls this.
+#include <hip/hip_runtime.h>
+#undef __device__
+#define __device__ __attribute__((host)) __attribute__((device))
+#include "mifx.h"
+#include "mifx_coordinate_grid.h"
+#include "mifx_tonemap.h"
+
+using namespace mifx;
+
+static v4 shade(int x, int y, int W, int H, const GridCamK& cam, float minD, float maxD, const mifx_coordinate_grid_attribs& a, uint32_t flags)
+{
+    v4 g{0.0f, 0.0f, 0.0f, 0.0f};
+    if (flags & (kGridPlaneFlags | kGridAxisFlags))
+    {
+        g = coordinate_grid_at(x, y, W, H, cam, minD, maxD, a, flags);
+        if ((flags & MIFX_COORDINATE_GRID_FEATURE_FLAG_CONVERT_TO_SRGB) && !(flags & MIFX_COORDINATE_GRID_DEBUG_FLAG_COORD)) g = mk4(linear_to_srgb(xyz(g)), g.w);
+    }
+    return g;
+}
+
+extern "C" {
+// depth: w x h floats; out: w x h float4
+int mifx_host_grid_render(const float* depth, int w, int h, const mifx_camera_attribs* camera, const mifx_coordinate_grid_attribs* a, uint32_t flags, float* out)
+{
+    const GridCamK cam = make_gridcamk(*camera);
+#pragma omp parallel for
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x)
+        {
+            const size_t i = size_t(y) * w + x;
+            const v4 g = shade(x, y, w, h, cam, depth[i], depth[i], *a, flags);
+            out[4 * i] = g.x; out[4 * i + 1] = g.y; out[4 * i + 2] = g.z; out[4 * i + 3] = g.w;
+        }
+    return 0;
+}
+
+// the pixels (xs[i], ys[i]) of a W x H frame with the depth range given per pixel; out: n float4
+int mifx_host_grid_pixels(int W, int H, const int* xs, const int* ys, int n, const float* minDepth, const float* maxDepth, const mifx_camera_attribs* camera,
+                          const mifx_coordinate_grid_attribs* a, uint32_t flags, float* out)
+{
+    const GridCamK cam = make_gridcamk(*camera);
+#pragma omp parallel for
+    for (int i = 0; i < n; ++i)
+    {
+        const v4 g = shade(xs[i], ys[i], W, H, cam, minDepth[i], maxDepth[i], *a, flags);
+        out[4 * i] = g.x; out[4 * i + 1] = g.y; out[4 * i + 2] = g.z; out[4 * i + 3] = g.w;
+    }
+    return 0;
+}
+
+// out: n x 12 floats -- PlaneAlpha of the planes YZ, XZ, XY, then (DistFromCamera, DistFromOrigin, DistToAxis) of the axes X, Y, Z
+int mifx_host_grid_terms(int W, int H, const int* xs, const int* ys, int n, const float* minDepth, const float* maxDepth, const mifx_camera_attribs* camera, float* out)
+{
+    const GridCamK cam = make_gridcamk(*camera);
+    for (int i = 0; i < n; ++i)
+    {
+        const GridRay        r = grid_camera_ray(grid_ndc(xs[i], ys[i], W, H, cam), cam);
+        const GridDepthRange z = grid_depth_range(cam, minDepth[i], maxDepth[i]);
+        float* o = out + 12 * size_t(i);
+        const float d0 = grid_plane_distance<0>(r), d1 = grid_plane_distance<1>(r), d2 = grid_plane_distance<2>(r);
+        o[0] = grid_plane_alpha(d0, grid_plane_hit<0>(r, d0), cam, z);
+        o[1] = grid_plane_alpha(d1, grid_plane_hit<1>(r, d1), cam, z);
+        o[2] = grid_plane_alpha(d2, grid_plane_hit<2>(r, d2), cam, z);
+        const GridAxisTerms t0 = grid_axis_terms<0>(r), t1 = grid_axis_terms<1>(r), t2 = grid_axis_terms<2>(r);
+        o[3] = t0.distFromCamera; o[4] = t0.distFromOrigin; o[5] = t0.distToAxis;
+        o[6] = t1.distFromCamera; o[7] = t1.distFromOrigin; o[8] = t1.distToAxis;
+        o[9] = t2.distFromCamera; o[10] = t2.distFromOrigin; o[11] = t2.distToAxis;
+    }
+    return 0;
+}
+
+// color: w x h float4, depth: w x h floats; out: w x h float4.  grid_flags without a plane / axis bit: the plain tone map.
+int mifx_host_copy_frame(const float* color, const float* depth, int w, int h, const mifx_camera_attribs* camera, const mifx_tone_mapping_attribs* tm, float ave_log_lum,
+                         uint32_t tonemap_flags, const mifx_coordinate_grid_attribs* a, uint32_t grid_flags, float* out)
+{
+    const GridCamK cam = make_gridcamk(*camera);
+    const ToneMapK k   = make_tonemapk(*tm, ave_log_lum);
+    const bool     srgb = (tonemap_flags & MIFX_TONEMAP_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0;
+    auto at = [&](int x, int y) { return (x < 0 || y < 0 || x >= w || y >= h) ? 0.0f : depth[size_t(y) * w + x]; };
+#pragma omp parallel for
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x)
+        {
+            const size_t i = size_t(y) * w + x;
+            const v3 c{color[4 * i], color[4 * i + 1], color[4 * i + 2]};
+            v3 t{};
+#define MIFX_HOST_TM(M) t = tone_map<M>(c, k)
+            MIFX_TONEMAP_DISPATCH(tm->iToneMappingMode, MIFX_HOST_TM)
+#undef MIFX_HOST_TM
+            if (grid_flags & (kGridPlaneFlags | kGridAxisFlags))
+            {
+                float lo = 1.0f, hi = 0.0f;
+                for (int dx = -1; dx <= 1; ++dx)
+                    for (int dy = -1; dy <= 1; ++dy)
+                    {
+                        const float d = at(x + dx, y + dy);
+                        lo = fminf(lo, d);
+                        hi = fmaxf(hi, d);
+                    }
+                t = grid_lerp(t, coordinate_grid_at(x, y, w, h, cam, lo, hi, *a, grid_flags & (kGridPlaneFlags | kGridAxisFlags)));
+            }
+            if (srgb) t = linear_to_srgb(t);
+            out[4 * i] = t.x; out[4 * i + 1] = t.y; out[4 * i + 2] = t.z; out[4 * i + 3] = color[4 * i + 3];
+        }
+    return 0;
+}
+
+float mifx_host_grid_ipow(float s, float e) { return grid_ipow(s, e); }
+}
