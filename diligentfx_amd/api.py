@@ -442,6 +442,54 @@ class CoordinateGridRenderer:
         return out if out is not None else color_target
 
 
+class ShadowMapManager:
+    """Components/ShadowMapManager, the per-texel half: ConvertToFilterable (mifx_shadow_convert_to_filterable) and the look-up of Shadows.fxh for every pixel of a frame
+    (mifx_shadow_map_filter).  Cascade distribution and shadow-map rendering stay with the rasteriser: the attribs are taken as given."""
+
+    def __init__(self, ctx: "PostFXContext", shadow_mode=B.SHADOW_MODE_PCF, is_32bit_filterable=True):
+        """ShadowMapManager::InitInfo::ShadowMode / Is32BitFilterableFmt.  Only the 32-bit filterable formats are built."""
+        if shadow_mode not in (B.SHADOW_MODE_PCF, B.SHADOW_MODE_VSM, B.SHADOW_MODE_EVSM2, B.SHADOW_MODE_EVSM4):
+            raise ValueError(f"unknown shadow mode {shadow_mode}")
+        if not is_32bit_filterable:
+            raise NotImplementedError("the 16-bit filterable formats (RG16_UNORM / RG16F / RGBA16F) are not built")
+        self.ctx = ctx
+        self.shadow_mode = shadow_mode
+        self.filterable = None
+
+    def convert_to_filterable(self, shadow_map, attribs: B.ShadowMapAttribs, out=None):
+        """ShadowMapManager::ConvertToFilterable.  shadow_map: float32 (slices, H, W).  Returns (and keeps) the filterable array, float32 (slices, H, W, 2) for VSM /
+        EVSM2 and (slices, H, W, 4) for EVSM4; PCF mode has none."""
+        if self.shadow_mode == B.SHADOW_MODE_PCF:
+            return None
+        if out is None:
+            out = torch.empty(tuple(shadow_map.shape) + (4 if self.shadow_mode == B.SHADOW_MODE_EVSM4 else 2,), dtype=torch.float32, device=shadow_map.device)
+        src, dst = B.shadow_map_array(shadow_map), B.filterable_shadow_map(out)
+        self.ctx.sync_stream()
+        B.check(self.ctx.lib.mifx_shadow_convert_to_filterable(self.ctx.handle, ctypes.byref(src), ctypes.byref(attribs), ctypes.c_uint32(self.shadow_mode), ctypes.byref(dst)))
+        self.filterable = out
+        return out
+
+    def filter(self, ctx, depth, camera: B.CameraAttribs, attribs: B.ShadowMapAttribs, shadow_map=None, filterable_map=None, filter_across_cascades=False,
+               best_cascade_search=False, cascade_info=False):
+        """FilterShadowMap (PCF: reads shadow_map) / SampleFilterableShadowMap (reads filterable_map, by default the last result of convert_to_filterable) for every
+        pixel of `depth`.  Returns the light amount (H, W), with cascade_info also the (H, W, 2) plane (float(iCascadeIdx), fNextCascadeBlendAmount)."""
+        ctx = ctx or self.ctx
+        light = torch.empty_like(depth)
+        casc = torch.empty(tuple(depth.shape) + (2,), dtype=torch.float32, device=depth.device) if cascade_info else None
+        params = B.ShadowFilterParams(self.shadow_mode, int(bool(filter_across_cascades)), int(bool(best_cascade_search)), 0)
+        sm = B.shadow_map_array(shadow_map) if shadow_map is not None else None
+        if filterable_map is None and self.shadow_mode != B.SHADOW_MODE_PCF:
+            filterable_map = self.filterable
+        fm = B.filterable_shadow_map(filterable_map) if filterable_map is not None else None
+        d, o = B.image(depth), B.image(light)
+        c = B.image(casc) if casc is not None else None
+        ctx.sync_stream()
+        B.check(ctx.lib.mifx_shadow_map_filter(ctx.handle, ctypes.byref(d), ctypes.byref(camera), ctypes.byref(attribs), ctypes.byref(params),
+                                                   ctypes.byref(sm) if sm is not None else None, ctypes.byref(fm) if fm is not None else None, ctypes.byref(o),
+                                                   ctypes.byref(c) if c is not None else None))
+        return (light, casc) if cascade_info else light
+
+
 def composite_selection(ctx: "PostFXContext", color, specular_ibl, ssr, ssao, normal, base_color, material, lut, camera, depth, selection_depth, closest_location,
                         selection: "B.SelectionAttribs", ssr_scale=1.0, ssao_scale=1.0, tone_mapping=None, ave_log_lum=0.3, out=None):
     """The composite with the selection tail (mifx_composite_execute_selection), Hydrogent/shaders/HnPostProcess.psh:145-185 + 211-241.  The outline colours of

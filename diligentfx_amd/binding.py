@@ -288,6 +288,53 @@ COORDINATE_GRID_FEATURE_FLAG_RENDER_AXIS_Z = 64
 COORDINATE_GRID_DEBUG_FLAG_COORD = 256  # (not in the reference: the raw output holds Coord and fwidth(Coord))
 
 
+MAX_CASCADES = 8
+SHADOW_MODE_PCF, SHADOW_MODE_VSM, SHADOW_MODE_EVSM2, SHADOW_MODE_EVSM4 = 1, 2, 3, 4  # BasicStructures.fxh:19-22
+
+
+class CascadeAttribs(ctypes.Structure):
+    """mifx_cascade_attribs -- CascadeAttribs (Shaders/Common/public/BasicStructures.fxh:6-14), 64 bytes"""
+    _fields_ = [("f4LightSpaceScale", c_f * 4), ("f4LightSpaceScaledBias", c_f * 4), ("f4StartEndZ", c_f * 4), ("f4MarginProjSpace", c_f * 4)]
+
+
+class ShadowMapAttribs(ctypes.Structure):
+    """mifx_shadow_map_attribs -- ShadowMapAttribs (BasicStructures.fxh:28-67), 1200 bytes"""
+    _fields_ = [("mWorldToLightView", c_f * 16), ("Cascades", CascadeAttribs * MAX_CASCADES), ("mWorldToShadowMapUVDepth", (c_f * 16) * MAX_CASCADES),
+                ("fCascadeCamSpaceZEnd", c_f * MAX_CASCADES), ("f4ShadowMapDim", c_f * 4), ("iNumCascades", c_i), ("fNumCascades", c_f), ("bVisualizeCascades", c_i),
+                ("bVisualizeShadowing", c_i), ("fReceiverPlaneDepthBiasClamp", c_f), ("fFixedDepthBias", c_f), ("fCascadeTransitionRegion", c_f), ("iMaxAnisotropy", c_i),
+                ("fVSMBias", c_f), ("fVSMLightBleedingReduction", c_f), ("fEVSMPositiveExponent", c_f), ("fEVSMNegativeExponent", c_f), ("bIs32BitEVSM", c_i),
+                ("iFixedFilterSize", c_i), ("fFilterWorldSize", c_f), ("fDummy", c_i)]
+
+    @classmethod
+    def default(cls):
+        """The reference's DEFAULT_VALUEs (what mifx_shadow_map_default_attribs writes); everything else is zero."""
+        a = cls()
+        a.fReceiverPlaneDepthBiasClamp, a.fFixedDepthBias, a.fCascadeTransitionRegion, a.iMaxAnisotropy = 10.0, 1e-5, 0.1, 4
+        a.fVSMBias, a.fVSMLightBleedingReduction, a.fEVSMPositiveExponent, a.fEVSMNegativeExponent = 1e-4, 0.0, 40.0, 5.0
+        a.bIs32BitEVSM, a.iFixedFilterSize, a.fFilterWorldSize = 1, 3, 0.0
+        return a
+
+
+class FilterableShadowMap(ctypes.Structure):  # mifx_filterable_shadow_map
+    _fields_ = [("data", c_p), ("width", c_u), ("height", c_u), ("slices", c_u), ("format", c_u), ("pitch_bytes", c_u), ("slice_pitch_bytes", ctypes.c_uint64)]
+
+
+class ShadowFilterParams(ctypes.Structure):  # mifx_shadow_filter_params: the compile-time macros of Shadows.fxh
+    _fields_ = [("shadow_mode", c_u), ("filter_across_cascades", c_u), ("best_cascade_search", c_u), ("reserved", c_u)]
+
+
+def shadow_map_array(t) -> "ShadowMapArray":
+    """float32 CUDA tensor (slices, H, W), rows and slices possibly pitched -> mifx_shadow_map_array"""
+    assert t.dim() == 3 and t.stride(2) == 1, "a (slices, H, W) float32 tensor with contiguous texels"
+    return ShadowMapArray(t.data_ptr(), t.shape[2], t.shape[1], t.shape[0], t.stride(1) * 4, t.stride(0) * 4)
+
+
+def filterable_shadow_map(t) -> FilterableShadowMap:
+    """float32 CUDA tensor (slices, H, W, 2 | 4), rows and slices possibly pitched -> mifx_filterable_shadow_map"""
+    assert t.dim() == 4 and t.shape[3] in (2, 4) and t.stride(3) == 1 and t.stride(2) == t.shape[3], "a (slices, H, W, 2 | 4) float32 tensor with contiguous texels"
+    return FilterableShadowMap(t.data_ptr(), t.shape[2], t.shape[1], t.shape[0], FORMAT_F32X2 if t.shape[3] == 2 else FORMAT_F32X4, t.stride(1) * 4, t.stride(0) * 4)
+
+
 class ChainFrame(ctypes.Structure):
     _fields_ = [("frame", FrameDesc), ("gbuffer", GBuffer), ("motion", PImage), ("prev_depth", PImage),
                 ("curr_camera", ctypes.POINTER(CameraAttribs)), ("prev_camera", ctypes.POINTER(CameraAttribs)),
@@ -303,6 +350,7 @@ SIZEOF_NAMES = {
     "pbr_light_attribs": PBRLightAttribs, "pbr_shade_attribs": PBRShadeAttribs, "frame_desc": FrameDesc, "chain_frame": ChainFrame,
     "composite_attribs": CompositeAttribs, "gbuffer": GBuffer, "ibl": IBL, "pbr_shadow_map_info": PBRShadowMapInfo,
     "selection_attribs": SelectionAttribs, "selection_composite_inputs": SelectionCompositeInputs, "coordinate_grid_attribs": CoordinateGridAttribs,
+    "cascade_attribs": CascadeAttribs, "shadow_map_attribs": ShadowMapAttribs, "filterable_shadow_map": FilterableShadowMap, "shadow_filter_params": ShadowFilterParams,
 }
 
 _lib = None

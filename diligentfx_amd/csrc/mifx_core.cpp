@@ -240,6 +240,10 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("selection_attribs", mifx_selection_attribs);
     MIFX_SZ("selection_composite_inputs", mifx_selection_composite_inputs);
     MIFX_SZ("coordinate_grid_attribs", mifx_coordinate_grid_attribs);
+    MIFX_SZ("cascade_attribs", mifx_cascade_attribs);
+    MIFX_SZ("shadow_map_attribs", mifx_shadow_map_attribs);
+    MIFX_SZ("filterable_shadow_map", mifx_filterable_shadow_map);
+    MIFX_SZ("shadow_filter_params", mifx_shadow_filter_params);
     MIFX_SZ("gbuffer", mifx_gbuffer);
     MIFX_SZ("ibl", mifx_ibl);
     MIFX_SZ("shard_info", mifx_shard_info);

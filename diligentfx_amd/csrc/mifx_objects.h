@@ -71,6 +71,8 @@ struct mifx_postfx
 
     // per-call working copy of the IBL cube maps with a one-texel apron per face (P6/P7, see pbr.hip); grown on demand
     mifx::IblApronCache ibl_apron;
+    // the intermediate array of the two-launch shadow conversion (shadows.hip), grown on demand; used on `stream` only, freed with the context
+    mifx::DeviceScratch shadow_scratch;
 
     ~mifx_postfx();
 };

@@ -845,6 +845,116 @@ MIFX_API mifx_status mifx_copy_frame_render(mifx_postfx* ctx, const mifx_image2d
                                             const mifx_tone_mapping_attribs* tone_mapping, float ave_log_lum, uint32_t tonemap_flags,
                                             const mifx_coordinate_grid_attribs* grid, uint32_t grid_feature_flags, const mifx_image2d* out);
 
+/* ------------------------------------------------------------------------------------------------ cascaded shadow maps (Components/ShadowMapManager, Shaders/Common/public/Shadows.fxh) */
+#define MIFX_MAX_CASCADES 8 /* MAX_CASCADES, BasicStructures.fxh:27 */
+/* CascadeAttribs -- Shaders/Common/public/BasicStructures.fxh:6-14 (64 bytes, byte-identical) */
+typedef struct mifx_cascade_attribs
+{
+    float f4LightSpaceScale[4];
+    float f4LightSpaceScaledBias[4];
+    float f4StartEndZ[4];
+    float f4MarginProjSpace[4]; /* cascade margin in light projection space, [-1, +1] x [-1, +1] x [0, +1] */
+} mifx_cascade_attribs;
+/* ShadowMapAttribs -- BasicStructures.fxh:28-67 (1200 bytes, byte for byte what the reference's constant buffer holds; matrices as in mifx_camera_attribs: row-major,
+ * mul(v, M)).  fCascadeCamSpaceZEnd is the host view of the shader's float4 f4CascadeCamSpaceZEnd[2]: FindCascade compares WHOLE groups of four, so the entries from
+ * iNumCascades up to the next multiple of four are read -- ShadowMapManager::DistributeCascades leaves +FLT_MAX there (ShadowMapManager.cpp:180) and so must the caller. */
+typedef struct mifx_shadow_map_attribs
+{
+    float                mWorldToLightView[16];
+    mifx_cascade_attribs Cascades[MIFX_MAX_CASCADES];
+    float                mWorldToShadowMapUVDepth[MIFX_MAX_CASCADES][16]; /* not read by the entries below */
+    float                fCascadeCamSpaceZEnd[MIFX_MAX_CASCADES];
+    float                f4ShadowMapDim[4]; /* width, height, 1 / width, 1 / height */
+    int32_t              iNumCascades;                 /* 0 */
+    float                fNumCascades;                 /* 0 */
+    int32_t              bVisualizeCascades;           /* 0 */
+    int32_t              bVisualizeShadowing;          /* 0 */
+    float                fReceiverPlaneDepthBiasClamp; /* 10 */
+    float                fFixedDepthBias;              /* 1e-5 */
+    float                fCascadeTransitionRegion;     /* 0.1 */
+    int32_t              iMaxAnisotropy;               /* 4 (not read: see mifx_shadow_map_filter) */
+    float                fVSMBias;                     /* 1e-4 */
+    float                fVSMLightBleedingReduction;   /* 0 */
+    float                fEVSMPositiveExponent;        /* 40 */
+    float                fEVSMNegativeExponent;        /* 5 */
+    int32_t              bIs32BitEVSM;                 /* 1: selects the exponent clamp only (42, otherwise 5.54: GetEVSMExponents); storage is fp32 either way */
+    int32_t              iFixedFilterSize;             /* 3 */
+    float                fFilterWorldSize;             /* 0 */
+    int32_t              fDummy;
+} mifx_shadow_map_attribs;
+enum /* SHADOW_MODE_*, BasicStructures.fxh:19-22 */
+{
+    MIFX_SHADOW_MODE_PCF   = 1,
+    MIFX_SHADOW_MODE_VSM   = 2,
+    MIFX_SHADOW_MODE_EVSM2 = 3,
+    MIFX_SHADOW_MODE_EVSM4 = 4
+};
+/* The filterable shadow-map array (ShadowMapManager::GetFilterableSRV): caller-owned, one mip, F32X2 texels for VSM / EVSM2 and TRUE fp32 F32X4 texels for EVSM4; slice k
+ * at data + k * slice_pitch_bytes.  pitch_bytes is a multiple of the texel size, data and both pitches are aligned to the texel size.  The 16-bit formats of the
+ * reference (RG16_UNORM / RG16F / RGBA16F) are not built. */
+typedef struct mifx_filterable_shadow_map
+{
+    void*    data;
+    uint32_t width, height, slices;
+    uint32_t format; /* MIFX_FORMAT_F32X2 or MIFX_FORMAT_F32X4 */
+    uint32_t pitch_bytes;
+    uint64_t slice_pitch_bytes;
+} mifx_filterable_shadow_map;
+typedef struct mifx_shadow_filter_params /* the compile-time macros of Shadows.fxh */
+{
+    uint32_t shadow_mode;            /* SHADOW_MODE: MIFX_SHADOW_MODE_* */
+    uint32_t filter_across_cascades; /* FILTER_ACROSS_CASCADES: 0 / 1 */
+    uint32_t best_cascade_search;    /* BEST_CASCADE_SEARCH: 0 / 1 */
+    uint32_t reserved;               /* 0 */
+} mifx_shadow_filter_params;
+/* The DEFAULT_VALUEs of ShadowMapAttribs; everything without one is zero. */
+MIFX_API mifx_status mifx_shadow_map_default_attribs(mifx_shadow_map_attribs* out);
+/* ShadowMapManager::ConvertToFilterable (Components/src/ShadowMapManager.cpp:533-600, Shaders/Shadows/private/ShadowConversions.fx): for every cascade VSMHorzPS
+ * (mode VSM) or EVSMHorzPS (EVSM2 / EVSM4: one shader, the target keeps two or four channels), then VertBlurPS unless iFixedFilterSize == 2.  Radii as the host computes
+ * them: (iFixedFilterSize - 1) / 2 when iFixedFilterSize > 0, otherwise fFilterWorldSize * f4LightSpaceScale.x|y * 0.5 / 2 * width|height, per cascade and axis;
+ * range = floor(radius + 0.5), GetSampleWeight as written, the weighted sum divided by the total weight after each pass.  A Load outside the slice returns 0 (for EVSM
+ * the depth 0 is warped like any other; a row of the intermediate target outside the slice is 0).  `out` has the size and slice count of `shadow_map`.
+ * Every finite radius up to MIFX_SHADOW_MAX_FILTER_RADIUS texels is taken, also one wider than the slice (the taps beyond it read 0 and count in the total weight); the
+ * work per texel is proportional to the range.  With a range above 3 in any cascade, and by default (mifx_shadow_set_conversion_fusion), the two passes are two launches
+ * through an intermediate array that the context owns (grown on demand on the context's device, used on its stream, freed with the context).
+ * MIFX_ERR_INVALID_ARG: shadow_map->slices != attribs->iNumCascades, more than MIFX_MAX_CASCADES, a mode outside 2 .. 4, a wrong format / size / pitch, a radius that
+ * is not finite or exceeds MIFX_SHADOW_MAX_FILTER_RADIUS.  MIFX_ERR_NOT_IMPLEMENTED in the native-storage build of the library.
+ * Kernel-timing names (mifx_postfx_set_kernel_timing): "shadow_convert_fused_kernel", "shadow_convert_two_launch", "shadow_convert_horz_kernel" (iFixedFilterSize == 2).
+ * mifx_shadow_convert_check: the argument checks alone -- no context, no device, nothing read but the descriptors and the attribs. */
+#define MIFX_SHADOW_MAX_FILTER_RADIUS 16384 /* the largest slice extent the entries take: a tap count is a loop count on the device */
+MIFX_API mifx_status mifx_shadow_convert_check(const mifx_shadow_map_array* shadow_map, const mifx_shadow_map_attribs* attribs, uint32_t mode, const mifx_filterable_shadow_map* out);
+MIFX_API mifx_status mifx_shadow_convert_to_filterable(mifx_postfx* ctx, const mifx_shadow_map_array* shadow_map, const mifx_shadow_map_attribs* attribs, uint32_t mode,
+                                                       const mifx_filterable_shadow_map* out);
+/* Internal switch for A/B comparisons: 1 = the conversion keeps the horizontal results of a tile in LDS and runs the vertical pass from there (one launch for all
+ * cascades) whenever every cascade's filter range is at most 3 texels; 0 (the default until a same-box A/B on an MI355X says the fused kernel is faster) = always the
+ * two launches.  Same bits either way.  Process-wide; returns the previous value. */
+MIFX_API int32_t mifx_shadow_set_conversion_fusion(int32_t enable);
+/* FilterShadowMap (Shadows.fxh:219-253; params->shadow_mode == PCF, reads shadow_map) or SampleFilterableShadowMap (:350-384; VSM / EVSM2 / EVSM4, reads filterable_map)
+ * for every pixel of `depth` (F32).  out_light_amount: F32, fLightAmount.  out_cascade (may be NULL): F32X2, (float(iCascadeIdx), fNextCascadeBlendAmount).
+ * PCF: attribs->iFixedFilterSize 2 / 3 / 5 / 7 is PCF_FILTER_SIZE (FilterShadowMapFixedPCF), <= 0 is FilterShadowMapVaryingPCF with fFilterWorldSize; other sizes are
+ * refused, as is an f4ShadowMapDim.xy that is not the shadow map's size.  The map that the mode does not read may be NULL.
+ * The varying filter loops over every texel its footprint covers (2 x 2 per iteration, the footprint clamped to the map), for every pixel: a footprint of
+ * |fFilterWorldSize * f4LightSpaceScale.x|y * 0.5| * width|height texels in any cascade that is not finite or exceeds MIFX_SHADOW_MAX_VARYING_PCF_TEXELS is refused
+ * (the reference has no such limit; it bounds the time one mistaken world size can cost on the device).
+ * mifx_shadow_map_filter_check: the argument checks alone -- no context, no device, nothing read but the descriptors, the params and the attribs.
+ * Conventions of this library (a deferred frame has only depth; the reference's callers interpolate these from a vertex shader):
+ *   - WorldPos = mul(float4(f2NormalizedXY, depth, 1), camera->mViewProjInv), divided by w; PosInLightViewSpace = mul(float4(WorldPos, 1), mWorldToLightView).xyz;
+ *     fCameraSpaceZ = DepthToCameraZ(depth, camera->mProj); f2NormalizedXY is that of the pixel centre (no jitter added).
+ *   - ddx / ddy of PosInLightViewSpace: fine derivatives inside the 2x2 quad at (x & ~1, y & ~1), ddx = right - left of the pixel's row, ddy = bottom - top of its
+ *     column; each pixel evaluates its two partners from their own depth texels; a partner outside the frame is evaluated as the pixel itself (derivative 0).
+ *   - a background pixel (depth == camera->fFarPlaneDepth) gets light amount 1, cascade index iNumCascades, blend amount 0; so does a pixel whose cascade index
+ *     reaches iNumCascades or more.
+ *   - SampleGrad on the filterable array (one mip, ShadowMapManager.cpp:63): a bilinear, clamped fetch of mip 0 at the UV in the slice rounded to nearest; the gradients
+ *     and iMaxAnisotropy are not used.  SampleCmpLevelZero: "reference < texel" on the clamped 2x2 footprint, blended with the bilinear weights.
+ * MIFX_ERR_NOT_IMPLEMENTED in the native-storage build of the library. */
+#define MIFX_SHADOW_MAX_VARYING_PCF_TEXELS 128
+MIFX_API mifx_status mifx_shadow_map_filter_check(const mifx_image2d* depth, const mifx_camera_attribs* camera, const mifx_shadow_map_attribs* attribs,
+                                                  const mifx_shadow_filter_params* params, const mifx_shadow_map_array* shadow_map,
+                                                  const mifx_filterable_shadow_map* filterable_map, const mifx_image2d* out_light_amount, const mifx_image2d* out_cascade);
+MIFX_API mifx_status mifx_shadow_map_filter(mifx_postfx* ctx, const mifx_image2d* depth, const mifx_camera_attribs* camera, const mifx_shadow_map_attribs* attribs,
+                                            const mifx_shadow_filter_params* params, const mifx_shadow_map_array* shadow_map,
+                                            const mifx_filterable_shadow_map* filterable_map, const mifx_image2d* out_light_amount, const mifx_image2d* out_cascade);
+
 /* ------------------------------------------------------------------------------------------------ whole chain (the caller: HnPostProcessTask::Execute, Hydrogent/src/Tasks/HnPostProcessTask.cpp:743-948) */
 typedef struct mifx_autoexposure mifx_autoexposure; /* auto exposure, declared below */
 typedef struct mifx_chain mifx_chain;
