@@ -12,8 +12,6 @@
 
 using namespace mifx;
 
-const SelectionHooks* mifx::selection_hooks = nullptr; // (set by selection.hip when the library is loaded)
-
 mifx_chain::~mifx_chain()
 {
     for (auto& e : ev)
@@ -31,7 +29,7 @@ mifx_chain::~mifx_chain()
     if (lane_x) (void)hipStreamDestroy(lane_x);
     if (lane_h) (void)hipStreamDestroy(lane_h);
     mifx::chain_detach_comm(this);
-    if (selection && selection_hooks) selection_hooks->destroy(selection);
+    mifx_selection_destroy(selection);
     mifx_autoexposure_destroy(auto_exposure);
     mifx_bloom_destroy(bloom);
     mifx_dof_destroy(dof);
@@ -174,7 +172,7 @@ static mifx_status chain_selection_composite(mifx_chain* chain, const mifx_chain
         MIFX_CHECK(mifx_reverse_exp_tone_map(chain->selection_attribs.outline_color, f->tone_mapping->fMiddleGray, f->ave_log_lum, a.outline_color));
         MIFX_CHECK(mifx_reverse_exp_tone_map(chain->selection_attribs.occluded_outline_color, f->tone_mapping->fMiddleGray, f->ave_log_lum, a.occluded_outline_color));
     }
-    return selection_hooks->chain_composite(chain->selection, a, &chain->selection_depth, ca, f->gbuffer.depth, comp, r7);
+    return selection_chain_composite(chain->selection, a, &chain->selection_depth, ca, f->gbuffer.depth, comp, r7);
 }
 
 // The composite draw (HnPostProcess.psh:145-185).  With fuse_ssr_cleanup the kernel evaluates SSR's last pass (R7, the bilateral cleanup) for its own pixel from the
@@ -925,12 +923,7 @@ mifx_status mifx_chain_set_selection(mifx_chain* chain, const mifx_selection_att
     }
     MIFX_REQUIRE(selection_depth != nullptr && selection_depth->data != nullptr, "mifx_chain_set_selection: the selection depth image is missing");
     MIFX_REQUIRE(attribs->outline_width > 0.0f, "mifx_chain_set_selection: outline_width %g must be positive", double(attribs->outline_width));
-    if (selection_hooks == nullptr)
-    {
-        set_error("mifx_chain_set_selection: this build of the library has no selection kernels");
-        return MIFX_ERR_NOT_IMPLEMENTED;
-    }
-    if (chain->selection == nullptr) MIFX_CHECK(selection_hooks->create(chain->ctx, &chain->selection));
+    if (chain->selection == nullptr) MIFX_CHECK(mifx_selection_create(chain->ctx, &chain->selection));
     chain->selection_attribs = *attribs;
     chain->selection_depth   = *selection_depth;
     chain->has_selection     = true;

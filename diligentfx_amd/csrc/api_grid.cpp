@@ -1,18 +1,9 @@
 // api_grid.cpp -- C ABI of the coordinate grid and axes (include/mifx.h "coordinate grid and axes"): the stand-alone renderer (Components/CoordinateGridRenderer) and the
-// copy-frame draw with the grid (Hydrogent/shaders/HnCopyFrame.psh).  The kernels are in grid.hip, reached through mifx::grid_hooks (mifx_grid_host.h).
+// copy-frame draw with the grid (Hydrogent/shaders/HnCopyFrame.psh).  The kernels and their launchers are in grid.hip (mifx_grid_host.h).
 #include "mifx_objects.h"
 #include "mifx_grid_host.h"
 
 using namespace mifx;
-
-const GridHooks* mifx::grid_hooks = nullptr; // (set by grid.hip when the library is loaded)
-
-static mifx_status grid_kernels_present(const char* who)
-{
-    if (grid_hooks != nullptr) return MIFX_OK;
-    set_error("%s: this build of the library has no coordinate-grid kernels", who);
-    return MIFX_ERR_NOT_IMPLEMENTED;
-}
 
 static const uint32_t kGridKnownFlags = MIFX_COORDINATE_GRID_FEATURE_FLAG_CONVERT_TO_SRGB | kGridPlaneFlags | kGridAxisFlags;
 
@@ -27,7 +18,6 @@ mifx_status mifx::copy_frame_grid_run(mifx_postfx* ctx, const mifx_image2d* colo
     // (the average is written on the auto-exposure object's context stream and read here on ctx's, as for mifx_tonemap_execute_auto)
     MIFX_REQUIRE(ae == nullptr || ae->ctx == ctx || (ae->ctx->device == ctx->device && ae->ctx->stream == ctx->stream),
                  "%s: the auto-exposure object belongs to a context on another device / stream", who);
-    MIFX_CHECK(grid_kernels_present(who));
     Img  in, d, o;
     bool packed = false;
     MIFX_CHECK(to_img_hdr(color, "color", in, packed));
@@ -35,7 +25,7 @@ mifx_status mifx::copy_frame_grid_run(mifx_postfx* ctx, const mifx_image2d* colo
     MIFX_CHECK(to_img_wh(out, MIFX_FORMAT_F32X4, color->width, color->height, "out", o));
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
     MifxKernelTimer timer(ctx, "copy_frame_grid_kernel");
-    return grid_hooks->copy_frame(ctx->stream, in, packed, d, win(o, ctx->needed_rows(o.h)), *tm, ae ? 1.0f : ave_log_lum, tonemap_flags,
+    return launch_copy_frame_grid(ctx->stream, in, packed, d, win(o, ctx->needed_rows(o.h)), *tm, ae ? 1.0f : ave_log_lum, tonemap_flags,
                                   ae ? static_cast<const float*>(ae->average.data) : nullptr, make_gridcamk(*camera), grid, grid_flags & (kGridPlaneFlags | kGridAxisFlags));
 }
 
@@ -63,7 +53,6 @@ mifx_status mifx_coordinate_grid_render(mifx_postfx* ctx, const mifx_image2d* de
     const bool debug = (feature_flags & MIFX_COORDINATE_GRID_DEBUG_FLAG_COORD) != 0;
     MIFX_REQUIRE(!debug || (color_target == nullptr && (feature_flags & kGridPlaneFlags) != 0 && attribs != nullptr),
                  "mifx_coordinate_grid_render: MIFX_COORDINATE_GRID_DEBUG_FLAG_COORD needs a plane flag and writes the raw output only");
-    MIFX_CHECK(grid_kernels_present("mifx_coordinate_grid_render"));
     if (attribs == nullptr) feature_flags = 0;
     Img d, target{}, raw{};
     MIFX_CHECK(to_img(depth, MIFX_FORMAT_F32, "depth", d));
@@ -87,7 +76,7 @@ mifx_status mifx_coordinate_grid_render(mifx_postfx* ctx, const mifx_image2d* de
     }
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
     MifxKernelTimer timer(ctx, "coordinate_grid_kernel");
-    return grid_hooks->render(ctx->stream, win(d, ctx->needed_rows(d.h)), target, raw, make_gridcamk(*camera), attribs ? *attribs : none, feature_flags);
+    return launch_coordinate_grid(ctx->stream, win(d, ctx->needed_rows(d.h)), target, raw, make_gridcamk(*camera), attribs ? *attribs : none, feature_flags);
 }
 
 // the copy-frame draw of HnPostProcessTask.cpp:920-925 (HnCopyFrame.psh:27-63)
@@ -109,7 +98,6 @@ mifx_status mifx_chain_set_coordinate_grid(mifx_chain* chain, const mifx_coordin
         chain->has_grid = false;
         return MIFX_OK;
     }
-    MIFX_CHECK(grid_kernels_present("mifx_chain_set_coordinate_grid"));
     chain->grid_attribs = *attribs;
     chain->grid_flags   = grid_feature_flags;
     chain->has_grid     = true;

@@ -1,23 +1,15 @@
 // api_shadows.cpp -- C ABI of the cascaded shadow maps (include/mifx.h "cascaded shadow maps"): ShadowMapManager::ConvertToFilterable and the per-pixel look-up
-// FilterShadowMap / SampleFilterableShadowMap.  The kernels are in shadows.hip, reached through mifx::shadow_hooks (mifx_shadows_host.h).
+// FilterShadowMap / SampleFilterableShadowMap.  The kernels and their launchers are in shadows.hip (mifx_shadows_host.h).
 #include "mifx_objects.h"
 #include "mifx_shadows_host.h"
 
 using namespace mifx;
 
-const ShadowHooks* mifx::shadow_hooks = nullptr; // (set by shadows.hip when the library is loaded)
 // The fused conversion kernel is built and tested (bit-identical), but no same-box A/B against the two launches has been measured yet: until one says it is faster,
 // the two launches are the default (mifx_shadow_set_conversion_fusion, tools/shadows_bench.py).
 static bool g_fuse_conversion = false;
 
 static_assert(sizeof(mifx_cascade_attribs) == 64 && sizeof(mifx_shadow_map_attribs) == 1200, "CascadeAttribs / ShadowMapAttribs are byte-identical to the reference's");
-
-static mifx_status shadow_kernels_present(const char* who)
-{
-    if (shadow_hooks != nullptr) return MIFX_OK;
-    set_error("%s: this build of the library has no shadow-map kernels (the native-storage build's filterable formats are not built)", who);
-    return MIFX_ERR_NOT_IMPLEMENTED;
-}
 
 static mifx_status to_shadow_arr(const mifx_shadow_map_array* m, const char* who, ShadowArrK& out)
 {
@@ -162,7 +154,6 @@ mifx_status mifx_shadow_convert_to_filterable(mifx_postfx* ctx, const mifx_shado
     FilterableArrK dst;
     ShadowConvK    k;
     MIFX_CHECK(convert_check(shadow_map, attribs, mode, out, who, src, dst, k));
-    MIFX_CHECK(shadow_kernels_present(who));
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
     // which kernels run is decided here, so that the kernel-timing names say it (mifx_postfx_set_kernel_timing)
     const bool skipBlur = attribs->iFixedFilterSize == 2;
@@ -170,7 +161,7 @@ mifx_status mifx_shadow_convert_to_filterable(mifx_postfx* ctx, const mifx_shado
     for (int i = 0; i < src.slices; ++i) fits = fits && shadow_filter_range(k.rH[i]) <= kShadowFusedMaxRange && shadow_filter_range(k.rV[i]) <= kShadowFusedMaxRange;
     const bool fused = !skipBlur && g_fuse_conversion && fits;
     MifxKernelTimer timer(ctx, skipBlur ? "shadow_convert_horz_kernel" : fused ? "shadow_convert_fused_kernel" : "shadow_convert_two_launch");
-    return shadow_hooks->convert(ctx->stream, ctx->shadow_scratch, src, dst, k, mode, skipBlur, fused);
+    return launch_shadow_convert(ctx->stream, ctx->shadow_scratch, src, dst, k, mode, skipBlur, fused);
 }
 
 mifx_status mifx_shadow_map_filter_check(const mifx_image2d* depth, const mifx_camera_attribs* camera, const mifx_shadow_map_attribs* attribs, const mifx_shadow_filter_params* params,
@@ -194,10 +185,9 @@ mifx_status mifx_shadow_map_filter(mifx_postfx* ctx, const mifx_image2d* depth, 
     FilterableArrK filterable;
     Img            d, light, cascade;
     MIFX_CHECK(filter_check(depth, camera, attribs, params, shadow_map, filterable_map, out_light_amount, out_cascade, who, map, filterable, d, light, cascade));
-    MIFX_CHECK(shadow_kernels_present(who));
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
     MifxKernelTimer timer(ctx, "shadow_filter_kernel");
-    return shadow_hooks->filter(ctx->stream, d, light, cascade, make_shadowlookupk(*camera, *attribs), map, filterable, params->shadow_mode, params->best_cascade_search != 0,
+    return launch_shadow_filter(ctx->stream, d, light, cascade, make_shadowlookupk(*camera, *attribs), map, filterable, params->shadow_mode, params->best_cascade_search != 0,
                                 params->filter_across_cascades != 0);
 }
 

@@ -79,42 +79,27 @@ mifx_status composite_args(const mifx_composite_attribs& a, const mifx_image2d* 
 
 mifx_status launch_composite(hipStream_t s, const mifx_composite_attribs& a, const mifx_image2d* out_img, int row_begin, int row_end, const SsrCleanupIn* r7)
 {
-    Img color, sibl, ssr, ssao, nrm, bc, mat, out;
-    MIFX_CHECK(to_img(out_img, MIFX_FORMAT_F32X4, "out", out));
-    out = rows_of(out, row_begin, row_end);
-    const uint32_t W = out_img->width, H = out_img->height;
-    MIFX_CHECK(to_img_wh(a.color, MIFX_FORMAT_F32X4, W, H, "color", color));
-    MIFX_CHECK(to_img_wh(a.specular_ibl, MIFX_FORMAT_F32X4, W, H, "specular_ibl", sibl));
-    if (r7) ssr = Img{};
-    else MIFX_CHECK(to_img_wh(a.ssr, MIFX_FORMAT_F32X4, W, H, "ssr", ssr));
-    MIFX_CHECK(to_img_wh(a.ssao, MIFX_PLANE_AO, W, H, "ssao", ssao));
-    MIFX_CHECK(to_img_wh(a.normal, MIFX_FORMAT_F32X4, W, H, "normal", nrm));
-    MIFX_CHECK(to_img_wh(a.base_color, MIFX_FORMAT_F32X4, W, H, "base_color", bc));
-    MIFX_CHECK(to_img_wh(a.material, MIFX_FORMAT_F32X4, W, H, "material", mat));
-    MIFX_REQUIRE(a.camera != nullptr, "camera must not be null");
-    LutK lut;
-    MIFX_CHECK(make_lutk(a.brdf_lut, lut));
-    int mode = a.tone_mapping ? a.tone_mapping->iToneMappingMode : 0;
-    MIFX_REQUIRE(mode >= 0 && mode <= MIFX_TONE_MAPPING_MODE_COMMERCE, "unknown tone mapping mode %d", mode);
-    // HnPostProcess.psh:183-185: ToneMap(Color, attribs, AverageLogLum * exp2(-fExposure))
-    const ToneMapK tm = a.tone_mapping ? make_tonemapk(*a.tone_mapping, a.ave_log_lum * m_exp2(-a.camera->fExposure)) : ToneMapK{};
-    const CamK cam = make_camk(*a.camera);
-    const dim3 block(64, 4, 1), grid = grid2d(out, block);
+    CompositeArgs k;
+    MIFX_CHECK(composite_args(a, out_img, row_begin, row_end, r7 != nullptr, k));
+    const dim3 block(64, 4, 1), grid = grid2d(k.out, block);
     if (r7)
     {
         // (the chain composites without a tone map -- TAA follows; the fused instance exists for that mode only)
-        MIFX_REQUIRE(mode == MIFX_TONE_MAPPING_MODE_NONE, "composite with the fused SSR cleanup: tone mapping mode %d not instantiated", mode);
-        hipLaunchKernelGGL((composite_kernel<MIFX_TONE_MAPPING_MODE_NONE, true>), grid, block, 0, s, color, sibl, ssr, ssao, nrm, bc, mat, lut, out, cam, a.ssr_scale, a.ssao_scale, tm, *r7);
+        MIFX_REQUIRE(k.mode == MIFX_TONE_MAPPING_MODE_NONE, "composite with the fused SSR cleanup: tone mapping mode %d not instantiated", k.mode);
+        hipLaunchKernelGGL((composite_kernel<MIFX_TONE_MAPPING_MODE_NONE, true>), grid, block, 0, s, k.color, k.sibl, k.ssr, k.ssao, k.nrm, k.bc, k.mat, k.lut, k.out, k.cam, a.ssr_scale,
+                           a.ssao_scale, k.tm, *r7);
     }
     else
     {
-#define MIFX_COMP(M) hipLaunchKernelGGL((composite_kernel<M, false>), grid, block, 0, s, color, sibl, ssr, ssao, nrm, bc, mat, lut, out, cam, a.ssr_scale, a.ssao_scale, tm, SsrCleanupIn{})
-        MIFX_TONEMAP_DISPATCH(mode, MIFX_COMP)
+#define MIFX_COMP(M) hipLaunchKernelGGL((composite_kernel<M, false>), grid, block, 0, s, k.color, k.sibl, k.ssr, k.ssao, k.nrm, k.bc, k.mat, k.lut, k.out, k.cam, a.ssr_scale, a.ssao_scale, k.tm, \
+                                        SsrCleanupIn{})
+        MIFX_TONEMAP_DISPATCH(k.mode, MIFX_COMP)
 #undef MIFX_COMP
     }
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
 }
+
 mifx_status launch_composite_selection(hipStream_t s, const mifx_composite_attribs& a, const SelectionK& sel, const mifx_image2d* out_img, int row_begin, int row_end,
                                        const SsrCleanupIn* r7)
 {

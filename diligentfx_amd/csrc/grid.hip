@@ -53,7 +53,7 @@ template <int MODE> __global__ __launch_bounds__(256) void copy_frame_grid_kerne
     st_v4_late<1>(out, x, y, mk4(t, c.w));
 }
 
-static mifx_status launch_coordinate_grid(hipStream_t s, Img rows, Img target, Img raw, const GridCamK& cam, const mifx_coordinate_grid_attribs& a, uint32_t flags)
+mifx_status launch_coordinate_grid(hipStream_t s, Img rows, Img target, Img raw, const GridCamK& cam, const mifx_coordinate_grid_attribs& a, uint32_t flags)
 {
     const dim3 block(64, 4, 1);
     hipLaunchKernelGGL(coordinate_grid_kernel, grid2d(rows, block), block, 0, s, rows, target, raw, cam, a, flags);
@@ -61,8 +61,8 @@ static mifx_status launch_coordinate_grid(hipStream_t s, Img rows, Img target, I
     return MIFX_OK;
 }
 
-static mifx_status launch_copy_frame_grid(hipStream_t s, Img in, bool packedIn, Img depth, Img out, const mifx_tone_mapping_attribs& attr, float ave_log_lum, uint32_t tonemap_flags,
-                                          const float* aveLum, const GridCamK& cam, const mifx_coordinate_grid_attribs& a, uint32_t grid_flags)
+mifx_status launch_copy_frame_grid(hipStream_t s, Img in, bool packedIn, Img depth, Img out, const mifx_tone_mapping_attribs& attr, float ave_log_lum, uint32_t tonemap_flags,
+                                   const float* aveLum, const GridCamK& cam, const mifx_coordinate_grid_attribs& a, uint32_t grid_flags)
 {
     ToneMapK tm = make_tonemapk(attr, ave_log_lum);
     tm.packedIn = packedIn ? 1 : 0;
@@ -75,10 +75,4 @@ static mifx_status launch_copy_frame_grid(hipStream_t s, Img in, bool packedIn, 
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
 }
-
-static const GridHooks kGridHooks{launch_coordinate_grid, launch_copy_frame_grid};
-static const struct GridHooksInstaller
-{
-    GridHooksInstaller() { grid_hooks = &kGridHooks; }
-} kGridHooksInstaller;
 } // namespace mifx

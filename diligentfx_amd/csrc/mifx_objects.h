@@ -347,6 +347,13 @@ struct mifx_autoexposure
     }
 };
 
+struct mifx_selection // == HnProcessSelectionTask
+{
+    mifx_postfx* ctx = nullptr;
+    mifx::Plane  out;    // closestSelectedLocationFinalTarget
+    mifx::Plane  tmp[2]; // the leading steps' ping-pong planes (max_distance > 4)
+};
+
 struct mifx_chain
 {
     mifx_postfx* ctx   = nullptr;
@@ -372,14 +379,14 @@ struct mifx_chain
     mifx_pbr_shadows         shadows{};
     mifx_shadow_map_array    shadow_array{};
     mifx_pbr_shadow_map_info shadow_infos[MIFX_PBR_MAX_SHADOW_MAPS]{};
-    // mifx_chain_set_selection: the jump flood + the selection composite in place of the composite (selection.hip, reached through mifx::selection_hooks); the attribs and the
+    // mifx_chain_set_selection: the jump flood + the selection composite in place of the composite (api_selection.cpp); the attribs and the
     // image descriptor are copies, the selection depth plane is borrowed
     bool                   has_selection = false;
     mifx_selection*        selection = nullptr;
     mifx_selection_attribs selection_attribs{};
     mifx_image2d           selection_depth{};
     uint64_t               last_selection_id = 0; // the selected prim of the previous frame executed with selection on (a change resets TAA)
-    // mifx_chain_set_coordinate_grid: the copy-frame draw with the grid as the frame's last pass (grid.hip, reached through mifx::grid_hooks); the attribs are a copy
+    // mifx_chain_set_coordinate_grid: the copy-frame draw with the grid as the frame's last pass (api_grid.cpp); the attribs are a copy
     bool                         has_grid = false;
     mifx_coordinate_grid_attribs grid_attribs{};
     uint32_t                     grid_flags = 0;

@@ -1,20 +1,16 @@
-// mifx_shadows_host.h -- host side of the cascaded shadow maps (shadows.hip, api_shadows.cpp).
-// The C entry points reach the launchers through `shadow_hooks`, which shadows.hip fills in at load time.  The native-storage build of the library compiles no shadow
-// kernels (the filterable formats of that build, RG16 / RGBA16, are out of scope): the pointer stays null and the entries return MIFX_ERR_NOT_IMPLEMENTED.
+// mifx_shadows_host.h -- the launchers of the cascaded shadow maps (shadows.hip), called by api_shadows.cpp.
+// The native-storage build of the library compiles no shadow kernels (the filterable formats of that build, RG16 / RGBA16, are out of scope): there shadows.hip defines
+// the two launchers as refusals (MIFX_ERR_NOT_IMPLEMENTED), so the entries need no check of their own.
 #pragma once
 #include "mifx_host.h"
 #include "mifx_shadows.h"
 
 namespace mifx
 {
-struct ShadowHooks
-{
-    // ConvertToFilterable for all cascades.  mode: MIFX_SHADOW_MODE_VSM / EVSM2 / EVSM4; skipBlur: iFixedFilterSize == 2 (the horizontal kernel alone); fused: the LDS-tile
-    // kernel (the caller has checked that every range fits); otherwise two launches through `scratch`, the calling context's own block on its own device
-    mifx_status (*convert)(hipStream_t s, DeviceScratch& scratch, const ShadowArrK& src, const FilterableArrK& dst, const ShadowConvK& k, uint32_t mode, bool skipBlur, bool fused);
-    // shadow_filter_kernel<mode, best, across>; cascade.p may be null
-    mifx_status (*filter)(hipStream_t s, Img depth, Img light, Img cascade, const ShadowLookupK& k, const ShadowArrK& map, const FilterableArrK& filterable, uint32_t mode, bool best,
-                          bool across);
-};
-extern const ShadowHooks* shadow_hooks; // (api_shadows.cpp; null without shadows.hip's kernels)
+// ConvertToFilterable for all cascades.  mode: MIFX_SHADOW_MODE_VSM / EVSM2 / EVSM4; skipBlur: iFixedFilterSize == 2 (the horizontal kernel alone); fused: the LDS-tile
+// kernel (the caller has checked that every range fits); otherwise two launches through `scratch`, the calling context's own block on its own device
+mifx_status launch_shadow_convert(hipStream_t s, DeviceScratch& scratch, const ShadowArrK& src, const FilterableArrK& dst, const ShadowConvK& k, uint32_t mode, bool skipBlur, bool fused);
+// shadow_filter_kernel<mode, best, across>; cascade.p may be null
+mifx_status launch_shadow_filter(hipStream_t s, Img depth, Img light, Img cascade, const ShadowLookupK& k, const ShadowArrK& map, const FilterableArrK& filterable, uint32_t mode, bool best,
+                                 bool across);
 } // namespace mifx

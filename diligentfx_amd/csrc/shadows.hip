@@ -71,7 +71,7 @@ template <int MODE, bool BEST, bool ACROSS> __global__ __launch_bounds__(256) vo
     if (cascade.p) GlobalAccess<v2>::store(cascade.p + size_t(y) * cascade.pitch + size_t(x) * 8u, v2{r.cascadeIdx, r.nextCascadeBlendAmount});
 }
 
-static mifx_status launch_shadow_convert(hipStream_t s, DeviceScratch& scratch, const ShadowArrK& src, const FilterableArrK& dst, const ShadowConvK& k, uint32_t mode, bool skipBlur, bool fused)
+mifx_status launch_shadow_convert(hipStream_t s, DeviceScratch& scratch, const ShadowArrK& src, const FilterableArrK& dst, const ShadowConvK& k, uint32_t mode, bool skipBlur, bool fused)
 {
     const dim3 block(64, 4, 1);
     const dim3 grid((src.w + 63) / 64, (src.h + 3) / 4, src.slices);
@@ -114,8 +114,8 @@ static mifx_status launch_shadow_convert(hipStream_t s, DeviceScratch& scratch, 
     return MIFX_OK;
 }
 
-static mifx_status launch_shadow_filter(hipStream_t s, Img depth, Img light, Img cascade, const ShadowLookupK& k, const ShadowArrK& map, const FilterableArrK& filterable, uint32_t mode,
-                                        bool best, bool across)
+mifx_status launch_shadow_filter(hipStream_t s, Img depth, Img light, Img cascade, const ShadowLookupK& k, const ShadowArrK& map, const FilterableArrK& filterable, uint32_t mode, bool best,
+                                 bool across)
 {
     const dim3 block(256, 1, 1);
     const dim3 grid((light.w + 31) / 32, (light.h + 7) / 8, 1);
@@ -138,11 +138,24 @@ static mifx_status launch_shadow_filter(hipStream_t s, Img depth, Img light, Img
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
 }
-
-static const ShadowHooks kShadowHooks{launch_shadow_convert, launch_shadow_filter};
-static const struct ShadowHooksInstaller
+} // namespace mifx
+#else  // MIFX_STORAGE_H4
+// The native-storage build compiles no shadow kernels (its filterable formats, RG16 / RGBA16, are out of scope): the two launchers are these refusals, which
+// mifx_shadow_convert_to_filterable and mifx_shadow_map_filter return once their arguments have passed every check.
+namespace mifx
 {
-    ShadowHooksInstaller() { shadow_hooks = &kShadowHooks; }
-} kShadowHooksInstaller;
+static mifx_status no_shadow_kernels(const char* who)
+{
+    set_error("%s: this build of the library has no shadow-map kernels (the native-storage build's filterable formats are not built)", who);
+    return MIFX_ERR_NOT_IMPLEMENTED;
+}
+mifx_status launch_shadow_convert(hipStream_t, DeviceScratch&, const ShadowArrK&, const FilterableArrK&, const ShadowConvK&, uint32_t, bool, bool)
+{
+    return no_shadow_kernels("mifx_shadow_convert_to_filterable");
+}
+mifx_status launch_shadow_filter(hipStream_t, Img, Img, Img, const ShadowLookupK&, const ShadowArrK&, const FilterableArrK&, uint32_t, bool, bool)
+{
+    return no_shadow_kernels("mifx_shadow_map_filter");
+}
 } // namespace mifx
 #endif // MIFX_STORAGE_H4

@@ -1,11 +1,14 @@
 // TEST INFRASTRUCTURE ONLY.  The product's HOST code (diligentfx_amd/csrc/api_*.cpp, mifx_core.cpp -- the objects behind the C ABI: what is prepared, cleared, ping-ponged and
 // launched in which order) linked WITHOUT its kernels and without a GPU: this file stands in for the two things below it --
 //   * the HIP runtime: memory is host memory, streams and events do nothing (everything "executes" at once, in program order);
-//   * the kernel launchers (mifx_host.h launch_*, defined in the .hip files): each hands its arguments to a callback, which the test installs (tests/cpu_product/device.py runs
+//   * the kernel launchers (mifx_host.h and mifx_*_host.h launch_*, defined in the .hip files): each hands its arguments to a callback, which the test installs (tests/cpu_product/device.py runs
 //     the reference's own shader for the pass on the planes it was given: oracle/_ref).
 // What this makes testable on the CPU: the product's sequencing against the executed reference host classes (oracle/refhost) over random sequences of frames.  What it is not: a CPU
 // path of the product -- nothing in diligentfx_amd/ builds or loads it, and the library that ships fails without its HIP kernels and a device.
 #include "mifx_host.h"
+#include "mifx_grid_host.h"
+#include "mifx_selection_host.h"
+#include "mifx_shadows_host.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -114,7 +117,7 @@ uint32_t native_texel_size(uint32_t fmt)
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- the launchers (generated from mifx_host.h by tests/cpu_product/gen_stubs.py)
+// ---------------------------------------------------------------------------------------------------------------- the launchers (generated from mifx_host.h and mifx_*_host.h by tests/cpu_product/gen_stubs.py)
 mifx_status launch_fill_f32(hipStream_t s, Img plane, int floats_per_texel, float value)
 {
     t_stream = s;
@@ -389,5 +392,35 @@ mifx_status launch_envmap(hipStream_t s, const mifx_envmap_render_attribs& a, co
 {
     t_stream = s;
     return record("envmap", a, tm, cam, prev, depth, color, motion);
+}
+mifx_status launch_coordinate_grid(hipStream_t s, Img rows, Img target, Img raw, const GridCamK& cam, const mifx_coordinate_grid_attribs& a, uint32_t flags)
+{
+    t_stream = s;
+    return record("coordinate_grid", rows, target, raw, cam, a, flags);
+}
+mifx_status launch_copy_frame_grid(hipStream_t s, Img in, bool packedIn, Img depth, Img out, const mifx_tone_mapping_attribs& attr, float ave_log_lum, uint32_t tonemap_flags, const float* aveLum, const GridCamK& cam, const mifx_coordinate_grid_attribs& a, uint32_t grid_flags)
+{
+    t_stream = s;
+    return record("copy_frame_grid", in, packedIn, depth, out, attr, ave_log_lum, tonemap_flags, aveLum, cam, a, grid_flags);
+}
+mifx_status launch_jump_flood(hipStream_t s, Img selectionDepth, float clearDepth, int iterations, Img tmp0, Img tmp1, Img out, int rowBegin, int rowEnd)
+{
+    t_stream = s;
+    return record("jump_flood", selectionDepth, clearDepth, iterations, tmp0, tmp1, out, rowBegin, rowEnd);
+}
+mifx_status launch_composite_selection(hipStream_t s, const mifx_composite_attribs& a, const SelectionK& sel, const mifx_image2d* out, int row_begin, int row_end, const SsrCleanupIn* r7)
+{
+    t_stream = s;
+    return record("composite_selection", a, sel, out, row_begin, row_end, r7);
+}
+mifx_status launch_shadow_convert(hipStream_t s, DeviceScratch& scratch, const ShadowArrK& src, const FilterableArrK& dst, const ShadowConvK& k, uint32_t mode, bool skipBlur, bool fused)
+{
+    t_stream = s;
+    return record("shadow_convert", scratch, src, dst, k, mode, skipBlur, fused);
+}
+mifx_status launch_shadow_filter(hipStream_t s, Img depth, Img light, Img cascade, const ShadowLookupK& k, const ShadowArrK& map, const FilterableArrK& filterable, uint32_t mode, bool best, bool across)
+{
+    t_stream = s;
+    return record("shadow_filter", depth, light, cascade, k, map, filterable, mode, best, across);
 }
 } // namespace mifx

@@ -38,6 +38,18 @@ def run(cpu_lib, *args, timeout=900, **extra_env):
     return r.stdout
 
 
+def test_the_launcher_stubs_are_what_the_generator_prints():
+    """Everything below the "the launchers" marker of stub_device.cpp is the output of gen_stubs.py for the current mifx_host.h / mifx_*_host.h: a launcher added or changed
+    in a header cannot miss the stub file."""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "cpu_product", "gen_stubs.py")], cwd=ROOT, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = open(os.path.join(HERE, "cpu_product", "stub_device.cpp")).read().splitlines(keepends=True)
+    marker = [i for i, line in enumerate(lines) if line.startswith("// ---") and "the launchers" in line]
+    assert len(marker) == 1, marker
+    assert "".join(lines[marker[0] + 1:]) == r.stdout, "stub_device.cpp: re-run tests/cpu_product/gen_stubs.py and paste its output below the marker"
+    assert r.stdout.count("mifx_status launch_") >= 61  # (the 55 launchers of mifx_host.h and the six of the mifx_*_host.h headers)
+
+
 def test_host_objects_on_the_cpu_equal_the_reference_sequencing(cpu_lib):
     out = run(cpu_lib, "scenarios")
     assert out.count("cpu product: scenario OK") >= 7, out
