@@ -76,7 +76,7 @@ int mifx_bloom::mip_count(const mifx_bloom_attribs& a) const { return int(a.Radi
 // Row windows of the fine levels (mifx_rows.h).  Footprints: a 13-tap down-sample texel r reads source rows 2r - 2 .. 2r + 3 (taps at +-2
 // texels around 2r + 1/2, bilinear: +1), an up-sample texel y reads coarse rows y/2 - 2 .. y/2 + 2 (3x3 tent, bilinear: +1); one extra row
 // of slack per level.
-mifx_bloom::Plan mifx_bloom::make_plan(Rows band, Rows need, int mipCount) const
+mifx_bloom::Plan mifx_bloom::make_plan(Rows band, Rows need, int mipCount, bool halo_level0) const
 {
     Plan p;
     const int H = int(h);
@@ -106,7 +106,7 @@ mifx_bloom::Plan mifx_bloom::make_plan(Rows band, Rows need, int mipCount) const
 }
 
 // Bloom::Execute (Bloom.cpp:407-446): prefilter (:288-311), downsample loop (:313-337), upsample loop + final composite (:339-396)
-mifx_status mifx_bloom::run(const mifx_bloom_render_attribs* ra, int phase, const FusedToneMap* tone_map)
+mifx_status mifx_bloom::run(const mifx_bloom_render_attribs* ra, int phase, const FusedToneMap* tone_map, const Request& req)
 {
     MIFX_RANGE("Bloom");
     mifx_postfx* c = ra->postfx ? ra->postfx : ctx;
@@ -122,7 +122,7 @@ mifx_status mifx_bloom::run(const mifx_bloom_render_attribs* ra, int phase, cons
     MIFX_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const Rows need = c->needed_rows(int(h));
-    const Plan p    = make_plan(c->band, need, mipCount);
+    const Plan p    = make_plan(c->band, need, mipCount, req.halo_level0);
     MIFX_REQUIRE(phase == 0 || p.G >= 0, "mifx_bloom_execute: phased execution needs a row band (mifx_chain_set_row_band)");
     MIFX_REQUIRE(phase != 0 || p.G < 0, "mifx_bloom_execute: a row band is set; run the two phases around the gather of down[%d]", p.G);
     auto dwin = [&](int i) { return p.G >= 0 ? win(down[i]->view(), p.down[i]) : down[i]->view(); };
@@ -148,12 +148,7 @@ mifx_status mifx_bloom::run(const mifx_bloom_render_attribs* ra, int phase, cons
             MifxKernelTimer timer(c, "bloom_prefilter_kernel");
             MIFX_CHECK(launch_bloom_prefilter(s, color, p.G >= 0 ? win(down[0]->view(), p.compute0) : down[0]->view(), a, packed));
         }
-        if (p.G >= 0 && after_level0) // (the rows of level 0 this rank reads but does not own: from the ranks that do)
-        {
-            auto hook = std::move(after_level0);
-            after_level0 = nullptr;
-            MIFX_CHECK(hook(*down[0], s));
-        }
+        if (p.G >= 0 && req.after_level0) MIFX_CHECK(req.after_level0(*down[0], s)); // (the rows of level 0 this rank reads but does not own: from the ranks that do)
         for (int i = 1; i < wide && (p.G < 0 || i <= p.G); ++i) MIFX_CHECK(launch_bloom_downsample(s, down[i - 1]->view(), dwin(i)));
         if (phase == 1) return MIFX_OK; // the caller now assembles down[G] from all ranks
     }
@@ -207,7 +202,7 @@ mifx_status mifx_bloom_execute(mifx_bloom* fx, const mifx_bloom_render_attribs* 
         set_error("mifx_bloom_execute: mifx_bloom_prepare must be called first");
         return MIFX_ERR_INVALID_OP;
     }
-    return fx->run(ra, 0);
+    return fx->run(ra, 0, nullptr, mifx_bloom::Request{});
 }
 
 mifx_status mifx_bloom_get_output(mifx_bloom* fx, mifx_image2d* out)
@@ -302,8 +297,11 @@ mifx_status mifx_taa_reset_history(mifx_taa* fx)
 mifx_status mifx_taa_execute(mifx_taa* fx, const mifx_taa_render_attribs* ra)
 {
     MIFX_REQUIRE(fx != nullptr && ra != nullptr && ra->attribs != nullptr, "mifx_taa_execute: null argument");
-    const mifx::TaaFusedComposite* fused = fx->fused_composite; // (a per-frame request: taken and cleared before anything can return)
-    fx->fused_composite = nullptr;
+    return fx->run(ra, nullptr);
+}
+mifx_status mifx_taa::run(const mifx_taa_render_attribs* ra, const mifx::TaaFusedComposite* fused)
+{
+    mifx_taa* const fx = this;
     mifx_postfx* ctx = ra->postfx ? ra->postfx : fx->ctx;
     if (!fx->prepared || !ctx || !ctx->executed)
     {

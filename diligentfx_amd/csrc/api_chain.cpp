@@ -154,8 +154,11 @@ static mifx_status chain_shade(mifx_chain* chain, const mifx_chain_frame* f, con
 // USD_Renderer.cpp:98).  A specular-glossiness shade would read the same plane as PhysicalDesc (specular colour + glossiness) and SSR / the composite would then take
 // their roughness from the specular-colour channels: refused.  A caller with specular-glossiness inputs shades with mifx_pbr_shade_execute and hands the chain's
 // other effects the plane mifx_pbr_specgloss_to_material produces.
-static mifx_status chain_check_workflow(const mifx_chain_frame* f)
+// (with the check that every attribs pointer is there: what each entry that takes a frame asks of it; `entry` = its name)
+static mifx_status chain_check_frame(const mifx_chain_frame* f, const char* entry)
 {
+    MIFX_REQUIRE(f->curr_camera && f->prev_camera && f->ibl && f->pbr && f->ssao && f->ssr && f->taa && f->bloom && f->tone_mapping,
+                 "%s: every attribs pointer of mifx_chain_frame must be set", entry);
     MIFX_REQUIRE(f->pbr->Workflow == MIFX_PBR_WORKFLOW_METALLIC_ROUGHNESS,
                  "mifx_chain_execute: Workflow %d: the chain's material plane is the metallic-roughness Material target (see mifx_pbr_specgloss_to_material)", f->pbr->Workflow);
     return MIFX_OK;
@@ -176,17 +179,22 @@ static mifx_status chain_selection_composite(mifx_chain* chain, const mifx_chain
 }
 
 // The composite draw (HnPostProcess.psh:145-185).  With fuse_ssr_cleanup the kernel evaluates SSR's last pass (R7, the bilateral cleanup) for its own pixel from the
-// effect's accumulated radiance instead of reading the plane R7 would have written (mifx_ssr_execute stopped after R6: mifx_objects.h `defer_cleanup`).
+// effect's accumulated radiance instead of reading the plane R7 would have written (mifx_ssr::run stopped after R6: mifx_ssr::Request::defer_cleanup).
 // With fuse_composite_taa on top of that (round 5) nothing is launched here: the TAA kernel of this frame evaluates the composite for the texels of its colour tile
-// (taa.hip) -- the request is left in chain->pending_fused and handed to mifx_taa_execute by chain_taa below.  Not on TAA's placeholder frame (a copy of the plane).
+// (taa.hip) -- the request is left in `hand` and given to mifx_taa::run by chain_taa below.  Not on TAA's placeholder frame (a copy of the plane).
+// `hand` is a local of the scope that calls both steps: the image descriptors its attribs point to are that scope's locals and the frame's.
+struct CompositeHandOver
+{
+    mifx_composite_attribs  attribs{}; // what chain_composite would have launched
+    mifx::TaaFusedComposite fused{nullptr, nullptr};
+};
 static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* radiance, const mifx_image2d* spec, const mifx_image2d* ssao_out,
-                                   const mifx_image2d* comp)
+                                   const mifx_image2d* comp, CompositeHandOver& hand)
 {
     mifx_postfx* ctx = chain->ctx;
     mifx_ssr*    ssr = chain->ssr;
     mifx_image2d ssr_out{};
     const bool fused = ssr->cleanup_pending; // (set by an execute that deferred the pass)
-    chain->pending_fused = mifx::TaaFusedComposite{nullptr, nullptr};
     if (!fused) MIFX_CHECK(mifx_ssr_get_output(ssr, &ssr_out));
     mifx_composite_attribs ca{radiance, spec, fused ? radiance /* not read */ : &ssr_out, ssao_out, f->gbuffer.normal, f->gbuffer.base_color, f->gbuffer.material, f->ibl->brdf_lut,
                               f->curr_camera, f->ssr_scale, f->ssao_scale, nullptr, f->ave_log_lum};
@@ -194,8 +202,8 @@ static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f,
     if (!fused) return mifx_composite_execute(ctx, &ca, comp);
     if (chain->fuse_composite_taa && chain->taa->technique_ready)
     {
-        chain->pending_composite = ca; // (its image descriptors are the caller's locals and the frame's: alive until the TAA call of this frame, made from the same scope)
-        chain->pending_fused     = mifx::TaaFusedComposite{&chain->pending_composite, &ssr->cleanup_in};
+        hand.attribs = ca;
+        hand.fused   = mifx::TaaFusedComposite{&hand.attribs, &ssr->cleanup_in};
         return MIFX_OK;
     }
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
@@ -204,7 +212,7 @@ static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f,
     return launch_composite(ctx->stream, ca, comp, rows.b, rows.e, &ssr->cleanup_in);
 }
 // TemporalAntiAliasing::Execute on the jittered composite (:871-897) -- on the plane, or with the composite evaluated in place (above)
-static mifx_status chain_taa(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* comp)
+static mifx_status chain_taa(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* comp, const CompositeHandOver& hand)
 {
     // a selected prim other than the previous frame's resets the accumulation (HnProcessSelectionTask.cpp:293-300)
     mifx_taa_attribs taa_attribs{};
@@ -215,10 +223,58 @@ static mifx_status chain_taa(mifx_chain* chain, const mifx_chain_frame* f, const
         chain->last_selection_id = chain->selection_attribs.selection_id;
     }
     mifx_taa_render_attribs ta{chain->ctx, comp, chain->has_selection && f->taa != nullptr ? &taa_attribs : f->taa};
-    const mifx::TaaFusedComposite fused = chain->pending_fused; // (a per-frame request: cleared whatever the call returns)
-    chain->pending_fused = mifx::TaaFusedComposite{nullptr, nullptr};
-    chain->taa->fused_composite = fused.attribs ? &fused : nullptr;
-    return mifx_taa_execute(chain->taa, &ta);
+    return chain->taa->run(&ta, hand.fused.attribs ? &hand.fused : nullptr);
+}
+
+// DepthOfField::Execute on the TAA output (:899-909; m_UseDOF requires TAA, :654), on the rows the context needs: `taa_out` becomes its output
+static mifx_status chain_depth_of_field(mifx_chain* chain, const mifx_chain_frame* f, mifx_image2d* taa_out)
+{
+    if (!chain->dof) return MIFX_OK;
+    MIFX_CHECK(mifx_dof_prepare(chain->dof, chain->ctx, chain->dof_flags));
+    mifx_dof_render_attribs da{chain->ctx, taa_out, f->gbuffer.depth, &chain->dof_attribs};
+    MIFX_CHECK(mifx_dof_execute(chain->dof, &da));
+    return mifx_dof_get_output(chain->dof, taa_out);
+}
+
+// The frame's last draw, the copy-frame pass on the Bloom output (HnPostProcessTask.cpp:920-926): ToneMap (+ sRGB) into the target's own format, with the coordinate grid
+// (mifx_chain_set_coordinate_grid, HnCopyFrame.psh:27-63: on the G-buffer depth and the frame's camera, on the rows the context needs -- whole-frame pixel coordinates and a
+// depth plane every rank holds whole, so a row band equals the rows of the unsharded frame), or plain.  With auto exposure on, fAveLogLum is the adapted average luminance.
+static mifx_status chain_copy_frame(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* bloom_out, const mifx_image2d* out_ldr, const mifx_native_image* out_native)
+{
+    mifx_postfx* ctx = chain->ctx;
+    if (out_native != nullptr)
+    {
+        // the copy-frame target in its own format (the swap chain's in the reference): the conversion is the tail of the tone-map kernel
+        MIFX_REQUIRE(chain->auto_exposure == nullptr, "mifx_chain_execute_native: not combined with auto exposure");
+        MIFX_REQUIRE(!chain->has_grid, "mifx_chain_execute_native: not combined with the coordinate grid");
+        return mifx_tonemap_execute_native(ctx, bloom_out, out_native, f->tone_mapping, f->ave_log_lum, f->tonemap_flags);
+    }
+    if (chain->has_grid)
+        return copy_frame_grid_run(ctx, bloom_out, f->gbuffer.depth, f->curr_camera, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->auto_exposure, chain->grid_attribs,
+                                   chain->grid_flags, out_ldr, "mifx_chain_execute");
+    if (chain->auto_exposure) return mifx_tonemap_execute_auto(ctx, bloom_out, out_ldr, f->tone_mapping, chain->auto_exposure, f->tonemap_flags);
+    return mifx_tonemap_execute(ctx, bloom_out, out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags);
+}
+
+// Bloom::Execute on the TAA (or depth-of-field) output (HnPostProcessTask.cpp:911-918) and the copy-frame draw
+static mifx_status chain_bloom_and_tone_map(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d& taa_out, const mifx_image2d* out_ldr, const mifx_native_image* out_native,
+                                            hipEvent_t between)
+{
+    mifx_postfx* ctx = chain->ctx;
+    mifx_image2d bloom_out;
+    mifx_bloom_render_attribs ba{ctx, &taa_out, f->bloom};
+    // With a plain fp32 target and a constant average luminance the copy-frame ToneMap() (:920-926) is the tail of Bloom's final up-sample: the Bloom output
+    // is written as always, the LDR frame in the same pass (bit-identical to the two passes; the "tonemap" stage time is then part of "bloom").
+    // (with the coordinate grid the frame's last pass is the copy-frame draw with the grid, which reads the Bloom output and the depth: not fused either)
+    const bool fuse_tone_map = out_native == nullptr && chain->auto_exposure == nullptr && chain->fuse_tone_map && !chain->has_grid;
+    const mifx_bloom::FusedToneMap ftm{out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->fuse_bloom_output};
+    MIFX_REQUIRE(chain->bloom->prepared, "mifx_chain_execute: bloom resources are not prepared");
+    MIFX_CHECK(chain->bloom->run(&ba, 0, fuse_tone_map ? &ftm : nullptr, mifx_bloom::Request{}));
+    if (between) MIFX_HIP_CHECK(hipEventRecord(between, ctx->stream));
+    if (fuse_tone_map) return MIFX_OK; // (the frame is written; the Bloom output plane on demand, mifx_bloom::run_deferred_output)
+    MIFX_CHECK(mifx_bloom_get_output(chain->bloom, &bloom_out));
+    if (out_native == nullptr && chain->auto_exposure) MIFX_CHECK(mifx_autoexposure_execute(chain->auto_exposure, &bloom_out, chain->ae_elapsed, chain->ae_adapt ? 1 : 0));
+    return chain_copy_frame(chain, f, &bloom_out, out_ldr, out_native);
 }
 
 // HnPostProcessTask::Prepare: per-frame PrepareResources in the order PostFX, SSAO, SSR, TAA, Bloom (:671-682), then the chain's own planes
@@ -235,6 +291,20 @@ extern "C++" mifx_status mifx::chain_prepare_resources(mifx_chain* chain, const 
     MIFX_CHECK(chain->specular_ibl.alloc(W, H, MIFX_FORMAT_F32X4));
     MIFX_CHECK(chain->composite.alloc(W, H, MIFX_FORMAT_F32X4));
     return MIFX_OK;
+}
+
+// The render attribs of PostFX prep, SSR and SSAO for this frame (`radiance`: the caller's descriptor of the shaded colour, which SSR reads)
+struct FrameAttribs
+{
+    mifx_postfx_render_attribs pa;
+    mifx_ssr_render_attribs    sr;
+    mifx_ssao_render_attribs   sa;
+};
+static FrameAttribs chain_frame_attribs(mifx_postfx* ctx, const mifx_chain_frame* f, const mifx_image2d* radiance)
+{
+    return {{f->gbuffer.depth, f->prev_depth, f->motion, f->curr_camera, f->prev_camera},
+            {ctx, radiance, f->gbuffer.depth, f->gbuffer.normal, f->gbuffer.material, f->motion, f->ssr},
+            {ctx, f->gbuffer.depth, f->gbuffer.normal, f->ssao}};
 }
 
 // Creates the chain's extra streams and events on first use.
@@ -263,12 +333,6 @@ extern "C++" bool mifx::chain_lanes_continue(mifx_chain* chain)
     chain->prep_consumed = false; // (set again by a frame that got as far as recording the event: an error return leaves it off)
     return cont;
 }
-
-static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* radiance, const mifx_image2d* spec, const mifx_image2d* ssao_out,
-                                   const mifx_image2d* comp);
-static mifx_status chain_taa(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* comp);
-static mifx_status chain_bloom_and_tone_map(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d& taa_out, const mifx_image2d* out_ldr, const mifx_native_image* out_native,
-                                            hipEvent_t between);
 
 // mifx_chain_set_overlap 3: one frame as three lanes that slide against each other across frames.  The frame's kernels fall into three resource classes --
 //   lane S (side stream):    PBR shade (+ R2), PostFX prep, Hi-Z (R1), SSAO A2 .. A8      vector-ALU bound (shade, A3) + their small pyramids
@@ -398,9 +462,7 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
         MIFX_HIP_CHECK(hipStreamWaitEvent(X, chain->evFork, 0));
     }
     if (pipelined && !chain->edges.empty()) ctx->kernel_hook = [chain](const char* name, bool begin) { chain_kernel_hook(chain, name, begin); };
-    mifx_postfx_render_attribs pa{f->gbuffer.depth, f->prev_depth, f->motion, f->curr_camera, f->prev_camera};
-    mifx_ssr_render_attribs    sr{ctx, &radiance, f->gbuffer.depth, f->gbuffer.normal, f->gbuffer.material, f->motion, f->ssr};
-    mifx_ssao_render_attribs   sa{ctx, f->gbuffer.depth, f->gbuffer.normal, f->ssao};
+    const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
     // lane S: shade, prep
     ctx->stream = S;
     MIFX_CHECK(chain_shade(chain, f, &radiance, &spec));
@@ -412,10 +474,7 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
     // (mode 5 with R7 as a pass of its own -- fusion bit 2 off: R7 of this frame overwrites the SSR output plane the PREVIOUS frame's composite, now on lane M, may still be
     //  reading; found by tests/cpu_product/order.py.  That configuration waits for the previous frame's composite / TAA here; with R7 inside the composite there is no such plane)
     if (late && !chain->fuse_ssr_cleanup) MIFX_HIP_CHECK(hipStreamWaitEvent(X, chain->evPrepConsumed, 0));
-    chain->ssr->defer_cleanup = chain->fuse_ssr_cleanup;
-    chain->ssr->hiz_stream    = S;
-    chain->ssr->hiz_done      = chain->evPrep;
-    MIFX_CHECK(mifx_ssr_execute(chain->ssr, &sr));
+    MIFX_CHECK(chain->ssr->run(&sr, mifx_ssr::Request{chain->fuse_ssr_cleanup, S, chain->evPrep}));
     // lane S: SSAO
     ctx->stream = S;
     MIFX_CHECK(mifx_ssao_execute(chain->ssao, &sa));
@@ -430,18 +489,13 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
     ctx->stream = T;
     MIFX_HIP_CHECK(hipStreamWaitEvent(T, chain->evSsao, 0));
     mifx_image2d ssao_out, taa_out;
+    CompositeHandOver hand;
     MIFX_CHECK(mifx_ssao_get_output(chain->ssao, &ssao_out));
-    MIFX_CHECK(chain_composite(chain, f, &radiance, &spec, &ssao_out, &comp));
+    MIFX_CHECK(chain_composite(chain, f, &radiance, &spec, &ssao_out, &comp, hand));
     if (!late) MIFX_HIP_CHECK(hipStreamWaitEvent(X, chain->evBloomDone, 0)); // (recorded by the previous frame; never recorded = no wait.  Mode 5: the previous Bloom is earlier on this stream)
-    MIFX_CHECK(chain_taa(chain, f, &comp));
+    MIFX_CHECK(chain_taa(chain, f, &comp, hand));
     MIFX_CHECK(mifx_taa_get_output(chain->taa, 0, &taa_out));
-    if (chain->dof)
-    {
-        MIFX_CHECK(mifx_dof_prepare(chain->dof, ctx, chain->dof_flags));
-        mifx_dof_render_attribs da{ctx, &taa_out, f->gbuffer.depth, &chain->dof_attribs};
-        MIFX_CHECK(mifx_dof_execute(chain->dof, &da));
-        MIFX_CHECK(mifx_dof_get_output(chain->dof, &taa_out));
-    }
+    MIFX_CHECK(chain_depth_of_field(chain, f, &taa_out));
     MIFX_HIP_CHECK(hipEventRecord(chain->evPrepConsumed, T));
     if (pipelined) MIFX_HIP_CHECK(hipEventRecord(chain->evXEnd[k & 1u], T));
     // lane M: Bloom, tone map
@@ -461,9 +515,7 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
 static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, const mifx_native_image* out_native)
 {
     MIFX_REQUIRE(chain != nullptr && f != nullptr && (out_ldr != nullptr) != (out_native != nullptr), "mifx_chain_execute: null argument");
-    MIFX_REQUIRE(f->curr_camera && f->prev_camera && f->ibl && f->pbr && f->ssao && f->ssr && f->taa && f->bloom && f->tone_mapping,
-                 "mifx_chain_execute: every attribs pointer of mifx_chain_frame must be set");
-    MIFX_CHECK(chain_check_workflow(f));
+    MIFX_CHECK(chain_check_frame(f, "mifx_chain_execute"));
     mifx_postfx* ctx = chain->ctx;
     MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
     if (chain->overlap >= 3 && !chain->profiling) return chain_execute_lanes(chain, f, out_ldr, out_native, chain->overlap);
@@ -476,9 +528,7 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
     };
     MIFX_CHECK(mark());
 
-    mifx_postfx_render_attribs pa{f->gbuffer.depth, f->prev_depth, f->motion, f->curr_camera, f->prev_camera};
-    mifx_ssr_render_attribs    sr{ctx, &radiance, f->gbuffer.depth, f->gbuffer.normal, f->gbuffer.material, f->motion, f->ssr};
-    mifx_ssao_render_attribs   sa{ctx, f->gbuffer.depth, f->gbuffer.normal, f->ssao};
+    const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
     if (chain->overlap && !chain->profiling)
     {
         // Two dependency chains:  shade -> SSR (needs the radiance and the prep outputs)   |   prep -> SSAO (depth / normals only).
@@ -508,8 +558,7 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
         MIFX_CHECK(st);
         MIFX_CHECK(chain_shade(chain, f, &radiance, &spec)); // (measured: the shade on the side stream as well, in front of prep, changes nothing: 1.747 vs 1.751 ms)
         MIFX_HIP_CHECK(hipStreamWaitEvent(main, chain->evPrep, 0));
-        chain->ssr->defer_cleanup = chain->fuse_ssr_cleanup;
-        MIFX_CHECK(mifx_ssr_execute(chain->ssr, &sr));
+        MIFX_CHECK(chain->ssr->run(&sr, mifx_ssr::Request{chain->fuse_ssr_cleanup}));
         MIFX_HIP_CHECK(hipStreamWaitEvent(main, chain->evSsao, 0));
         stage += 4;
     }
@@ -522,30 +571,23 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
         MIFX_CHECK(mifx_postfx_execute(ctx, &pa));
         MIFX_CHECK(mark());
         // ScreenSpaceReflection::Execute (:811-822)
-        chain->ssr->defer_cleanup = chain->fuse_ssr_cleanup;
-        MIFX_CHECK(mifx_ssr_execute(chain->ssr, &sr));
+        MIFX_CHECK(chain->ssr->run(&sr, mifx_ssr::Request{chain->fuse_ssr_cleanup}));
         MIFX_CHECK(mark());
         // ScreenSpaceAmbientOcclusion::Execute (:824-832)
         MIFX_CHECK(mifx_ssao_execute(chain->ssao, &sa));
         MIFX_CHECK(mark());
     }
-    mifx_image2d ssao_out, taa_out, bloom_out;
+    mifx_image2d ssao_out, taa_out;
+    CompositeHandOver hand;
     MIFX_CHECK(mifx_ssao_get_output(chain->ssao, &ssao_out));
     // composite draw (:834-869), no tone mapping while TAA is on
-    MIFX_CHECK(chain_composite(chain, f, &radiance, &spec, &ssao_out, &comp));
+    MIFX_CHECK(chain_composite(chain, f, &radiance, &spec, &ssao_out, &comp, hand));
     MIFX_CHECK(mark());
     // TemporalAntiAliasing::Execute on the jittered composite (:871-897)
-    MIFX_CHECK(chain_taa(chain, f, &comp));
+    MIFX_CHECK(chain_taa(chain, f, &comp, hand));
     MIFX_CHECK(mifx_taa_get_output(chain->taa, 0, &taa_out));
     MIFX_CHECK(mark());
-    // DepthOfField::Execute on the TAA output (:899-909; m_UseDOF requires TAA, :654)
-    if (chain->dof)
-    {
-        MIFX_CHECK(mifx_dof_prepare(chain->dof, ctx, chain->dof_flags));
-        mifx_dof_render_attribs da{ctx, &taa_out, f->gbuffer.depth, &chain->dof_attribs};
-        MIFX_CHECK(mifx_dof_execute(chain->dof, &da));
-        MIFX_CHECK(mifx_dof_get_output(chain->dof, &taa_out));
-    }
+    MIFX_CHECK(chain_depth_of_field(chain, f, &taa_out));
     chain->prep_consumed = false;
     if (chain->overlap >= 2 && !chain->profiling && chain->evPrepConsumed)
     {
@@ -558,53 +600,6 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
     ++stage;
     MIFX_CHECK(mark());
     chain->timed = chain->profiling;
-    return MIFX_OK;
-}
-
-// mifx_chain_set_coordinate_grid: the copy-frame draw with the grid (HnCopyFrame.psh:27-63) on the Bloom output, the G-buffer depth and the frame's camera, on the rows the
-// context needs; fAveLogLum from the auto-exposure object when the chain has one.  Whole-frame pixel coordinates and a depth plane every rank holds whole: a row band
-// equals the rows of the unsharded frame.
-static mifx_status chain_copy_frame_grid(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* bloom_out, const mifx_image2d* out_ldr)
-{
-    return copy_frame_grid_run(chain->ctx, bloom_out, f->gbuffer.depth, f->curr_camera, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->auto_exposure, chain->grid_attribs,
-                               chain->grid_flags, out_ldr, "mifx_chain_execute");
-}
-
-// Bloom::Execute on the TAA (or depth-of-field) output (HnPostProcessTask.cpp:911-918) and the copy-frame draw = ToneMap (+ sRGB) (:920-926)
-static mifx_status chain_bloom_and_tone_map(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d& taa_out, const mifx_image2d* out_ldr, const mifx_native_image* out_native,
-                                            hipEvent_t between)
-{
-    mifx_postfx* ctx = chain->ctx;
-    mifx_image2d bloom_out;
-    mifx_bloom_render_attribs ba{ctx, &taa_out, f->bloom};
-    // With a plain fp32 target and a constant average luminance the copy-frame ToneMap() (:920-926) is the tail of Bloom's final up-sample: the Bloom output
-    // is written as always, the LDR frame in the same pass (bit-identical to the two passes; the "tonemap" stage time is then part of "bloom").
-    // (with the coordinate grid the frame's last pass is the copy-frame draw with the grid, which reads the Bloom output and the depth: not fused either)
-    const bool fuse_tone_map = out_native == nullptr && chain->auto_exposure == nullptr && chain->fuse_tone_map && !chain->has_grid;
-    const mifx_bloom::FusedToneMap ftm{out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->fuse_bloom_output};
-    MIFX_REQUIRE(chain->bloom->prepared, "mifx_chain_execute: bloom resources are not prepared");
-    MIFX_CHECK(chain->bloom->run(&ba, 0, fuse_tone_map ? &ftm : nullptr));
-    if (between) MIFX_HIP_CHECK(hipEventRecord(between, ctx->stream));
-    if (fuse_tone_map) return MIFX_OK; // (the frame is written; the Bloom output plane on demand, mifx_bloom::run_deferred_output)
-    MIFX_CHECK(mifx_bloom_get_output(chain->bloom, &bloom_out));
-    // copy-frame draw = ToneMap (+ sRGB) (:920-926); with auto exposure on, fAveLogLum is the adapted average luminance of the scene colour
-    if (out_native != nullptr)
-    {
-        // the copy-frame target in its own format (the swap chain's in the reference): the conversion is the tail of the tone-map kernel
-        MIFX_REQUIRE(chain->auto_exposure == nullptr, "mifx_chain_execute_native: not combined with auto exposure");
-        MIFX_REQUIRE(!chain->has_grid, "mifx_chain_execute_native: not combined with the coordinate grid");
-        MIFX_CHECK(mifx_tonemap_execute_native(ctx, &bloom_out, out_native, f->tone_mapping, f->ave_log_lum, f->tonemap_flags));
-    }
-    else if (chain->auto_exposure)
-    {
-        MIFX_CHECK(mifx_autoexposure_execute(chain->auto_exposure, &bloom_out, chain->ae_elapsed, chain->ae_adapt ? 1 : 0));
-        if (chain->has_grid) MIFX_CHECK(chain_copy_frame_grid(chain, f, &bloom_out, out_ldr));
-        else MIFX_CHECK(mifx_tonemap_execute_auto(ctx, &bloom_out, out_ldr, f->tone_mapping, chain->auto_exposure, f->tonemap_flags));
-    }
-    else if (chain->has_grid)
-        MIFX_CHECK(chain_copy_frame_grid(chain, f, &bloom_out, out_ldr));
-    else
-        MIFX_CHECK(mifx_tonemap_execute(ctx, &bloom_out, out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags));
     return MIFX_OK;
 }
 
@@ -645,13 +640,13 @@ extern "C++" bool mifx::shard_bloom_halo_enabled() // MIFX_SHARD_BLOOM_HALO=0: r
 }
 namespace
 {
-ShardRows shard_rows(const mifx_chain* chain, const mifx_chain_frame* f, Rows band)
+ShardRows shard_rows(const mifx_chain* chain, const mifx_chain_frame* f, Rows band, bool halo_level0)
 {
     const int H = int(f->frame.Height);
     ShardRows r;
     r.band = rows_clip(band, H);
     r.need = chain->auto_exposure ? rows_expand(r.band, 1, H) : r.band;
-    const mifx_bloom::Plan p = chain->bloom->make_plan(r.band, r.need, chain->bloom->mip_count(*f->bloom));
+    const mifx_bloom::Plan p = chain->bloom->make_plan(r.band, r.need, chain->bloom->mip_count(*f->bloom), halo_level0);
     r.post = p.G >= 0 ? rows_hull(p.taa, r.need) : Rows{0, H};
     r.taa  = r.post;
     // depth of field sits between TAA and Bloom: its output on r.post needs the TAA output on the colour rows of mifx_dof::windows (bokeh gather and fill radii)
@@ -686,18 +681,16 @@ extern "C" mifx_status mifx_chain_set_row_band(mifx_chain* chain, int32_t row_be
 //   phase 4: luminance reduction + adaptation (the same 64x64 values in the same order on every rank: the average is bit-identical), tone map
 // follows (without auto exposure phase 4 does nothing).
 // (SSAO before SSR: the reference runs SSR first, but the two effects only share read-only inputs.)
-extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, int32_t phase)
+// `req`: what mifx_chain_execute_sharded asks of this one call (mifx_objects.h); empty for a caller that drives the phases itself.
+extern "C++" mifx_status mifx::chain_execute_phase(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, int32_t phase, const ChainPhaseRequest& req)
 {
     MIFX_REQUIRE(chain != nullptr && f != nullptr && out_ldr != nullptr && phase >= 0 && phase <= 4, "mifx_chain_execute_phase: bad argument");
     MIFX_REQUIRE(!chain->band.empty(), "mifx_chain_execute_phase: no row band set (mifx_chain_set_row_band)");
-    MIFX_REQUIRE(f->curr_camera && f->prev_camera && f->ibl && f->pbr && f->ssao && f->ssr && f->taa && f->bloom && f->tone_mapping,
-                 "mifx_chain_execute_phase: every attribs pointer of mifx_chain_frame must be set");
-    MIFX_CHECK(chain_check_workflow(f));
+    MIFX_CHECK(chain_check_frame(f, "mifx_chain_execute_phase"));
     mifx_postfx* ctx = chain->ctx;
-    const uint32_t W = f->frame.Width, H = f->frame.Height;
     if (phase == 0) MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
     const mifx_image2d radiance = chain->radiance.desc(), spec = chain->specular_ibl.desc(), comp = chain->composite.desc();
-    const ShardRows r = shard_rows(chain, f, chain->band);
+    const ShardRows r = shard_rows(chain, f, chain->band, req.bloom.halo_level0);
     struct NeedGuard // the row request is per call: never leave one behind for a later whole-frame call
     {
         mifx_postfx* c;
@@ -710,6 +703,7 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
     }
     mifx_image2d ssao_out, taa_out, bloom_out;
     mifx_bloom_render_attribs ba{ctx, nullptr, f->bloom};
+    const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
     // A history-halo exchange of the previous sharded frame that is still travelling (mifx_chain_execute_sharded, async_halos) is joined where this frame first reads the
     // plane -- also for a caller that mixes mifx_chain_execute_sharded frames with phases of its own.
     if (phase == 1 && chain->halo_ssao_pending)
@@ -724,19 +718,15 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
     }
     if (phase == 1)
     {
-        mifx_postfx_render_attribs pa{f->gbuffer.depth, f->prev_depth, f->motion, f->curr_camera, f->prev_camera};
         ctx->need = r.prep;
         MIFX_CHECK(mifx_postfx_execute(ctx, &pa));
-        if (chain->sig_after_prep) MIFX_HIP_CHECK(hipEventRecord(chain->sig_after_prep, ctx->stream)); // (the sharded frame's SSAO lane: SSR on the other lane waits for this)
+        if (req.sig_after_prep) MIFX_HIP_CHECK(hipEventRecord(req.sig_after_prep, ctx->stream)); // (the sharded frame's SSAO lane: SSR on the other lane waits for this)
         ctx->need = r.comp;
-        mifx_ssao_render_attribs sa{ctx, f->gbuffer.depth, f->gbuffer.normal, f->ssao};
-        return mifx_ssao_execute(chain->ssao, &sa);
+        return chain->ssao->run(&sa, req.ssao);
     }
     if (phase == 2)
     {
         ctx->need = r.comp;
-        mifx_ssr_render_attribs sr{ctx, &radiance, f->gbuffer.depth, f->gbuffer.normal, f->gbuffer.material, f->motion, f->ssr};
-        chain->ssr->defer_cleanup = chain->fuse_ssr_cleanup;
         // No exchange of the shaded radiance: the ray march records where every ray hit, and the hit fetch loads the colour from the rows this rank shaded in
         // phase 0 or shades the hit pixel itself (the G-buffer and the IBL maps are whole on every rank; same kernel body, bit-identical colour).
         if (chain->shaded_rows.empty() || chain->shaded_frame != f->frame.Index)
@@ -744,7 +734,8 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
             set_error("mifx_chain_execute_phase: phase 2 of frame %u before its phase 0 (the hit fetch needs the rows that phase shaded)", f->frame.Index);
             return MIFX_ERR_INVALID_OP;
         }
-        chain->ssr->after_trace = [chain, f, ctx, radiance](Img rays, Img coords) -> mifx_status {
+        mifx_ssr::Request ssr_req{chain->fuse_ssr_cleanup, req.hiz_stream, req.hiz_done};
+        ssr_req.after_trace = [chain, f, ctx, radiance](Img rays, Img coords) -> mifx_status {
             MIFX_HIP_CHECK(hipSetDevice(ctx->device));
             MifxKernelTimer timer(ctx, "pbr_hit_fetch_kernel");
             if (chain->has_layers || chain->has_shadows) // the frame was shaded with mifx_chain_set_material_layers: the hit pixels take the same permutation
@@ -757,28 +748,20 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
             return launch_pbr_hit_fetch(ctx->stream, ctx->ibl_apron, &f->gbuffer, *f->curr_camera, *f->pbr, f->ibl, f->background, rays, coords, &radiance, chain->shaded_rows.b,
                                         chain->shaded_rows.e, (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0);
         };
-        chain->ssr->hit_local_rows = chain->shaded_rows; // (R4 loads the colour of a hit in these rows itself; only the others go through the fetch)
-        const mifx_status st_ssr = mifx_ssr_execute(chain->ssr, &sr);
-        chain->ssr->after_trace    = nullptr;
-        chain->ssr->hit_local_rows = Rows{0, 0};
-        MIFX_CHECK(st_ssr);
-        if (chain->wait_before_composite) MIFX_HIP_CHECK(hipStreamWaitEvent(ctx->stream, chain->wait_before_composite, 0)); // (the end of SSAO on its lane)
+        ssr_req.hit_local_rows = chain->shaded_rows; // (R4 loads the colour of a hit in these rows itself; only the others go through the fetch)
+        MIFX_CHECK(chain->ssr->run(&sr, ssr_req));
+        if (req.wait_before_composite) MIFX_HIP_CHECK(hipStreamWaitEvent(ctx->stream, req.wait_before_composite, 0)); // (the end of SSAO on its lane)
+        CompositeHandOver hand;
         MIFX_CHECK(mifx_ssao_get_output(chain->ssao, &ssao_out));
-        MIFX_CHECK(chain_composite(chain, f, &radiance, &spec, &ssao_out, &comp));
+        MIFX_CHECK(chain_composite(chain, f, &radiance, &spec, &ssao_out, &comp, hand));
         ctx->need = r.taa;
-        MIFX_CHECK(chain_taa(chain, f, &comp));
+        MIFX_CHECK(chain_taa(chain, f, &comp, hand));
         MIFX_CHECK(mifx_taa_get_output(chain->taa, 0, &taa_out));
-        if (chain->dof) // DepthOfField::Execute on the TAA output, on the rows Bloom reads of it
-        {
-            ctx->need = r.post;
-            MIFX_CHECK(mifx_dof_prepare(chain->dof, ctx, chain->dof_flags));
-            mifx_dof_render_attribs da{ctx, &taa_out, f->gbuffer.depth, &chain->dof_attribs};
-            MIFX_CHECK(mifx_dof_execute(chain->dof, &da));
-            MIFX_CHECK(mifx_dof_get_output(chain->dof, &taa_out));
-        }
+        ctx->need = r.post; // (depth of field, on the rows Bloom reads of its output)
+        MIFX_CHECK(chain_depth_of_field(chain, f, &taa_out));
         ctx->need = r.need;
         ba.color  = &taa_out;
-        return chain->bloom->run(&ba, 1);
+        return chain->bloom->run(&ba, 1, nullptr, req.bloom);
     }
     mifx_autoexposure* ae = chain->auto_exposure;
     if (phase == 4)
@@ -788,8 +771,7 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
         MIFX_CHECK(launch_autoexposure_reduce(ctx->stream, ae->low_res.view(), static_cast<float*>(ae->average.data), chain->ae_elapsed, chain->ae_adapt ? 1 : 0));
         MIFX_CHECK(mifx_bloom_get_output(chain->bloom, &bloom_out));
         ctx->need = r.band;
-        if (chain->has_grid) return chain_copy_frame_grid(chain, f, &bloom_out, out_ldr);
-        return mifx_tonemap_execute_auto(ctx, &bloom_out, out_ldr, f->tone_mapping, ae, f->tonemap_flags);
+        return chain_copy_frame(chain, f, &bloom_out, out_ldr, nullptr);
     }
     MIFX_CHECK(mifx_taa_get_output(chain->taa, 0, &taa_out));
     if (chain->dof) MIFX_CHECK(mifx_dof_get_output(chain->dof, &taa_out)); // (computed in phase 2)
@@ -797,7 +779,7 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
     ba.color  = &taa_out;
     const bool fuse_tone_map = chain->fuse_tone_map && ae == nullptr && !chain->has_grid;
     const mifx_bloom::FusedToneMap ftm{out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags, chain->fuse_bloom_output};
-    MIFX_CHECK(chain->bloom->run(&ba, 2, fuse_tone_map ? &ftm : nullptr));
+    MIFX_CHECK(chain->bloom->run(&ba, 2, fuse_tone_map ? &ftm : nullptr, req.bloom));
     if (fuse_tone_map) return MIFX_OK;
     MIFX_CHECK(mifx_bloom_get_output(chain->bloom, &bloom_out));
     if (ae)
@@ -805,11 +787,14 @@ extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_ch
         Img  color;
         bool packed = false;
         MIFX_CHECK(to_img_hdr(&bloom_out, "bloom output", color, packed));
-        const Rows rows = mifx_autoexposure::sample_rows(r.band, int(H));
+        const Rows rows = mifx_autoexposure::sample_rows(r.band, int(f->frame.Height));
         return launch_autoexposure_rows(ctx->stream, color, ae->low_res.view(), rows.b, rows.e, packed);
     }
-    if (chain->has_grid) return chain_copy_frame_grid(chain, f, &bloom_out, out_ldr);
-    return mifx_tonemap_execute(ctx, &bloom_out, out_ldr, f->tone_mapping, f->ave_log_lum, f->tonemap_flags);
+    return chain_copy_frame(chain, f, &bloom_out, out_ldr, nullptr); // (no auto exposure here: the grid or the plain tone map)
+}
+extern "C" mifx_status mifx_chain_execute_phase(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, int32_t phase)
+{
+    return mifx::chain_execute_phase(chain, f, out_ldr, phase, mifx::ChainPhaseRequest{});
 }
 
 // What the caller has to move between the phases: planes (valid after the phase that writes them) and row counts.
@@ -818,30 +803,27 @@ extern "C" mifx_status mifx_chain_get_shard_info(mifx_chain* chain, const mifx_c
     MIFX_REQUIRE(chain != nullptr && f != nullptr && out != nullptr && f->bloom && f->ssao && f->ssr, "mifx_chain_get_shard_info: null argument");
     MIFX_REQUIRE(!chain->band.empty() && chain->bloom->prepared, "mifx_chain_get_shard_info: set a row band and run phase 0 first");
     // (a chain whose frames run through mifx_chain_execute_sharded exchanges Bloom's level-0 halos and so needs shorter history halos: report what that frame uses)
-    const bool was = chain->bloom->halo_level0;
-    chain->bloom->halo_level0 = chain->comm != nullptr && mifx::shard_bloom_halo_enabled();
-    *out = mifx::chain_shard_info(chain, f, chain->band);
-    chain->bloom->halo_level0 = was;
+    *out = mifx::chain_shard_info(chain, f, chain->band, chain->comm != nullptr && mifx::shard_bloom_halo_enabled());
     return MIFX_OK;
 }
 
 // Bloom's row plan of any band of the frame (mifx_chain_execute_sharded: which rows of level 0 a rank produces and which it reads, for the halo exchange of that level)
-extern "C++" mifx_bloom::Plan mifx::chain_bloom_plan(const mifx_chain* chain, const mifx_chain_frame* f, Rows band)
+extern "C++" mifx_bloom::Plan mifx::chain_bloom_plan(const mifx_chain* chain, const mifx_chain_frame* f, Rows band, bool halo_level0)
 {
-    const ShardRows r = shard_rows(chain, f, band);
-    return chain->bloom->make_plan(r.band, r.need, chain->bloom->mip_count(*f->bloom));
+    const ShardRows r = shard_rows(chain, f, band, halo_level0);
+    return chain->bloom->make_plan(r.band, r.need, chain->bloom->mip_count(*f->bloom), halo_level0);
 }
 
 // the same for any band of the frame: the rows a rank owning `band` has to receive (mifx_chain_execute_sharded derives every rank's needs from
 // the cuts, so that both sides of an exchange move the same rows without a round of communication)
-extern "C++" mifx_shard_info mifx::chain_shard_info(const mifx_chain* chain, const mifx_chain_frame* f, Rows band)
+extern "C++" mifx_shard_info mifx::chain_shard_info(const mifx_chain* chain, const mifx_chain_frame* f, Rows band, bool halo_level0)
 {
     mifx_shard_info info{};
     mifx_shard_info* out = &info;
     {
     const int H = int(f->frame.Height);
-    const ShardRows r = shard_rows(chain, f, band);
-    const mifx_bloom::Plan p = chain->bloom->make_plan(r.band, r.band, chain->bloom->mip_count(*f->bloom));
+    const ShardRows r = shard_rows(chain, f, band, halo_level0);
+    const mifx_bloom::Plan p = chain->bloom->make_plan(r.band, r.band, chain->bloom->mip_count(*f->bloom), halo_level0);
     const int m = chain->max_motion;
     auto ghost = [&](Rows w) { const int lo = r.band.b - w.b, hi = w.e - r.band.e; return lo > hi ? lo : hi; };
     // rows a pass reads of its history = its row window grown by the reprojection reach and the filter support

@@ -645,20 +645,15 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
     std::vector<Rows> bands(world);
     std::vector<mifx_shard_info> info(world);
     int halos[3] = {0, 0, 0}; // TAA, SSR, SSAO: both neighbours of an edge move the same number of rows = the largest need of any rank
-    // Round 6: Bloom's level 0 with halos (mifx_bloom::halo_level0) -- the row windows of everything in front of Bloom follow from it, so the request is in place before
-    // the needs of the ranks are derived; it ends with the call (HaloLevel0 below).
-    struct HaloLevel0
-    {
-        mifx_bloom* b;
-        ~HaloLevel0() { b->halo_level0 = false; b->after_level0 = nullptr; }
-    } haloLevel0{chain->bloom};
-    chain->bloom->halo_level0 = mifx::shard_bloom_halo_enabled();
+    // Round 6: Bloom's level 0 with halos (mifx_bloom::Request::halo_level0) -- the row windows of everything in front of Bloom follow from it: the needs of the ranks
+    // are derived with it and every phase of the frame is asked for it.
+    const bool halo_level0 = mifx::shard_bloom_halo_enabled();
     std::vector<mifx_bloom::Plan> plans(world);
     if (c)
     {
         for (int r = 0; r < world; ++r) bands[r] = Rows{chain->cuts[r], chain->cuts[r + 1]};
-        for (int r = 0; r < world; ++r) info[r] = chain_shard_info(chain, f, bands[r]);
-        for (int r = 0; r < world; ++r) plans[r] = mifx::chain_bloom_plan(chain, f, bands[r]);
+        for (int r = 0; r < world; ++r) info[r] = chain_shard_info(chain, f, bands[r], halo_level0);
+        for (int r = 0; r < world; ++r) plans[r] = mifx::chain_bloom_plan(chain, f, bands[r], halo_level0);
         for (int r = 0; r < world; ++r)
         {
             MIFX_REQUIRE(info[r].gather_level == info[rank].gather_level, "mifx_chain_execute_sharded: ranks disagree on the Bloom gather level");
@@ -673,9 +668,9 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
     const bool lanes = chain->overlap >= 2 && async && !chain->profiling;
     // Three lanes (chain->overlap >= 3): prep + SSAO (phase 1) on a lane A of their own -- they read the G-buffer and the PostFX planes only -- beside the shade (phase 0) and
     // SSR (the first half of phase 2) on L.  L waits for the prep (SSR's temporal pass reads its planes) before phase 2 and for the end of SSAO in front of the composite
-    // (mifx_chain::sig_after_prep / wait_before_composite); the next frame's A waits for this frame's phase 2 on L, the last reader of what the prep and SSAO overwrite.
+    // (ChainPhaseRequest::sig_after_prep / wait_before_composite); the next frame's A waits for this frame's phase 2 on L, the last reader of what the prep and SSAO overwrite.
     const bool lanes3 = lanes && chain->overlap >= 3;
-    // ... and a stream H for SSR's depth hierarchy (mifx_ssr::hiz_stream): whole-frame streaming work on every rank that depends on the depth buffer alone -- beside the
+    // ... and a stream H for SSR's depth hierarchy (mifx_ssr::Request::hiz_stream): whole-frame streaming work on every rank that depends on the depth buffer alone -- beside the
     // shade instead of between it and the march.  Its last reader is the previous frame's march (phase 2 on L); the march of this frame waits for it inside mifx_ssr_execute.
     hipStream_t L = M; // the stream of phases 0 - 2
     hipStream_t A = M; // the stream of phase 1
@@ -704,7 +699,7 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
             if (Hs) MIFX_HIP_CHECK(hipStreamWaitEvent(Hs, chain->evPrepConsumed, 0));
         }
     }
-    struct Restore // whatever happens, the context's stream is M again and ends behind the lanes, and no event request is left on the chain
+    struct Restore // whatever happens, the context's stream is M again and ends behind the lanes
     {
         mifx_chain* ch;
         hipStream_t m, l, a, h;
@@ -712,8 +707,6 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
         ~Restore()
         {
             ch->ctx->stream = m;
-            ch->sig_after_prep = ch->wait_before_composite = nullptr;
-            if (ch->ssr) { ch->ssr->hiz_stream = nullptr; ch->ssr->hiz_done = nullptr; }
             if (joined) return;
             if (l != m && hipEventRecord(ch->evJoinS, l) == hipSuccess) (void)hipStreamWaitEvent(m, ch->evJoinS, 0);
             if (a != l && hipEventRecord(ch->evJoinX, a) == hipSuccess) (void)hipStreamWaitEvent(m, ch->evJoinX, 0);
@@ -770,11 +763,14 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
 
     // phases 0 and 1: shade, prep, SSAO.  (Until round 3 the band rows of the shaded radiance were all-gathered here -- 465 MB per GPU and frame at 8K / 8 ranks; the
     // ray march now records where it hit and phase 2 loads the colour there or re-shades it: api_chain.cpp.)  mifx_chain_execute_phase joins a pending halo exchange of
-    // the previous frame where the phase first reads the plane.
+    // the previous frame where the phase first reads the plane.  Every phase gets a request of its own (mifx_objects.h ChainPhaseRequest).
+    ChainPhaseRequest plain; // (phases 0, 3 and 4; what phases 1 and 2 start from)
+    plain.bloom.halo_level0 = halo_level0;
     ctx->stream = L;
-    MIFX_CHECK(mifx_chain_execute_phase(chain, f, out_ldr, 0));
+    MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 0, plain));
     ctx->stream = A;
-    if (lanes3) chain->sig_after_prep = chain->evPrep;
+    ChainPhaseRequest q1 = plain;
+    if (lanes3) q1.sig_after_prep = chain->evPrep;
     // Round 6: the last level of SSAO's depth pyramid, which A3's far taps read anywhere, is reduced by the rank that owns its rows and all-gathered (two planes of
     // (H / 16) x (W / 16) texels: 1 MB per frame at 7680x4320) instead of reduced whole on every rank: the row of the last level that holds frame row y belongs to the
     // rank whose band holds its first frame row.  Every rank takes the same decision (it follows from the frame and the SSAO flags alone); MIFX_SHARD_GATHER_SSAO_LEVEL=0
@@ -788,22 +784,17 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
         if (can)
         {
             auto own = [&](Rows band) { return Rows{(band.b + (1 << kLast) - 1) >> kLast, (band.e + (1 << kLast) - 1) >> kLast}; };
-            chain->ssao->gather_last_level = true;
-            chain->ssao->own_last_level    = own(c ? bands[rank] : chain->band);
+            q1.ssao.gather_last_level = true;
+            q1.ssao.own_last_level    = own(c ? bands[rank] : chain->band);
             if (c)
             {
                 std::vector<Rows> owned(world);
                 for (int r = 0; r < world; ++r) owned[r] = own(bands[r]);
-                chain->ssao->after_prefilter = [c, owned](const Plane& d, const Plane& z, hipStream_t s) -> mifx_status { return allgather_rows(c, {&d, &z}, owned, s); };
+                q1.ssao.after_prefilter = [c, owned](const Plane& d, const Plane& z, hipStream_t s) -> mifx_status { return allgather_rows(c, {&d, &z}, owned, s); };
             }
         }
     }
-    const mifx_status p1 = mifx_chain_execute_phase(chain, f, out_ldr, 1);
-    chain->ssao->own_last_level    = Rows{0, 0}; // (per-frame requests: gone whatever the phase returned)
-    chain->ssao->gather_last_level = false;
-    chain->ssao->after_prefilter   = nullptr;
-    MIFX_CHECK(p1);
-    chain->sig_after_prep = nullptr;
+    MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 1, q1));
     if (lanes3) MIFX_HIP_CHECK(hipEventRecord(chain->evSsao, A));
     if (async) MIFX_CHECK(halos_after(A, chain->evAfterP1, chain->evHaloSsao, chain->halo_ssao_pending, {{&chain->ssao->history_ao[ci], halos[2]}, {&chain->ssao->history_len[ci], halos[2]}}));
     ctx->stream = L;
@@ -811,25 +802,26 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
     // phase 2 (behind the previous frame's phase 3, whose Bloom levels and depth-of-field output it overwrites), then the Bloom level every rank needs whole: what each
     // rank owns follows from its band
     if (lanes) MIFX_HIP_CHECK(hipStreamWaitEvent(L, chain->evBloomDone, 0)); // (never recorded = no wait)
+    ChainPhaseRequest q2 = plain;
     if (lanes3)
     {
         MIFX_HIP_CHECK(hipStreamWaitEvent(L, chain->evPrep, 0));
-        chain->wait_before_composite = chain->evSsao;
+        q2.wait_before_composite = chain->evSsao;
         const char* hizLane = std::getenv("MIFX_SHARD_HIZ_LANE"); // (0: the hierarchy stays on L between the shade and the march -- A/B runs)
         if (Hs && (hizLane == nullptr || std::atoi(hizLane) != 0))
         {
-            chain->ssr->hiz_stream = Hs; // (a per-frame request: mifx_ssr_execute takes and clears it)
-            chain->ssr->hiz_done   = chain->evHiz;
+            q2.hiz_stream = Hs;
+            q2.hiz_done   = chain->evHiz;
         }
     }
     // Bloom's level-0 halos: between the prefilter and the first down-sampling (inside phase 2, on this lane) every rank sends the rows of level 0 it owns that another rank
     // reads but does not produce -- the rows beside the band edges -- and receives its own; who reads and who produces what follows from the plans of all ranks.
-    if (c && chain->bloom->halo_level0)
+    if (c && halo_level0)
     {
         bool any = false;
         for (int r = 0; r < world; ++r) any = any || (plans[r].G >= 0 && !(plans[r].compute0.b == plans[r].down[0].b && plans[r].compute0.e == plans[r].down[0].e));
         if (any)
-            chain->bloom->after_level0 = [c, rank, world, &plans](const Plane& level0, hipStream_t s) -> mifx_status {
+            q2.bloom.after_level0 = [c, rank, world, &plans](const Plane& level0, hipStream_t s) -> mifx_status {
                 MIFX_CHECK(c->begin());
                 GroupGuard guard(c);
                 c->time_start(s);
@@ -854,9 +846,7 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
                 return MIFX_OK;
             };
     }
-    MIFX_CHECK(mifx_chain_execute_phase(chain, f, out_ldr, 2));
-    chain->bloom->after_level0 = nullptr;
-    chain->wait_before_composite = nullptr;
+    MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 2, q2));
     if (c && me.gather_level >= 0)
     {
         std::vector<Rows> own(world);
@@ -873,7 +863,7 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
         MIFX_HIP_CHECK(hipStreamWaitEvent(M, chain->evPrepConsumed, 0));
         restore.joined = true;
     }
-    MIFX_CHECK(mifx_chain_execute_phase(chain, f, out_ldr, 3));
+    MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 3, plain));
     if (chain->auto_exposure) // the low-resolution luminance rows of every band, then the reduction and the tone map
     {
         if (c)
@@ -882,7 +872,7 @@ static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_fram
             for (int r = 0; r < world; ++r) lum[r] = Rows{info[r].ae_begin, info[r].ae_end};
             MIFX_CHECK(allgather_rows(c, chain->auto_exposure->low_res, lum, M));
         }
-        MIFX_CHECK(mifx_chain_execute_phase(chain, f, out_ldr, 4));
+        MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 4, plain));
     }
     if (lanes)
     {

@@ -111,10 +111,13 @@ mifx_status mifx_ssr_reset_history(mifx_ssr* fx)
 mifx_status mifx_ssr_execute(mifx_ssr* fx, const mifx_ssr_render_attribs* ra)
 {
     MIFX_REQUIRE(fx != nullptr && ra != nullptr && ra->attribs != nullptr, "mifx_ssr_execute: null argument");
-    const hipStream_t hizStream = fx->hiz_stream; // (a per-frame request: taken and cleared before anything can return)
-    const hipEvent_t  hizDone   = fx->hiz_done;
-    fx->hiz_stream = nullptr;
-    fx->hiz_done   = nullptr;
+    return fx->run(ra, mifx_ssr::Request{});
+}
+
+} // extern "C"
+mifx_status mifx_ssr::run(const mifx_ssr_render_attribs* ra, const Request& req)
+{
+    mifx_ssr* const fx = this;
     mifx_postfx* ctx = ra->postfx ? ra->postfx : fx->ctx;
     if (!fx->prepared || !ctx || !ctx->executed)
     {
@@ -159,11 +162,11 @@ mifx_status mifx_ssr_execute(mifx_ssr* fx, const mifx_ssr_render_attribs* ra)
     const bool   direct0    = (fx->direct_level0 > 0 || (fx->direct_level0 < 0 && !ctx->band.empty())) && depthBytes < (size_t(1) << 31) && depth.pitch < (1 << 24) && depth.w < (1 << 24) &&
                               depth.h < (1 << 24);
     const Img level0Copy = direct0 ? Img{} : fx->hiz[0].view();
-    if (hizStream != nullptr && hizDone != nullptr)
+    if (req.hiz_stream != nullptr && req.hiz_done != nullptr)
     {
-        MIFX_CHECK(launch_ssr_hiz_pyramid(hizStream, hiz, level0Copy, rev));
-        MIFX_HIP_CHECK(hipEventRecord(hizDone, hizStream));
-        MIFX_HIP_CHECK(hipStreamWaitEvent(s, hizDone, 0));
+        MIFX_CHECK(launch_ssr_hiz_pyramid(req.hiz_stream, hiz, level0Copy, rev));
+        MIFX_HIP_CHECK(hipEventRecord(req.hiz_done, req.hiz_stream));
+        MIFX_HIP_CHECK(hipStreamWaitEvent(s, req.hiz_done, 0));
     }
     else
         MIFX_CHECK(launch_ssr_hiz_pyramid(s, hiz, level0Copy, rev));
@@ -209,22 +212,16 @@ mifx_status mifx_ssr_execute(mifx_ssr* fx, const mifx_ssr_render_attribs* ra)
     {
         MifxKernelTimer timer(ctx, "ssr_intersection_kernel");
         Img coords{};
-        if (fx->after_trace)
+        if (req.after_trace)
         {
             MIFX_CHECK(fx->hit_coords.alloc(fx->ray_radiance.w, fx->ray_radiance.h, MIFX_FORMAT_F32));
             coords = fx->hit_coords.view();
         }
         MIFX_CHECK(launch_ssr_intersection(s, color, normal, fx->roughness.view(), ctx->noise_xy.view(), slab, half ? fx->mask_half.view() : fx->mask.view(), motion,
                                            win(fx->ray_radiance.view(), half ? h4 : w4), fx->ray_dir_pdf.view(), cur, a,
-                                           (fx->flags & MIFX_SSR_FEATURE_FLAG_PREVIOUS_FRAME) != 0, half, coords, fx->hit_local_rows.b, fx->hit_local_rows.e));
+                                           (fx->flags & MIFX_SSR_FEATURE_FLAG_PREVIOUS_FRAME) != 0, half, coords, req.hit_local_rows.b, req.hit_local_rows.e));
     }
-    if (fx->after_trace)
-    {
-        auto hook = std::move(fx->after_trace);
-        fx->after_trace    = nullptr;
-        fx->hit_local_rows = Rows{0, 0};
-        MIFX_CHECK(hook(win(fx->ray_radiance.view(), half ? h4 : w4), fx->hit_coords.view()));
-    }
+    if (req.after_trace) MIFX_CHECK(req.after_trace(win(fx->ray_radiance.view(), half ? h4 : w4), fx->hit_coords.view()));
     // R5
     {
         MifxKernelTimer timer(ctx, "ssr_spatial_kernel");
@@ -238,19 +235,16 @@ mifx_status mifx_ssr_execute(mifx_ssr* fx, const mifx_ssr_render_attribs* ra)
                                        fx->hist_radiance[pi].view(), fx->hist_variance[pi].view(), fx->mask.view(), win(fx->hist_radiance[ci].view(), w6), fx->hist_variance[ci].view(), cur,
                                        prev, a));
     }
-    // R7 (now, or inside the chain's composite: mifx_objects.h `defer_cleanup`)
+    // R7 (now, or inside the chain's composite: mifx_objects.h Request::defer_cleanup)
     fx->cleanup_in     = SsrCleanupIn{depth, fx->roughness.view(), fx->hist_radiance[ci].view(), fx->hist_variance[ci].view(), fx->mask.view(), a.RoughnessThreshold,
                                       a.BilateralCleanupSpatialSigmaFactor, a.AlphaInterpolation, rev ? 1 : 0};
     fx->cleanup_normal = normal;
     fx->cleanup_cam    = cur;
     fx->cleanup_rows   = w7;
     fx->cleanup_pending = true;
-    if (!fx->defer_cleanup) MIFX_CHECK(fx->run_cleanup());
-    fx->defer_cleanup = false; // (a per-frame request)
-    return MIFX_OK;
+    return req.defer_cleanup ? MIFX_OK : fx->run_cleanup();
 }
 
-} // extern "C"
 mifx_status mifx_ssr::run_cleanup()
 {
     if (!cleanup_pending) return MIFX_OK;

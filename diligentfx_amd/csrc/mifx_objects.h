@@ -119,14 +119,17 @@ struct mifx_ssao
     bool         force_reset = true;
 
     static constexpr int kMips = 5;            // SSAO_DEPTH_PREFILTERED_MAX_MIP + 1
-    // Round 6, per-frame requests of a sharded frame (api_comm.cpp; cleared by the execute that takes them).  A2's last level is read anywhere (A3's far taps), so until
-    // round 5 every rank reduced the WHOLE depth pyramid -- 46 us of a 1.15 ms band at 7680x4320 / 8 ranks.  With `own_last_level` = the rows of the last level this rank
-    // owns (non-empty), A2 reduces only the source rows its own store windows and those rows need, and `after_prefilter` -- the all-gather of the last level's depth and
-    // camera-z planes, 1 MB per frame in total at that size -- runs between A2 and A3.  Without the hook (mifx_chain_execute_band: the compute side alone) the rows of
-    // other ranks stay stale.
-    bool       gather_last_level = false; // the request itself (a thin band may own no row of the last level: own_last_level is then empty)
-    mifx::Rows own_last_level{0, 0};
-    std::function<mifx_status(const mifx::Plane& depthLast, const mifx::Plane& camzLast, hipStream_t s)> after_prefilter;
+    // What one execute of a sharded frame asks for (api_comm.cpp).  A2's last level is read anywhere (A3's far taps), so until round 5 every rank reduced the WHOLE depth
+    // pyramid -- 46 us of a 1.15 ms band at 7680x4320 / 8 ranks.  With `own_last_level` = the rows of the last level this rank owns, A2 reduces only the source rows its
+    // own store windows and those rows need, and `after_prefilter` -- the all-gather of the last level's depth and camera-z planes, 1 MB per frame in total at that size --
+    // runs between A2 and A3.  Without the hook (mifx_chain_execute_band: the compute side alone) the rows of other ranks stay stale.
+    struct Request
+    {
+        bool       gather_last_level = false; // the request itself (a thin band may own no row of the last level: own_last_level is then empty)
+        mifx::Rows own_last_level{0, 0};
+        std::function<mifx_status(const mifx::Plane& depthLast, const mifx::Plane& camzLast, hipStream_t s)> after_prefilter;
+    };
+    mifx_status run(const mifx_ssao_render_attribs* ra, const Request& req); // mifx_ssao_execute = run with an empty request
     // Row-band sharding: A5's / A6's row window starts and ends on a multiple of this many rows -- one row of A6's last level, what the fused pyramid kernel needs
     // (mifx_pyramid.h first_row(); 32 until round 5, when a launch had to start on one of its own 16-row blocks of level 1)
     static constexpr int kWindowAlign = 1 << (kMips - 1);
@@ -161,15 +164,23 @@ struct mifx_ssr
     uint32_t     last_frame = ~0u;
 
     static constexpr int kMips = 7; // SSR_DEPTH_HIERARCHY_MAX_MIP + 1
-    // Row-band sharding without a radiance exchange (api_chain.cpp, phase 2): R4 records where every ray hit (hit_coords: x | y << 16 per ray texel) instead of
-    // loading the colour there, and `after_trace` -- the chain's hit fetch (launch_pbr_hit_fetch) -- runs between R4 and R5.  Both are per-frame requests.
+    // What one execute is asked for beyond the render attribs (the chain: api_chain.cpp).
+    struct Request
+    {
+        // R7 deferred (the chain's composite evaluates the cleanup per pixel instead of reading `output`, mifx_ssr_cleanup.h): the execute stops after R6 and keeps what
+        // the pass needs (cleanup_pending below)
+        bool defer_cleanup = false;
+        // R1 on another stream (the chain's lanes, mifx_chain_set_overlap 3): the depth hierarchy depends on the depth buffer only; it is recorded on `hiz_stream`,
+        // `hiz_done` is recorded behind it and the effect's own stream waits for that event before R2 / R4.
+        hipStream_t hiz_stream = nullptr;
+        hipEvent_t  hiz_done   = nullptr;
+        // Row-band sharding without a radiance exchange (api_chain.cpp, phase 2): R4 records where every ray hit (hit_coords: x | y << 16 per ray texel) instead of
+        // loading the colour there, and `after_trace` -- the chain's hit fetch (launch_pbr_hit_fetch) -- runs between R4 and R5.
+        std::function<mifx_status(mifx::Img rays, mifx::Img coords)> after_trace;
+        mifx::Rows hit_local_rows{0, 0}; // with after_trace: the rows of the colour buffer that are valid on this rank -- R4 loads hits there itself and records only the others
+    };
+    mifx_status run(const mifx_ssr_render_attribs* ra, const Request& req); // mifx_ssr_execute = run with an empty request
     mifx::Plane hit_coords;
-    std::function<mifx_status(mifx::Img rays, mifx::Img coords)> after_trace;
-    mifx::Rows  hit_local_rows{0, 0}; // with after_trace: the rows of the colour buffer that are valid on this rank -- R4 loads hits there itself and records only the others
-    // R1 on another stream (per-frame request of the chain's lanes mode, mifx_chain_set_overlap 3): the depth hierarchy depends on the depth buffer only; it is
-    // recorded on `hiz_stream`, `hiz_done` is recorded behind it and the effect's own stream waits for that event before R2 / R4.
-    hipStream_t hiz_stream = nullptr;
-    hipEvent_t  hiz_done   = nullptr;
     int         direct_level0 = -1; // the march reads level 0 from the caller's depth plane instead of a copy: -1 = in row-band frames only, 0 = never, 1 = always (api_ssr.cpp)
     mifx::Plane hiz[kMips];         // R1: views into hiz_slab (level 0 = copy of the depth)
     mifx::DeviceScratch hiz_slab;
@@ -195,9 +206,7 @@ struct mifx_ssr
     mifx::Plane res_radiance, res_variance, res_depth;     // R5
     mifx::Plane hist_radiance[2], hist_variance[2];        // R6 ping-pong
     mifx::Plane output;                                    // R7
-    // R7 deferred (the chain's composite evaluates the cleanup per pixel instead of reading `output`, mifx_ssr_cleanup.h): mifx_ssr_execute then stops after R6 and
-    // keeps what the pass needs; mifx_ssr_get_output runs it on demand (tests, tools), so the plane is still there for whoever asks.
-    bool               defer_cleanup   = false; // set by the chain before execute (per frame)
+    // R7 deferred (Request::defer_cleanup): what the pass needs, kept so that mifx_ssr_run_deferred_cleanup can still produce the plane for whoever asks (tests, tools)
     bool               cleanup_pending = false;
     mifx::SsrCleanupIn cleanup_in{};
     mifx::Img          cleanup_normal{};
@@ -219,10 +228,10 @@ struct mifx_taa
     // reference's host code (oracle/refhost, round 4); bit `flags` of techniques_created = that flag set has been executed once.
     uint32_t     techniques_created = 0;
     bool         technique_ready    = false; // of this frame's flag set, as of mifx_taa_prepare
-    // Per-frame request of the chain (MIFX_CHAIN_FUSE_COMPOSITE_INTO_TAA): the colour to accumulate is the chain's composite, which the kernel evaluates itself for its
-    // colour tile (taa.hip) -- `color` of the render attribs is then not read.  Taken and cleared by mifx_taa_execute; never combined with the placeholder frame (the
-    // chain asks technique_ready first).
-    const mifx::TaaFusedComposite* fused_composite = nullptr;
+    // mifx_taa_execute = run without `fused`.  With it (the chain, MIFX_CHAIN_FUSE_COMPOSITE_INTO_TAA) the colour to accumulate is the chain's composite, which the kernel
+    // evaluates itself for its colour tile (taa.hip) -- `color` of the render attribs is then not read.  Never combined with the placeholder frame (the chain asks
+    // technique_ready first).
+    mifx_status run(const mifx_taa_render_attribs* ra, const mifx::TaaFusedComposite* fused);
 };
 
 struct mifx_bloom
@@ -248,14 +257,17 @@ struct mifx_bloom
         mifx::Rows compute0{0, 0};   // rows of level 0 the prefilter of THIS rank produces: down[0], or -- halo_level0 -- the rows it owns (own0); the others arrive
         mifx::Rows own0{0, 0};       // rows of level 0 whose first full-resolution row lies in the band (a partition of the level over the ranks)
     };
-    // Round 6, a request of mifx_chain_execute_sharded (api_comm.cpp) for the duration of a frame.  Bloom's level 0 (half resolution) feeds two consumers beyond a band's
-    // own rows: the rows of level 1 the rank owns (+-4 level-0 rows) and the up-sampling of its band (+-3).  Until round 5 every rank produced those rows itself, which
-    // made the TAA output -- and with it the shade, SSR, SSAO, the composite -- 13 rows taller than the band on each side.  With halo_level0 a rank prefilters the level-0
-    // rows it owns (TAA window: band +- 4) and the ranks exchange the few rows beside the band edges (`after_level0`: 245 KB per neighbour at 7680x4320) between the prefilter
-    // and the first down-sampling.  Off for a caller that drives the phases itself (mifx_chain_execute_phase: no hook, no new exchange to know about).
-    bool halo_level0 = false;
-    std::function<mifx_status(const mifx::Plane& level0, hipStream_t s)> after_level0;
-    Plan make_plan(mifx::Rows band, mifx::Rows need, int mipCount) const;
+    // What mifx_chain_execute_sharded (api_comm.cpp) asks of the runs of a frame.  Bloom's level 0 (half resolution) feeds two consumers beyond a band's own rows: the rows
+    // of level 1 the rank owns (+-4 level-0 rows) and the up-sampling of its band (+-3).  Until round 5 every rank produced those rows itself, which made the TAA output --
+    // and with it the shade, SSR, SSAO, the composite -- 13 rows taller than the band on each side.  With halo_level0 a rank prefilters the level-0 rows it owns (TAA
+    // window: band +- 4) and the ranks exchange the few rows beside the band edges (`after_level0`: 245 KB per neighbour at 7680x4320) between the prefilter and the first
+    // down-sampling.  Off for a caller that drives the phases itself (mifx_chain_execute_phase: no hook, no new exchange to know about).
+    struct Request
+    {
+        bool halo_level0 = false;
+        std::function<mifx_status(const mifx::Plane& level0, hipStream_t s)> after_level0;
+    };
+    Plan make_plan(mifx::Rows band, mifx::Rows need, int mipCount, bool halo_level0) const;
     int  mip_count(const mifx_bloom_attribs& a) const;
     // the chain's copy-frame pass fused into the final up-sample (launch_bloom_final_tonemap): the LDR target and the ToneMap() arguments
     struct FusedToneMap
@@ -274,7 +286,7 @@ struct mifx_bloom
     mifx_bloom_attribs deferred_attribs{};
     mifx::Rows         deferred_rows{0, 0};
     mifx_status        run_deferred_output();
-    mifx_status run(const mifx_bloom_render_attribs* ra, int phase, const FusedToneMap* tone_map = nullptr); // 0: everything, 1: up to the gather, 2: after the gather
+    mifx_status run(const mifx_bloom_render_attribs* ra, int phase, const FusedToneMap* tone_map, const Request& req); // 0: everything, 1: up to the gather, 2: after the gather
 };
 
 struct mifx_dof // == DepthOfField (PostProcess/DepthOfField/src/DepthOfField.cpp)
@@ -400,8 +412,6 @@ struct mifx_chain
     bool         fuse_bloom_output = true; // the Bloom output plane is not written when the tone map is fused into the final up-sample (produced on demand)
     bool         fuse_composite_taa = false; // the composite (with R7 inside) evaluated by the TAA kernel for its colour tile: the composite plane is neither written nor read (taa.hip).
                                             // OFF by default: measured 85 us SLOWER per 4K frame than the two passes (profiles/r05_ab_composite_into_taa.txt)
-    mifx_composite_attribs  pending_composite{};        // ... what chain_composite would have launched, kept for the TAA call of the same frame
-    mifx::TaaFusedComposite pending_fused{nullptr, nullptr};
     bool         fuse_ssr_mask = true; // R2 (roughness + reflection mask of SSR) written by the shade kernel, which reads the same material / depth texels
     int          overlap = 0; // opt-in (mifx_chain_set_overlap): 1 = prep + SSAO beside shade + SSR, 2 = and across frames, 3 = three lanes across frames, 4 = three lanes, two frames in flight, 5 = 4 with the composite / TAA / depth of field on the Bloom lane; per-kernel durations then overlap and lose their roofline meaning
     bool         prep_consumed = false; // evPrepConsumed was recorded by the previous frame
@@ -447,10 +457,7 @@ struct mifx_chain
     hipEvent_t  evAfterP1 = nullptr, evAfterP2 = nullptr, evHaloSsao = nullptr, evHaloRest = nullptr;
     bool        halo_ssao_pending = false, halo_rest_pending = false;
     // mifx_chain_execute_sharded with mifx_chain_set_overlap 3: prep + SSAO (phase 1) run on a lane of their own beside the shade (phase 0) and SSR (the first half of
-    // phase 2).  Phase 1 records `sig_after_prep` behind the PostFX prep, phase 2 waits for `wait_before_composite` (the end of SSAO) in front of the composite; both are
-    // set for the duration of one call by execute_sharded_impl (api_comm.cpp) and null otherwise.
-    hipEvent_t  sig_after_prep = nullptr, wait_before_composite = nullptr;
-    // ... and SSR's depth hierarchy, whole-frame streaming work that depends on the depth buffer alone, on a fourth stream beside the shade (mifx_ssr::hiz_stream)
+    // phase 2; the two events between the lanes travel in mifx::ChainPhaseRequest below), and SSR's depth hierarchy, whole-frame streaming work that depends on the depth buffer alone, on a fourth stream beside the shade (mifx_ssr::Request::hiz_stream)
     hipStream_t lane_h = nullptr;
     hipEvent_t  evHiz = nullptr, evJoinH = nullptr;
     void        join_halos(); // the context's stream waits for both exchanges (before anything that is not a frame of this chain touches the history planes)
@@ -459,10 +466,22 @@ struct mifx_chain
 
 namespace mifx
 {
-// what a rank owning the rows `band` of the frame has to receive between the phases (api_chain.cpp); mifx_chain_get_shard_info = this for the chain's own band
-mifx_shard_info chain_shard_info(const mifx_chain* chain, const mifx_chain_frame* f, Rows band);
-mifx_bloom::Plan chain_bloom_plan(const mifx_chain* chain, const mifx_chain_frame* f, Rows band);
+// what a rank owning the rows `band` of the frame has to receive between the phases (api_chain.cpp); mifx_chain_get_shard_info = this for the chain's own band.
+// halo_level0: of a frame whose Bloom runs with mifx_bloom::Request::halo_level0
+mifx_shard_info chain_shard_info(const mifx_chain* chain, const mifx_chain_frame* f, Rows band, bool halo_level0);
+mifx_bloom::Plan chain_bloom_plan(const mifx_chain* chain, const mifx_chain_frame* f, Rows band, bool halo_level0);
 bool            shard_bloom_halo_enabled();
+// What execute_sharded_impl (api_comm.cpp) asks of one phase; mifx_chain_execute_phase = chain_execute_phase with an empty request.
+struct ChainPhaseRequest
+{
+    hipEvent_t         sig_after_prep        = nullptr; // phase 1 records it behind the PostFX prep (SSR on the other lane waits for it)
+    hipEvent_t         wait_before_composite = nullptr; // phase 2 waits for it in front of the composite (the end of SSAO on its lane)
+    hipStream_t        hiz_stream            = nullptr; // phase 2: mifx_ssr::Request
+    hipEvent_t         hiz_done              = nullptr;
+    mifx_ssao::Request ssao;                            // phase 1
+    mifx_bloom::Request bloom;                          // halo_level0: the row windows of every phase follow from it; after_level0: phase 2
+};
+mifx_status chain_execute_phase(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, int32_t phase, const ChainPhaseRequest& req);
 // HnPostProcessTask::Prepare: the per-frame PrepareResources of every effect and the chain's own planes (idempotent for an unchanged frame description)
 mifx_status chain_prepare_resources(mifx_chain* chain, const mifx_chain_frame* f);
 // the chain's extra streams and their events, created on first use; whether this frame's lanes may start behind the previous frame's events alone (api_chain.cpp)
