@@ -308,18 +308,23 @@ static FrameAttribs chain_frame_attribs(mifx_postfx* ctx, const mifx_chain_frame
 }
 
 // Creates the chain's extra streams and events on first use.
-extern "C++" mifx_status mifx::chain_make_lanes(mifx_chain* chain, bool three)
+extern "C++" mifx_status mifx::chain_make_lanes(mifx_chain* chain, int lanes)
 {
     if (!chain->side)
     {
         // (a stream priority for the second stream was measured: lowest 1.713-1.723 ms, highest 1.728-1.736 ms, default 1.701-1.703 ms per 4K frame in mode 2)
         MIFX_HIP_CHECK(hipStreamCreateWithFlags(&chain->side, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&chain->evFork, &chain->evPrep, &chain->evSsao, &chain->evPrepConsumed}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (hipEvent_t* e : {&chain->evFork, &chain->evPrep, &chain->evSsao, &chain->evPrepConsumed, &chain->evJoinS}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-    if (three && !chain->lane_x)
+    if (lanes >= 3 && !chain->lane_x)
     {
         MIFX_HIP_CHECK(hipStreamCreateWithFlags(&chain->lane_x, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&chain->evBloomDone, &chain->evJoinS, &chain->evJoinX, &chain->evXEnd[0], &chain->evXEnd[1], &chain->evSsrDone}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (hipEvent_t* e : {&chain->evBloomDone, &chain->evJoinX, &chain->evXEnd[0], &chain->evXEnd[1], &chain->evSsrDone}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    if (lanes >= 4 && !chain->lane_h)
+    {
+        MIFX_HIP_CHECK(hipStreamCreateWithFlags(&chain->lane_h, hipStreamNonBlocking));
+        for (hipEvent_t* e : {&chain->evHiz, &chain->evJoinH}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     return MIFX_OK;
 }
@@ -327,11 +332,19 @@ extern "C++" mifx_status mifx::chain_make_lanes(mifx_chain* chain, bool three)
 // Whether the lanes of this frame may start behind the previous frame's events alone: the previous frame recorded them, and the library queued nothing on the context
 // stream since (history fills of a reset or of a re-allocating prepare, history imports, a new stream: mifx_postfx::stream_epoch).  Otherwise every lane is ordered
 // behind the context stream once.
-extern "C++" bool mifx::chain_lanes_continue(mifx_chain* chain)
+static bool chain_lanes_continue(mifx_chain* chain)
 {
     const bool cont = chain->prep_consumed && chain->seen_epoch == chain->ctx->stream_epoch;
     chain->prep_consumed = false; // (set again by a frame that got as far as recording the event: an error return leaves it off)
     return cont;
+}
+extern "C++" mifx_status mifx::chain_fork_lanes(mifx_chain* chain, std::initializer_list<LaneEvent> lanes, bool across_frames)
+{
+    const bool cont = chain_lanes_continue(chain) && across_frames; // (in this order: a frame that may not continue clears prep_consumed as well)
+    if (!cont) MIFX_HIP_CHECK(hipEventRecord(chain->evFork, chain->ctx->stream));
+    for (const LaneEvent& l : lanes)
+        if (l.lane != nullptr && (!cont || l.ev != nullptr)) MIFX_HIP_CHECK(hipStreamWaitEvent(l.lane, cont ? l.ev : chain->evFork, 0));
+    return MIFX_OK;
 }
 
 // mifx_chain_set_overlap 3: one frame as three lanes that slide against each other across frames.  The frame's kernels fall into three resource classes --
@@ -426,7 +439,7 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
     mifx_postfx*      ctx = chain->ctx;
     const hipStream_t M   = ctx->stream;
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
-    MIFX_CHECK(chain_make_lanes(chain, true));
+    MIFX_CHECK(chain_make_lanes(chain, 3));
     const hipStream_t S = chain->side, X = chain->lane_x;
     if (pipelined)
     {
@@ -434,33 +447,11 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
         chain_swap_shadow(chain); // this frame's set = the one the frame before the previous frame used
     }
     const mifx_image2d radiance = chain->radiance.desc(), spec = chain->specular_ibl.desc(), comp = chain->composite.desc();
-    struct Rejoin // whatever happens, the context stream ends behind both lanes and is the context's stream again
-    {
-        mifx_chain* c;
-        hipStream_t m;
-        bool        done = false;
-        ~Rejoin()
-        {
-            c->ctx->stream      = m;
-            c->ctx->kernel_hook = nullptr;
-            if (done) return; // (the regular path joined through evSsao -> evPrepConsumed)
-            if (hipEventRecord(c->evJoinS, c->side) == hipSuccess) (void)hipStreamWaitEvent(m, c->evJoinS, 0);
-            if (hipEventRecord(c->evJoinX, c->lane_x) == hipSuccess) (void)hipStreamWaitEvent(m, c->evJoinX, 0);
-        }
-    } rejoin{chain, M};
+    LaneJoin join{chain, M, {S, chain->evJoinS}, {X, chain->evJoinX}}; // (the regular path joins through evSsao -> evPrepConsumed)
     const uint64_t k = chain->seq;
-    if (chain_lanes_continue(chain))
-    {
-        // lane S behind the last reader of what it overwrites: the end of lane X of the previous frame -- or, two frames in flight, of the frame before that one
-        const bool deep = pipelined && k >= 2 && f->frame.Index == chain->last_index + 1u;
-        MIFX_HIP_CHECK(hipStreamWaitEvent(S, deep ? chain->evXEnd[k & 1u] : chain->evPrepConsumed, 0)); // (evXEnd[k & 1] still holds frame k - 2's record)
-    }
-    else
-    {
-        MIFX_HIP_CHECK(hipEventRecord(chain->evFork, M));
-        MIFX_HIP_CHECK(hipStreamWaitEvent(S, chain->evFork, 0));
-        MIFX_HIP_CHECK(hipStreamWaitEvent(X, chain->evFork, 0));
-    }
+    // lane S continues behind the last reader of what it overwrites: the end of lane X of the previous frame -- or, two frames in flight, of the frame before that one
+    const bool deep = pipelined && k >= 2 && f->frame.Index == chain->last_index + 1u;
+    MIFX_CHECK(chain_fork_lanes(chain, {{S, deep ? chain->evXEnd[k & 1u] : chain->evPrepConsumed}, {X, nullptr}})); // (evXEnd[k & 1] still holds frame k - 2's record)
     if (pipelined && !chain->edges.empty()) ctx->kernel_hook = [chain](const char* name, bool begin) { chain_kernel_hook(chain, name, begin); };
     const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
     // lane S: shade, prep
@@ -501,7 +492,7 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
     // lane M: Bloom, tone map
     ctx->stream = M;
     if (!late) MIFX_HIP_CHECK(hipStreamWaitEvent(M, chain->evPrepConsumed, 0));
-    rejoin.done = true;
+    join.joined = true;
     MIFX_CHECK(chain_bloom_and_tone_map(chain, f, taa_out, out_ldr, out_native, nullptr));
     MIFX_HIP_CHECK(hipEventRecord(chain->evBloomDone, M));
     chain->seen_epoch    = ctx->stream_epoch;
@@ -529,12 +520,15 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
     MIFX_CHECK(mark());
 
     const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
-    if (chain->overlap && !chain->profiling)
+    const bool        two  = chain->overlap && !chain->profiling;
+    const hipStream_t main = ctx->stream;
+    if (two) MIFX_CHECK(chain_make_lanes(chain, 2));
+    // (the regular path joins through evPrep / evSsao; it says so in front of Bloom, as the three lanes do: an error return after the fork leaves `main` behind the side stream)
+    LaneJoin join{chain, main, {two ? chain->side : nullptr, chain->evJoinS}};
+    if (two)
     {
         // Two dependency chains:  shade -> SSR (needs the radiance and the prep outputs)   |   prep -> SSAO (depth / normals only).
         // The second one is recorded on the side stream; the launch stream joins before the composite.  Same kernels, same results.
-        hipStream_t main = ctx->stream;
-        MIFX_CHECK(chain_make_lanes(chain, false));
         // Across frames (overlap 2; the caller guarantees that the frame's input planes are complete when execute is called): the side stream does not wait for the
         // previous frame's Bloom and tone map, only for its last reader of what prep and SSAO overwrite (the PostFX planes and the blue noise: SSR, TAA, depth of field),
         // so that the next frame's prep + SSAO fill the GPU under the small launches of the Bloom pyramid.
@@ -543,19 +537,13 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
         //  1.706 / 1.720 vs 1.708 / 1.704 ms.  The gain of running two kernels at once saturates at ~5.6 %, which is also what two whole chains on two streams reach
         //  (tools/exp_two_chains.py).  tools/overlap_stats.py shows what runs beside what: profiles/r03_overlap_stats.txt.)
         // (only while nothing else was queued on the context stream in between -- a reset's or a re-allocating prepare's history fills, an import: chain_lanes_continue)
-        if (chain_lanes_continue(chain) && chain->overlap >= 2) MIFX_HIP_CHECK(hipStreamWaitEvent(chain->side, chain->evPrepConsumed, 0));
-        else
-        {
-            MIFX_HIP_CHECK(hipEventRecord(chain->evFork, main));
-            MIFX_HIP_CHECK(hipStreamWaitEvent(chain->side, chain->evFork, 0));
-        }
+        MIFX_CHECK(chain_fork_lanes(chain, {{chain->side, chain->evPrepConsumed}}, chain->overlap >= 2));
         ctx->stream = chain->side;
-        mifx_status st = mifx_postfx_execute(ctx, &pa);
-        if (st >= 0) st = hipEventRecord(chain->evPrep, chain->side) == hipSuccess ? MIFX_OK : MIFX_ERR_HIP;
-        if (st >= 0) st = mifx_ssao_execute(chain->ssao, &sa);
-        if (st >= 0) st = hipEventRecord(chain->evSsao, chain->side) == hipSuccess ? MIFX_OK : MIFX_ERR_HIP;
+        MIFX_CHECK(mifx_postfx_execute(ctx, &pa));
+        MIFX_HIP_CHECK(hipEventRecord(chain->evPrep, chain->side));
+        MIFX_CHECK(mifx_ssao_execute(chain->ssao, &sa));
+        MIFX_HIP_CHECK(hipEventRecord(chain->evSsao, chain->side));
         ctx->stream = main;
-        MIFX_CHECK(st);
         MIFX_CHECK(chain_shade(chain, f, &radiance, &spec)); // (measured: the shade on the side stream as well, in front of prep, changes nothing: 1.747 vs 1.751 ms)
         MIFX_HIP_CHECK(hipStreamWaitEvent(main, chain->evPrep, 0));
         MIFX_CHECK(chain->ssr->run(&sr, mifx_ssr::Request{chain->fuse_ssr_cleanup}));
@@ -596,6 +584,7 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
         chain->prep_consumed = true;
     }
     MIFX_CHECK(mark());
+    join.joined = true;
     MIFX_CHECK(chain_bloom_and_tone_map(chain, f, taa_out, out_ldr, out_native, chain->profiling ? chain->ev[stage] : nullptr)); // (the stage mark between the two)
     ++stage;
     MIFX_CHECK(mark());
@@ -818,9 +807,7 @@ extern "C++" mifx_bloom::Plan mifx::chain_bloom_plan(const mifx_chain* chain, co
 // the cuts, so that both sides of an exchange move the same rows without a round of communication)
 extern "C++" mifx_shard_info mifx::chain_shard_info(const mifx_chain* chain, const mifx_chain_frame* f, Rows band, bool halo_level0)
 {
-    mifx_shard_info info{};
-    mifx_shard_info* out = &info;
-    {
+    mifx_shard_info out{};
     const int H = int(f->frame.Height);
     const ShardRows r = shard_rows(chain, f, band, halo_level0);
     const mifx_bloom::Plan p = chain->bloom->make_plan(r.band, r.band, chain->bloom->mip_count(*f->bloom), halo_level0);
@@ -831,16 +818,15 @@ extern "C++" mifx_shard_info mifx::chain_shard_info(const mifx_chain* chain, con
                              f->frame.Height % 16u == 0u && !(chain->ssao_flags & MIFX_SSAO_FEATURE_FLAG_HALF_RESOLUTION); // as in mifx_ssao_execute
     const Rows ssao5 = rows_align(rows_expand(rows_expand(r.comp, int(std::ceil(f->ssao->SpatialReconstructionRadius)) + 1, H), centredTaps ? 24 : 48, H), mifx_ssao::kWindowAlign, H);
     const Rows ssr6  = rows_expand(r.comp, 3, H);
-    out->band_begin = r.band.b; out->band_end = r.band.e;
-    out->halo_taa   = ghost(r.taa) + m + 3;   // Catmull-Rom history taps: +-2 texels around the reprojected position
-    out->halo_ssr   = ghost(ssr6) + 2 * m + 2; // incident and hit-point reprojection, bilinear
-    out->halo_ssao  = ghost(ssao5) + m + 2;
-    out->gather_level = p.G;
-    out->own_begin = p.own.b; out->own_end = p.own.e;
+    out.band_begin = r.band.b; out.band_end = r.band.e;
+    out.halo_taa   = ghost(r.taa) + m + 3;   // Catmull-Rom history taps: +-2 texels around the reprojected position
+    out.halo_ssr   = ghost(ssr6) + 2 * m + 2; // incident and hit-point reprojection, bilinear
+    out.halo_ssao  = ghost(ssao5) + m + 2;
+    out.gather_level = p.G;
+    out.own_begin = p.own.b; out.own_end = p.own.e;
     const Rows ae = chain->auto_exposure ? mifx_autoexposure::sample_rows(r.band, H) : Rows{0, 0};
-    out->ae_begin = ae.b; out->ae_end = ae.e;
-    }
-    return info;
+    out.ae_begin = ae.b; out.ae_end = ae.e;
+    return out;
 }
 
 extern "C" mifx_status mifx_chain_get_shard_plane(mifx_chain* chain, const char* name, mifx_image2d* out)

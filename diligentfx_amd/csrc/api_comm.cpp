@@ -360,29 +360,42 @@ struct GroupGuard
     GroupGuard(const GroupGuard&) = delete;
     GroupGuard& operator=(const GroupGuard&) = delete;
 };
-// rows [b, e) of a pitched plane: one contiguous slab
-inline unsigned char* row_ptr(const Plane& p, int row) { return static_cast<unsigned char*>(p.data) + size_t(row) * p.pitch; }
-inline size_t         row_bytes(const Plane& p, int b, int e) { return e > b ? size_t(e - b) * p.pitch : 0; }
-
-// every rank's rows [b_r, e_r) of every plane of `planes` (planes of one height) go to every other rank: an all-gather of uneven row slabs as direct sends, one group
-mifx_status allgather_rows(mifx_comm* c, std::initializer_list<const Plane*> planes, const std::vector<Rows>& rows, hipStream_t s)
+// One exchange group on stream `s`: begin, the time bracket, `body` -- which only says which rows of which plane go to and come from which rank (rows [b, e) of a pitched
+// plane are one contiguous slab; empty rows are no transfer: both sides know the ranges) --, end.  An early return closes the group and drops the open bracket (GroupGuard).
+struct RowExchange
+{
+    mifx_comm*  c;
+    hipStream_t s;
+    static unsigned char* at(const Plane& p, int row) { return static_cast<unsigned char*>(p.data) + size_t(row) * p.pitch; }
+    mifx_status send(const Plane& p, Rows r, int q) const { return r.empty() ? MIFX_OK : c->send(at(p, r.b), size_t(r.e - r.b) * p.pitch, q, s); }
+    mifx_status recv(const Plane& p, Rows r, int q) const { return r.empty() ? MIFX_OK : c->recv(at(p, r.b), size_t(r.e - r.b) * p.pitch, q, s); }
+};
+template <class Body> mifx_status exchange_rows(mifx_comm* c, hipStream_t s, const Body& body)
 {
     MIFX_CHECK(c->begin());
-    GroupGuard guard(c); // (closes the group and drops the open time bracket on every early return)
+    GroupGuard guard(c);
     c->time_start(s);
-    for (const Plane* plane : planes)
-        for (int r = 0; r < c->world; ++r)
-        {
-            if (r == c->rank) continue;
-            // (a rank may own no rows of a small plane: both sides skip the transfer, the ranges are known to all)
-            if (!rows[c->rank].empty()) MIFX_CHECK(c->send(row_ptr(*plane, rows[c->rank].b), row_bytes(*plane, rows[c->rank].b, rows[c->rank].e), r, s));
-            if (!rows[r].empty()) MIFX_CHECK(c->recv(row_ptr(*plane, rows[r].b), row_bytes(*plane, rows[r].b, rows[r].e), r, s));
-        }
+    MIFX_CHECK(body(RowExchange{c, s}));
     MIFX_CHECK(c->end(s));
     c->time_stop(s);
     return MIFX_OK;
 }
-mifx_status allgather_rows(mifx_comm* c, const Plane& plane, const std::vector<Rows>& rows, hipStream_t s) { return allgather_rows(c, {&plane}, rows, s); }
+
+// every rank's rows [b_r, e_r) of every plane of `planes` (planes of one height) go to every other rank: an all-gather of uneven row slabs as direct sends, one group
+// (a rank may own no rows of a small plane: both sides skip the transfer)
+mifx_status allgather_rows(mifx_comm* c, std::initializer_list<const Plane*> planes, const std::vector<Rows>& rows, hipStream_t s)
+{
+    return exchange_rows(c, s, [&](RowExchange x) -> mifx_status {
+        for (const Plane* plane : planes)
+            for (int r = 0; r < c->world; ++r)
+            {
+                if (r == c->rank) continue;
+                MIFX_CHECK(x.send(*plane, rows[c->rank], r));
+                MIFX_CHECK(x.recv(*plane, rows[r], r));
+            }
+        return MIFX_OK;
+    });
+}
 } // namespace
 
 extern "C" {
@@ -623,267 +636,243 @@ extern "C++" void mifx::chain_detach_comm(mifx_chain* chain)
     chain->cuts.clear();
 }
 
-// One frame of a rank's band: the phases of mifx_chain_execute_phase with the exchanges between them -- or, comm == nullptr (mifx_chain_execute_band), without them.
-//
-// Two lanes across frames (round 5; chain->overlap >= 2 and asynchronous halos, the input contract of mifx_chain_set_overlap 2): phases 0 - 2 -- shade, prep, SSAO, SSR,
-// composite, TAA, Bloom's fine levels, the Bloom gather -- run on the chain's side stream L, phase 3 -- Bloom's coarse levels and the final pass, ~15 launches of a few
-// microseconds each that leave the GPU idle -- on the context's stream M behind them.  The next frame's L does not wait for M until its own phase 2 (which overwrites the
-// Bloom levels and the depth-of-field output phase 3 reads), so this frame's Bloom tail runs beside the next frame's shade and SSAO -- what the unsharded chain's lanes do
-// for the whole frame, for a band whose fixed per-rank work weighs eight times as much.  When the call returns, M is ordered behind everything of the frame.
-// (chain->overlap >= 3: a third lane for the PostFX prep and SSAO, below.)
-static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, mifx_comm* c)
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------ the sharded frame, in parts
+namespace
 {
-    const int H = int(f->frame.Height);
-    const int world = c ? c->world : 1, rank = c ? c->rank : 0;
-    mifx_postfx* ctx = chain->ctx;
-    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
-    const hipStream_t M = ctx->stream;
-
-    // Everything that can be refused is checked before the first kernel and before any group is opened: what every rank owns and needs follows from the cuts and the
-    // per-frame attributes alone (the resources are prepared first: the Bloom plan reads the level sizes).
-    MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
-    std::vector<Rows> bands(world);
-    std::vector<mifx_shard_info> info(world);
-    int halos[3] = {0, 0, 0}; // TAA, SSR, SSAO: both neighbours of an edge move the same number of rows = the largest need of any rank
-    // Round 6: Bloom's level 0 with halos (mifx_bloom::Request::halo_level0) -- the row windows of everything in front of Bloom follow from it: the needs of the ranks
-    // are derived with it and every phase of the frame is asked for it.
-    const bool halo_level0 = mifx::shard_bloom_halo_enabled();
-    std::vector<mifx_bloom::Plan> plans(world);
-    if (c)
+// What every rank owns and needs: it follows from the cuts and the per-frame attributes alone (after the frame's prepare calls: the Bloom plan reads the level sizes), so
+// everything that can be refused is refused before the first kernel and before any group is opened.  Without a communicator (mifx_chain_execute_band) only halo_level0 counts.
+struct ShardFrame
+{
+    int                           H = 0;
+    std::vector<Rows>             bands;
+    std::vector<mifx_shard_info>  info;
+    std::vector<mifx_bloom::Plan> plans;
+    int  halos[3] = {0, 0, 0}; // TAA, SSR, SSAO: both neighbours of an edge move the same number of rows = the largest need of any rank
+    bool halo_level0 = false; // round 6: Bloom's level 0 with halos (mifx_bloom::Request) -- the needs of the ranks are derived with it, every phase is asked for it
+};
+mifx_status shard_frame(const mifx_chain* chain, const mifx_chain_frame* f, const mifx_comm* c, ShardFrame& fr)
+{
+    fr.H           = int(f->frame.Height);
+    fr.halo_level0 = mifx::shard_bloom_halo_enabled();
+    if (!c) return MIFX_OK;
+    for (int r = 0; r < c->world; ++r) fr.bands.push_back(Rows{chain->cuts[r], chain->cuts[r + 1]});
+    for (const Rows& band : fr.bands) fr.info.push_back(chain_shard_info(chain, f, band, fr.halo_level0));
+    for (const Rows& band : fr.bands) fr.plans.push_back(mifx::chain_bloom_plan(chain, f, band, fr.halo_level0));
+    for (const mifx_shard_info& i : fr.info)
     {
-        for (int r = 0; r < world; ++r) bands[r] = Rows{chain->cuts[r], chain->cuts[r + 1]};
-        for (int r = 0; r < world; ++r) info[r] = chain_shard_info(chain, f, bands[r], halo_level0);
-        for (int r = 0; r < world; ++r) plans[r] = mifx::chain_bloom_plan(chain, f, bands[r], halo_level0);
-        for (int r = 0; r < world; ++r)
-        {
-            MIFX_REQUIRE(info[r].gather_level == info[rank].gather_level, "mifx_chain_execute_sharded: ranks disagree on the Bloom gather level");
-            halos[0] = std::max(halos[0], int(info[r].halo_taa)); halos[1] = std::max(halos[1], int(info[r].halo_ssr)); halos[2] = std::max(halos[2], int(info[r].halo_ssao));
-        }
+        MIFX_REQUIRE(i.gather_level == fr.info[c->rank].gather_level, "mifx_chain_execute_sharded: ranks disagree on the Bloom gather level");
+        fr.halos[0] = std::max(fr.halos[0], int(i.halo_taa)); fr.halos[1] = std::max(fr.halos[1], int(i.halo_ssr)); fr.halos[2] = std::max(fr.halos[2], int(i.halo_ssao));
     }
-    const mifx_shard_info me = c ? info[rank] : mifx_shard_info{};
-    // (a halo taller than a neighbour's band reaches into the band beyond it: the exchange below sends every rank the rows of its ghost zones from whichever
-    //  ranks own them -- "multi-hop" in one step, since all ranks are peers over xGMI)
+    return MIFX_OK;
+}
 
-    const bool async = chain->async_halos;
-    const bool lanes = chain->overlap >= 2 && async && !chain->profiling;
-    // Three lanes (chain->overlap >= 3): prep + SSAO (phase 1) on a lane A of their own -- they read the G-buffer and the PostFX planes only -- beside the shade (phase 0) and
-    // SSR (the first half of phase 2) on L.  L waits for the prep (SSR's temporal pass reads its planes) before phase 2 and for the end of SSAO in front of the composite
-    // (ChainPhaseRequest::sig_after_prep / wait_before_composite); the next frame's A waits for this frame's phase 2 on L, the last reader of what the prep and SSAO overwrite.
-    const bool lanes3 = lanes && chain->overlap >= 3;
-    // ... and a stream H for SSR's depth hierarchy (mifx_ssr::Request::hiz_stream): whole-frame streaming work on every rank that depends on the depth buffer alone -- beside the
-    // shade instead of between it and the march.  Its last reader is the previous frame's march (phase 2 on L); the march of this frame waits for it inside mifx_ssr_execute.
-    hipStream_t L = M; // the stream of phases 0 - 2
-    hipStream_t A = M; // the stream of phase 1
-    hipStream_t Hs = nullptr;
-    if (lanes)
-    {
-        MIFX_CHECK(mifx::chain_make_lanes(chain, true));
-        L = chain->side;
-        A = lanes3 ? chain->lane_x : L;
-        if (lanes3 && !chain->lane_h)
-        {
-            MIFX_HIP_CHECK(hipStreamCreateWithFlags(&chain->lane_h, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&chain->evHiz, &chain->evJoinH}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-        Hs = lanes3 ? chain->lane_h : nullptr;
-        if (!mifx::chain_lanes_continue(chain)) // first frame, or the library queued work on M since the last one (resets, imports, re-allocations): the lanes behind M once
-        {
-            MIFX_HIP_CHECK(hipEventRecord(chain->evFork, M));
-            MIFX_HIP_CHECK(hipStreamWaitEvent(L, chain->evFork, 0));
-            if (lanes3) MIFX_HIP_CHECK(hipStreamWaitEvent(A, chain->evFork, 0));
-            if (Hs) MIFX_HIP_CHECK(hipStreamWaitEvent(Hs, chain->evFork, 0));
-        }
-        else if (lanes3)
-        {
-            MIFX_HIP_CHECK(hipStreamWaitEvent(A, chain->evPrepConsumed, 0)); // (recorded on L behind the previous frame's phase 2)
-            if (Hs) MIFX_HIP_CHECK(hipStreamWaitEvent(Hs, chain->evPrepConsumed, 0));
-        }
-    }
-    struct Restore // whatever happens, the context's stream is M again and ends behind the lanes
-    {
-        mifx_chain* ch;
-        hipStream_t m, l, a, h;
-        bool        joined = false;
-        ~Restore()
-        {
-            ch->ctx->stream = m;
-            if (joined) return;
-            if (l != m && hipEventRecord(ch->evJoinS, l) == hipSuccess) (void)hipStreamWaitEvent(m, ch->evJoinS, 0);
-            if (a != l && hipEventRecord(ch->evJoinX, a) == hipSuccess) (void)hipStreamWaitEvent(m, ch->evJoinX, 0);
-            if (h != nullptr && hipEventRecord(ch->evJoinH, h) == hipSuccess) (void)hipStreamWaitEvent(m, ch->evJoinH, 0);
-        }
-    } restore{chain, M, L, A, Hs};
-
-    // History halos for the next frame: every rank receives the rows of its two ghost zones from whichever ranks own them.  Both sides of a transfer derive its rows from
-    // the cuts and the halo sizes = the largest need of any rank, recomputed every frame (the needs follow the per-frame attributes: SSAO reconstruction radius, Bloom radius).
-    const uint32_t ci = f->frame.Index & 1u;
-    struct HistoryPlane { const Plane* p; int halo; };
-    auto exchange_halos = [&](std::initializer_list<HistoryPlane> planes, hipStream_t s) -> mifx_status {
-        if (!c) return MIFX_OK;
-        MIFX_CHECK(c->begin());
-        GroupGuard guard(c);
-        c->time_start(s);
-        auto meet = [](Rows a, Rows b) { return Rows{a.b > b.b ? a.b : b.b, a.e < b.e ? a.e : b.e}; };
+// History halos for the next frame: every rank receives the rows of its two ghost zones from whichever ranks own them.  Both sides of a transfer derive its rows from
+// the cuts and the halo sizes = the largest need of any rank, recomputed every frame (the needs follow the per-frame attributes: SSAO reconstruction radius, Bloom radius).
+// (a halo taller than a neighbour's band reaches into the band beyond it: "multi-hop" in one step, since all ranks are peers over xGMI)
+struct HistoryPlane { const Plane* p; int halo; };
+mifx_status exchange_halos(mifx_comm* c, const ShardFrame& fr, std::initializer_list<HistoryPlane> planes, hipStream_t s)
+{
+    if (!c) return MIFX_OK;
+    return exchange_rows(c, s, [&](RowExchange x) -> mifx_status {
         for (const HistoryPlane& hp : planes)
         {
-            const int  halo = hp.halo;
-            const Rows mine = bands[rank];
             // the ghost zone of rank r on the side of rank q: the `halo` rows above its band when q lies above it, below otherwise
-            auto ghost = [&](int r, int q) { return rows_clip(q < r ? Rows{bands[r].b - halo, bands[r].b} : Rows{bands[r].e, bands[r].e + halo}, H); };
-            for (int q = 0; q < world; ++q)
+            auto ghost = [&](int r, int q) { return rows_clip(q < r ? Rows{fr.bands[r].b - hp.halo, fr.bands[r].b} : Rows{fr.bands[r].e, fr.bands[r].e + hp.halo}, fr.H); };
+            for (int q = 0; q < c->world; ++q)
             {
-                if (q == rank) continue;
-                const Rows out = meet(mine, ghost(q, rank)), in = meet(bands[q], ghost(rank, q)); // both follow from the cuts: the peer computes the same two ranges
-                if (!out.empty()) MIFX_CHECK(c->send(row_ptr(*hp.p, out.b), row_bytes(*hp.p, out.b, out.e), q, s));
-                if (!in.empty()) MIFX_CHECK(c->recv(row_ptr(*hp.p, in.b), row_bytes(*hp.p, in.b, in.e), q, s));
+                if (q == c->rank) continue;
+                MIFX_CHECK(x.send(*hp.p, rows_meet(fr.bands[c->rank], ghost(q, c->rank)), q)); // both follow from the cuts: the peer computes the same two ranges
+                MIFX_CHECK(x.recv(*hp.p, rows_meet(fr.bands[q], ghost(c->rank, q)), q));
             }
         }
-        MIFX_CHECK(c->end(s));
-        c->time_stop(s);
         return MIFX_OK;
+    });
+}
+// Asynchronous halos (mifx_chain::async_halos): a plane's halo is sent on `halo_stream` as soon as the pass that writes it is done, and the stream of the phases waits
+// for it where the next frame first reads that plane.  Every rank issues its groups in the same order (SSAO halos, Bloom gather, TAA + SSR halos), as the transports require.
+mifx_status halos_after(mifx_chain* chain, mifx_comm* c, const ShardFrame& fr, hipStream_t producer, hipEvent_t produced, hipEvent_t exchanged, bool& pending,
+                        std::initializer_list<HistoryPlane> planes)
+{
+    if (!c) return MIFX_OK;
+    MIFX_HIP_CHECK(hipEventRecord(produced, producer));
+    MIFX_HIP_CHECK(hipStreamWaitEvent(chain->halo_stream, produced, 0));
+    MIFX_CHECK(exchange_halos(c, fr, planes, chain->halo_stream));
+    MIFX_HIP_CHECK(hipEventRecord(exchanged, chain->halo_stream));
+    pending = true;
+    // (work queued on the context's stream outside this function is ordered behind the exchange: mifx_postfx::queued_outside_execute; the event is re-recorded every frame)
+    auto& joins = chain->ctx->pending_joins;
+    if (std::find(joins.begin(), joins.end(), exchanged) == joins.end()) joins.push_back(exchanged);
+    return MIFX_OK;
+}
+
+// Round 6: the last level of SSAO's depth pyramid, which A3's far taps read anywhere, is reduced by the rank that owns its rows and all-gathered (two planes of
+// (H / 16) x (W / 16) texels: 1 MB per frame at 7680x4320) instead of reduced whole on every rank: the row of the last level that holds frame row y belongs to the
+// rank whose band holds its first frame row.  Every rank takes the same decision (it follows from the frame and the SSAO flags alone); MIFX_SHARD_GATHER_SSAO_LEVEL=0
+// keeps round 5's whole pyramids.  mifx_chain_execute_band (c == nullptr) reduces what a rank of the sharded frame reduces and leaves the other rows stale.
+mifx_ssao::Request shard_ssao_request(const mifx_chain* chain, const mifx_chain_frame* f, mifx_comm* c, const ShardFrame& fr)
+{
+    static const bool gatherOn = []() { const char* e = std::getenv("MIFX_SHARD_GATHER_SSAO_LEVEL"); return e == nullptr || std::atoi(e) != 0; }();
+    constexpr int kLast = mifx_ssao::kMips - 1;
+    mifx_ssao::Request req;
+    if (!gatherOn || (chain->ssao_flags & MIFX_SSAO_FEATURE_FLAG_HALF_RESOLUTION) != 0 || chain->ssao->depth16 ||
+        pyramid_fusable_levels(int(f->frame.Width), fr.H, kLast) != kLast || chain->band.empty())
+        return req;
+    auto own = [&](Rows band) { return Rows{(band.b + (1 << kLast) - 1) >> kLast, (band.e + (1 << kLast) - 1) >> kLast}; };
+    req.gather_last_level = true;
+    req.own_last_level    = own(c ? fr.bands[c->rank] : chain->band);
+    if (!c) return req;
+    std::vector<Rows> owned;
+    for (const Rows& band : fr.bands) owned.push_back(own(band));
+    req.after_prefilter = [c, owned](const Plane& d, const Plane& z, hipStream_t s) -> mifx_status { return allgather_rows(c, {&d, &z}, owned, s); };
+    return req;
+}
+
+// Bloom's level-0 halos: between the prefilter and the first down-sampling (inside phase 2, on its lane) every rank sends the rows of level 0 it owns that another rank
+// reads but does not produce -- the rows beside the band edges -- and receives its own; who reads and who produces what follows from the plans of all ranks.
+// Empty where no rank reads such a row.  (`fr` outlives the frame's phases: the request holds a reference)
+decltype(mifx_bloom::Request::after_level0) shard_bloom_level0_exchange(mifx_comm* c, const ShardFrame& fr)
+{
+    bool any = false;
+    for (const mifx_bloom::Plan& p : fr.plans) any = any || (p.G >= 0 && !(p.compute0.b == p.down[0].b && p.compute0.e == p.down[0].e));
+    if (!c || !fr.halo_level0 || !any) return nullptr;
+    return [c, &fr](const Plane& level0, hipStream_t s) -> mifx_status {
+        return exchange_rows(c, s, [&](RowExchange x) -> mifx_status {
+            // the two parts of what rank q reads and does not produce: below and above the rows it prefilters itself
+            auto part = [&](int q, int k) { return k == 0 ? Rows{fr.plans[q].down[0].b, fr.plans[q].compute0.b} : Rows{fr.plans[q].compute0.e, fr.plans[q].down[0].e}; };
+            for (int q = 0; q < c->world; ++q)
+                for (int k = 0; k < 2; ++k)
+                {
+                    if (q == c->rank) continue;
+                    MIFX_CHECK(x.send(level0, rows_meet(part(q, k), fr.plans[c->rank].own0), q));
+                    MIFX_CHECK(x.recv(level0, rows_meet(part(c->rank, k), fr.plans[q].own0), q));
+                }
+            return MIFX_OK;
+        });
     };
-    // Asynchronous halos (mifx_chain::async_halos): a plane's halo is sent on `halo_stream` as soon as the pass that writes it is done, and the stream of the phases waits
-    // for it where the next frame first reads that plane.  Every rank issues its groups in the same order (SSAO halos, Bloom gather, TAA + SSR halos), as the transports require.
-    if (c && async && chain->halo_stream == nullptr)
+}
+
+// The streams of the frame.  Two lanes across frames (round 5; chain->overlap >= 2 and asynchronous halos, the input contract of mifx_chain_set_overlap 2): phases 0 - 2 --
+// shade, prep, SSAO, SSR, composite, TAA, Bloom's fine levels, the Bloom gather -- run on the chain's side stream L, phase 3 -- Bloom's coarse levels and the final pass,
+// ~15 launches of a few microseconds each that leave the GPU idle -- on the context's stream M behind them.  The next frame's L does not wait for M until its own phase 2
+// (which overwrites the Bloom levels and the depth-of-field output phase 3 reads), so this frame's Bloom tail runs beside the next frame's shade and SSAO -- what the
+// unsharded chain's lanes do for the whole frame, for a band whose fixed per-rank work weighs eight times as much.
+// Three lanes (chain->overlap >= 3): prep + SSAO (phase 1) on a lane A of their own -- they read the G-buffer and the PostFX planes only -- beside the shade (phase 0) and
+// SSR (the first half of phase 2) on L.  L waits for the prep (SSR's temporal pass reads its planes) before phase 2 and for the end of SSAO in front of the composite
+// (ChainPhaseRequest::sig_after_prep / wait_before_composite); the next frame's A waits for this frame's phase 2 on L (evPrepConsumed), the last reader of what the prep and
+// SSAO overwrite.  ... and a stream H for SSR's depth hierarchy (mifx_ssr::Request::hiz_stream): whole-frame streaming work on every rank that depends on the depth buffer
+// alone -- beside the shade instead of between it and the march.  Its last reader is the previous frame's march (phase 2 on L); this frame's march waits for it inside mifx_ssr_execute.
+// The first frame, or one before which the library queued work on M (resets, imports, re-allocations), starts every lane behind M once (chain_fork_lanes).
+struct ShardLanes { hipStream_t L, A, H; bool two, three; }; // L: phases 0 - 2, A: phase 1 (both the context's stream without lanes), H: null without the third lane
+mifx_status shard_lanes(mifx_chain* chain, const mifx_comm* c, ShardLanes& ln)
+{
+    const bool two = chain->overlap >= 2 && chain->async_halos && !chain->profiling, three = two && chain->overlap >= 3;
+    ln = ShardLanes{chain->ctx->stream, chain->ctx->stream, nullptr, two, three};
+    if (two)
+    {
+        MIFX_CHECK(mifx::chain_make_lanes(chain, three ? 4 : 3));
+        ln.L = chain->side;
+        ln.A = three ? chain->lane_x : ln.L;
+        ln.H = three ? chain->lane_h : nullptr;
+        MIFX_CHECK(mifx::chain_fork_lanes(chain, {{ln.L, nullptr}, {three ? ln.A : nullptr, chain->evPrepConsumed}, {ln.H, chain->evPrepConsumed}}));
+    }
+    if (c && chain->async_halos && chain->halo_stream == nullptr) // the stream of halos_after
     {
         MIFX_HIP_CHECK(hipStreamCreateWithFlags(&chain->halo_stream, hipStreamNonBlocking));
         for (hipEvent_t* e : {&chain->evAfterP1, &chain->evAfterP2, &chain->evHaloSsao, &chain->evHaloRest}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-    auto halos_after = [&](hipStream_t producer, hipEvent_t produced, hipEvent_t exchanged, bool& pending, std::initializer_list<HistoryPlane> planes) -> mifx_status {
-        if (!c) return MIFX_OK;
-        MIFX_HIP_CHECK(hipEventRecord(produced, producer));
-        MIFX_HIP_CHECK(hipStreamWaitEvent(chain->halo_stream, produced, 0));
-        MIFX_CHECK(exchange_halos(planes, chain->halo_stream));
-        MIFX_HIP_CHECK(hipEventRecord(exchanged, chain->halo_stream));
-        pending = true;
-        // (work queued on the context's stream outside this function is ordered behind the exchange: mifx_postfx::queued_outside_execute; the event is re-recorded every frame)
-        if (std::find(ctx->pending_joins.begin(), ctx->pending_joins.end(), exchanged) == ctx->pending_joins.end()) ctx->pending_joins.push_back(exchanged);
-        return MIFX_OK;
-    };
+    return MIFX_OK;
+}
+} // namespace
+
+// One frame of a rank's band: the phases of mifx_chain_execute_phase with the exchanges between them -- or, comm == nullptr (mifx_chain_execute_band), without them.
+// mifx_chain_execute_phase joins a pending halo exchange of the previous frame where the phase first reads the plane; every phase gets a request of its own
+// (mifx_objects.h ChainPhaseRequest).  When the call returns, M is ordered behind everything of the frame.
+static mifx_status execute_sharded_impl(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, mifx_comm* c)
+{
+    mifx_postfx* ctx = chain->ctx;
+    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
+    MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
+    ShardFrame fr;
+    MIFX_CHECK(shard_frame(chain, f, c, fr));
+    ShardLanes ln;
+    MIFX_CHECK(shard_lanes(chain, c, ln));
+    const hipStream_t M = ctx->stream, L = ln.L, A = ln.A; // (shard_lanes leaves the context's stream alone)
+    LaneJoin join{chain, M, {ln.two ? L : nullptr, chain->evJoinS}, {ln.three ? A : nullptr, chain->evJoinX}, {ln.H, chain->evJoinH}};
+    const bool        async = chain->async_halos;
+    const uint32_t    ci    = f->frame.Index & 1u;
+    const HistoryPlane taa{&chain->taa->accum[ci], fr.halos[0]}, ssrRad{&chain->ssr->hist_radiance[ci], fr.halos[1]}, ssrVar{&chain->ssr->hist_variance[ci], fr.halos[1]},
+        ao{&chain->ssao->history_ao[ci], fr.halos[2]}, aoLen{&chain->ssao->history_len[ci], fr.halos[2]};
 
     // phases 0 and 1: shade, prep, SSAO.  (Until round 3 the band rows of the shaded radiance were all-gathered here -- 465 MB per GPU and frame at 8K / 8 ranks; the
-    // ray march now records where it hit and phase 2 loads the colour there or re-shades it: api_chain.cpp.)  mifx_chain_execute_phase joins a pending halo exchange of
-    // the previous frame where the phase first reads the plane.  Every phase gets a request of its own (mifx_objects.h ChainPhaseRequest).
+    // ray march now records where it hit and phase 2 loads the colour there or re-shades it: api_chain.cpp.)
     ChainPhaseRequest plain; // (phases 0, 3 and 4; what phases 1 and 2 start from)
-    plain.bloom.halo_level0 = halo_level0;
+    plain.bloom.halo_level0 = fr.halo_level0;
     ctx->stream = L;
     MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 0, plain));
     ctx->stream = A;
     ChainPhaseRequest q1 = plain;
-    if (lanes3) q1.sig_after_prep = chain->evPrep;
-    // Round 6: the last level of SSAO's depth pyramid, which A3's far taps read anywhere, is reduced by the rank that owns its rows and all-gathered (two planes of
-    // (H / 16) x (W / 16) texels: 1 MB per frame at 7680x4320) instead of reduced whole on every rank: the row of the last level that holds frame row y belongs to the
-    // rank whose band holds its first frame row.  Every rank takes the same decision (it follows from the frame and the SSAO flags alone); MIFX_SHARD_GATHER_SSAO_LEVEL=0
-    // keeps round 5's whole pyramids.  mifx_chain_execute_band (c == nullptr) reduces what a rank of the sharded frame reduces and leaves the other rows stale.
-    {
-        static const bool gatherOn = []() { const char* e = std::getenv("MIFX_SHARD_GATHER_SSAO_LEVEL"); return e == nullptr || std::atoi(e) != 0; }();
-        constexpr int kLast = mifx_ssao::kMips - 1;
-        const uint32_t W = f->frame.Width;
-        const bool can = gatherOn && (chain->ssao_flags & MIFX_SSAO_FEATURE_FLAG_HALF_RESOLUTION) == 0 && !chain->ssao->depth16 &&
-                         pyramid_fusable_levels(int(W), H, kLast) == kLast && !chain->band.empty();
-        if (can)
-        {
-            auto own = [&](Rows band) { return Rows{(band.b + (1 << kLast) - 1) >> kLast, (band.e + (1 << kLast) - 1) >> kLast}; };
-            q1.ssao.gather_last_level = true;
-            q1.ssao.own_last_level    = own(c ? bands[rank] : chain->band);
-            if (c)
-            {
-                std::vector<Rows> owned(world);
-                for (int r = 0; r < world; ++r) owned[r] = own(bands[r]);
-                q1.ssao.after_prefilter = [c, owned](const Plane& d, const Plane& z, hipStream_t s) -> mifx_status { return allgather_rows(c, {&d, &z}, owned, s); };
-            }
-        }
-    }
+    if (ln.three) q1.sig_after_prep = chain->evPrep;
+    q1.ssao = shard_ssao_request(chain, f, c, fr);
     MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 1, q1));
-    if (lanes3) MIFX_HIP_CHECK(hipEventRecord(chain->evSsao, A));
-    if (async) MIFX_CHECK(halos_after(A, chain->evAfterP1, chain->evHaloSsao, chain->halo_ssao_pending, {{&chain->ssao->history_ao[ci], halos[2]}, {&chain->ssao->history_len[ci], halos[2]}}));
+    if (ln.three) MIFX_HIP_CHECK(hipEventRecord(chain->evSsao, A));
+    if (async) MIFX_CHECK(halos_after(chain, c, fr, A, chain->evAfterP1, chain->evHaloSsao, chain->halo_ssao_pending, {ao, aoLen}));
     ctx->stream = L;
 
     // phase 2 (behind the previous frame's phase 3, whose Bloom levels and depth-of-field output it overwrites), then the Bloom level every rank needs whole: what each
     // rank owns follows from its band
-    if (lanes) MIFX_HIP_CHECK(hipStreamWaitEvent(L, chain->evBloomDone, 0)); // (never recorded = no wait)
+    if (ln.two) MIFX_HIP_CHECK(hipStreamWaitEvent(L, chain->evBloomDone, 0)); // (never recorded = no wait)
     ChainPhaseRequest q2 = plain;
-    if (lanes3)
+    if (ln.three)
     {
         MIFX_HIP_CHECK(hipStreamWaitEvent(L, chain->evPrep, 0));
         q2.wait_before_composite = chain->evSsao;
         const char* hizLane = std::getenv("MIFX_SHARD_HIZ_LANE"); // (0: the hierarchy stays on L between the shade and the march -- A/B runs)
-        if (Hs && (hizLane == nullptr || std::atoi(hizLane) != 0))
+        if (hizLane == nullptr || std::atoi(hizLane) != 0)
         {
-            q2.hiz_stream = Hs;
+            q2.hiz_stream = ln.H;
             q2.hiz_done   = chain->evHiz;
         }
     }
-    // Bloom's level-0 halos: between the prefilter and the first down-sampling (inside phase 2, on this lane) every rank sends the rows of level 0 it owns that another rank
-    // reads but does not produce -- the rows beside the band edges -- and receives its own; who reads and who produces what follows from the plans of all ranks.
-    if (c && halo_level0)
-    {
-        bool any = false;
-        for (int r = 0; r < world; ++r) any = any || (plans[r].G >= 0 && !(plans[r].compute0.b == plans[r].down[0].b && plans[r].compute0.e == plans[r].down[0].e));
-        if (any)
-            q2.bloom.after_level0 = [c, rank, world, &plans](const Plane& level0, hipStream_t s) -> mifx_status {
-                MIFX_CHECK(c->begin());
-                GroupGuard guard(c);
-                c->time_start(s);
-                auto meet = [](Rows a, Rows b) { return Rows{a.b > b.b ? a.b : b.b, a.e < b.e ? a.e : b.e}; };
-                // the two parts of what rank q reads and does not produce: below and above the rows it prefilters itself
-                auto parts = [&](int q, Rows out[2]) { out[0] = Rows{plans[q].down[0].b, plans[q].compute0.b}; out[1] = Rows{plans[q].compute0.e, plans[q].down[0].e}; };
-                for (int q = 0; q < world; ++q)
-                {
-                    if (q == rank) continue;
-                    Rows theirs[2], mine[2];
-                    parts(q, theirs);
-                    parts(rank, mine);
-                    for (int k = 0; k < 2; ++k)
-                    {
-                        const Rows out = meet(theirs[k], plans[rank].own0), in = meet(mine[k], plans[q].own0);
-                        if (!out.empty()) MIFX_CHECK(c->send(row_ptr(level0, out.b), row_bytes(level0, out.b, out.e), q, s));
-                        if (!in.empty()) MIFX_CHECK(c->recv(row_ptr(level0, in.b), row_bytes(level0, in.b, in.e), q, s));
-                    }
-                }
-                MIFX_CHECK(c->end(s));
-                c->time_stop(s);
-                return MIFX_OK;
-            };
-    }
+    q2.bloom.after_level0 = shard_bloom_level0_exchange(c, fr);
     MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 2, q2));
-    if (c && me.gather_level >= 0)
+    if (c && fr.info[c->rank].gather_level >= 0)
     {
-        std::vector<Rows> own(world);
-        for (int r = 0; r < world; ++r) own[r] = Rows{info[r].own_begin, info[r].own_end};
-        MIFX_CHECK(allgather_rows(c, *chain->bloom->down[me.gather_level], own, L));
+        std::vector<Rows> own;
+        for (const mifx_shard_info& i : fr.info) own.push_back(Rows{i.own_begin, i.own_end});
+        MIFX_CHECK(allgather_rows(c, {chain->bloom->down[fr.info[c->rank].gather_level]}, own, L));
     }
-    if (async)
-        MIFX_CHECK(halos_after(L, chain->evAfterP2, chain->evHaloRest, chain->halo_rest_pending,
-                               {{&chain->taa->accum[ci], halos[0]}, {&chain->ssr->hist_radiance[ci], halos[1]}, {&chain->ssr->hist_variance[ci], halos[1]}}));
+    if (async) MIFX_CHECK(halos_after(chain, c, fr, L, chain->evAfterP2, chain->evHaloRest, chain->halo_rest_pending, {taa, ssrRad, ssrVar}));
     ctx->stream = M;
-    if (lanes)
+    if (ln.two)
     {
         MIFX_HIP_CHECK(hipEventRecord(chain->evPrepConsumed, L));
         MIFX_HIP_CHECK(hipStreamWaitEvent(M, chain->evPrepConsumed, 0));
-        restore.joined = true;
+        join.joined = true;
     }
     MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 3, plain));
     if (chain->auto_exposure) // the low-resolution luminance rows of every band, then the reduction and the tone map
     {
         if (c)
         {
-            std::vector<Rows> lum(world);
-            for (int r = 0; r < world; ++r) lum[r] = Rows{info[r].ae_begin, info[r].ae_end};
-            MIFX_CHECK(allgather_rows(c, chain->auto_exposure->low_res, lum, M));
+            std::vector<Rows> lum;
+            for (const mifx_shard_info& i : fr.info) lum.push_back(Rows{i.ae_begin, i.ae_end});
+            MIFX_CHECK(allgather_rows(c, {&chain->auto_exposure->low_res}, lum, M));
         }
         MIFX_CHECK(mifx::chain_execute_phase(chain, f, out_ldr, 4, plain));
     }
-    if (lanes)
+    if (ln.two)
     {
         MIFX_HIP_CHECK(hipEventRecord(chain->evBloomDone, M));
         chain->seen_epoch    = ctx->stream_epoch;
         chain->prep_consumed = true;
     }
     if (async) return MIFX_OK;
-    return exchange_halos({{&chain->taa->accum[ci], halos[0]}, {&chain->ssr->hist_radiance[ci], halos[1]}, {&chain->ssr->hist_variance[ci], halos[1]},
-                           {&chain->ssao->history_ao[ci], halos[2]}, {&chain->ssao->history_len[ci], halos[2]}}, M);
+    return exchange_halos(c, fr, {taa, ssrRad, ssrVar, ao, aoLen}, M);
 }
+
+extern "C" {
 
 mifx_status mifx_chain_execute_sharded(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr)
 {

@@ -484,9 +484,33 @@ struct ChainPhaseRequest
 mifx_status chain_execute_phase(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* out_ldr, int32_t phase, const ChainPhaseRequest& req);
 // HnPostProcessTask::Prepare: the per-frame PrepareResources of every effect and the chain's own planes (idempotent for an unchanged frame description)
 mifx_status chain_prepare_resources(mifx_chain* chain, const mifx_chain_frame* f);
-// the chain's extra streams and their events, created on first use; whether this frame's lanes may start behind the previous frame's events alone (api_chain.cpp)
-mifx_status chain_make_lanes(mifx_chain* chain, bool three);
-bool        chain_lanes_continue(mifx_chain* chain);
+// A frame on more than one stream (api_chain.cpp).  chain_make_lanes: the chain's extra streams and their events, created on first use -- `lanes` 2: side; 3: and lane_x;
+// 4: and lane_h (the sharded frame's depth-hierarchy stream).
+mifx_status chain_make_lanes(mifx_chain* chain, int lanes);
+// chain_fork_lanes: how the frame's lanes start.  Where they may continue from the previous frame (it recorded its events and the library queued nothing on the context's
+// stream since; `across_frames` off: never) each lane waits for its event alone (null: no wait); otherwise evFork is recorded on the context's stream once and every lane
+// waits for it.  A null `lane` is skipped, here and below.
+struct LaneEvent { hipStream_t lane; hipEvent_t ev; };
+mifx_status chain_fork_lanes(mifx_chain* chain, std::initializer_list<LaneEvent> lanes, bool across_frames = true);
+// Whatever happens between the fork and the end of the frame, the context's stream is `m` again, carries no kernel hook and -- unless the regular path joined the lanes
+// through its own events and said so -- ends behind every lane: each lane's event is recorded on it and `m` waits for it, in the order given.
+struct LaneJoin
+{
+    mifx_chain* chain;
+    hipStream_t m;
+    LaneEvent   lanes[3];
+    bool        joined = false;
+    LaneJoin(mifx_chain* c, hipStream_t main, LaneEvent a, LaneEvent b = {}, LaneEvent d = {}) : chain(c), m(main), lanes{a, b, d} {}
+    LaneJoin(const LaneJoin&) = delete;
+    ~LaneJoin()
+    {
+        chain->ctx->stream      = m;
+        chain->ctx->kernel_hook = nullptr;
+        if (joined) return;
+        for (const LaneEvent& l : lanes)
+            if (l.lane != nullptr && hipEventRecord(l.ev, l.lane) == hipSuccess) (void)hipStreamWaitEvent(m, l.ev, 0);
+    }
+};
 // the depth hierarchy of a W x H frame as one allocation + per-level views (api_ssr.cpp)
 mifx_status ssr_alloc_hiz(uint32_t W, uint32_t H, Plane* hiz, DeviceScratch& slab);
 // the chain stops borrowing its communicator (api_comm.cpp)

@@ -16,6 +16,7 @@ struct Rows
 };
 inline Rows rows_clip(Rows r, int h) { return Rows{r.b < 0 ? 0 : r.b, r.e > h ? h : r.e}; }
 inline Rows rows_expand(Rows r, int g, int h) { return rows_clip(Rows{r.b - g, r.e + g}, h); }
+inline Rows rows_meet(Rows a, Rows b) { return Rows{a.b > b.b ? a.b : b.b, a.e < b.e ? a.e : b.e}; }
 inline Rows rows_hull(Rows a, Rows b) { return Rows{a.b < b.b ? a.b : b.b, a.e > b.e ? a.e : b.e}; }
 inline Rows rows_align(Rows r, int a, int h) { return rows_clip(Rows{(r.b / a) * a, ((r.e + a - 1) / a) * a}, h); }
 // rows of the next coarser level (half resolution, hl rows) that cover the rows r of the finer level, grown by g coarse rows

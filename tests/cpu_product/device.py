@@ -89,6 +89,7 @@ class Device:
         self.log = []
         self.algorithm = "gtao"
         self.taa_flags_seen = None
+        self.fail_next = None  # the name of a launch that fails once (MIFX_ERR_HIP) instead of running
 
     def chain(self, rev):
         return cpu_chain.CpuChain(self.lib, self.prefix, reversed_depth=bool(rev))
@@ -107,6 +108,12 @@ class Device:
         name = c.name.decode()
         a = [c.arg[i] for i in range(c.count)]
         self.log.append(name)
+        if name == self.fail_next:  # (run.py lane_errors: this launch fails once -- the return value is the launcher's status)
+            self.fail_next = None
+            if TRACK is not None:
+                TRACK.begin_launch(c.stream or 0, name + " (fails)")
+                TRACK.end_launch()
+            return -3
         try:
             with self._lock:  # (the checker binds its textures to globals: one pass at a time, whichever rank's thread asks)
                 if TRACK is not None:
@@ -554,10 +561,41 @@ class Device:
         return o
 
     def do_tonemap(self, src, out, attribs, ave_log_lum, flags, ave_lum, packed_in):
-        assert not ave_lum.p and not packed_in.i
+        assert not packed_in.i
+        lum = max(0.05, float(ctypes.c_float.from_address(ave_lum.p).value)) if ave_lum.p else ave_log_lum.f  # (auto exposure: GetAverageSceneLuminance of the 1x1 average)
         o = cpu_chain.f32((out.img.h, out.img.w, 4))
-        self.chain(False).call("tonemap", [tight(view(src.img, 4))], [o], attribs=ctypes.string_at(attribs.p, attribs.bytes), fval=[ave_log_lum.f], ival=[int(flags.i)])
+        self.chain(False).call("tonemap", [tight(view(src.img, 4))], [o], attribs=ctypes.string_at(attribs.p, attribs.bytes), fval=[lum], ival=[int(flags.i)])
         store(out.img, o, 4)
+
+    # auto exposure: the low-resolution luminance is the reference's pass; the mip chain and the blend into the 1x1 average are restated here (the checker's entry does
+    # both in one go, the sharded frame needs them apart): the same code for the whole frame and for the rows of a band, so the two are equal or the rows travelled wrong
+    # (run by tests/test_cpu_product.py test_auto_exposure_in_the_sharded_frame_on_the_cpu and by run.py trace; the kernels themselves are held to the reference on the device)
+    def _low_res_luminance(self, color):
+        low, scratch = cpu_chain.f32((64, 64, 2)), cpu_chain.f32((1, 1))
+        self.chain(False).call("autoexposure", [tight(view(color.img, 4))], [low, scratch], fval=[0.0], ival=[0])
+        return low
+
+    @staticmethod
+    def _average_luminance(low, average, elapsed, adapt):
+        v = tight(low)
+        while v.shape[0] > 1:
+            v = ((v[0::2, 0::2] + v[0::2, 1::2]) + (v[1::2, 0::2] + v[1::2, 1::2])) * np.float32(0.25)
+        wsum, w = np.float32(v[0, 0, 0]), np.float32(v[0, 0, 1])
+        weight = np.float32(1.0 - np.exp(-elapsed) if adapt else 1.0) * np.clip(w / np.float32(1e-3), np.float32(0), np.float32(1))
+        dst = ctypes.c_float.from_address(average.p)
+        dst.value = float(np.float32(np.exp(wsum / max(w, np.float32(1e-6)))) * weight + np.float32(dst.value) * (np.float32(1) - weight))
+
+    def do_autoexposure(self, color, low_res, average, elapsed, adapt, packed_in):
+        assert not packed_in.i
+        store(low_res.img, self._low_res_luminance(color), 2)
+        self._average_luminance(view(low_res.img, 2), average, elapsed.f, adapt.i)
+
+    def do_autoexposure_rows(self, color, low_res, row_begin, row_end, packed_in):
+        assert not packed_in.i
+        view(low_res.img, 2, _write=True)[row_begin.i: row_end.i] = self._low_res_luminance(color)[row_begin.i: row_end.i]
+
+    def do_autoexposure_reduce(self, low_res, average, elapsed, adapt):
+        self._average_luminance(view(low_res.img, 2), average, elapsed.f, adapt.i)
 
     def do_bloom_final_tonemap(self, inp, down, out, ldr, bloom_attribs, tm_attribs, ave_log_lum, flags, write_bloom_output, packed_input):
         assert not packed_input.i

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY.  Runs scenarios of the DEVICE tests (tests/test_gpu_host_sequence.py: the effect objects driven through the C ABI, compared with oracle/cpu_chain.py)
 on the CPU build of the product's host code (tests/cpu_product/build.py) with the reference's shaders standing in for the kernels (tests/cpu_product/device.py).
 
-    MIFX_LIB_PATH=tests/cpu_product/_build/libmifx_cpu.so python tests/cpu_product/run.py scenarios | dof | chain | random FIRST LAST | chain_random FIRST LAST
+    MIFX_LIB_PATH=tests/cpu_product/_build/libmifx_cpu.so python tests/cpu_product/run.py scenarios | dof | chain | random FIRST LAST | chain_random FIRST LAST | order | trace [PART OF A NAME] | lane_errors | ...
 
 (started by tests/test_cpu_product.py in a process of its own: the Python mirror diligentfx_amd/api.py is used as it is, with three of its device plumbing points replaced
 here -- the stream handle, the device of the tensors, the view of an effect-owned plane -- so that torch CPU tensors stand for device memory.)"""
@@ -206,7 +206,7 @@ GROUP_CASES = [(2, 160, 192, None, ""), (3, 160, 192, (0, 60, 130, 192), ""), (4
                (3, 160, 192, (0, 60, 130, 192), "three lanes")]  # mifx_chain_set_overlap 3: the event requests of the SSAO lane (streams do nothing here: the host logic)
 
 
-def local_group_case(lib, case, frames=4):
+def local_group_case(lib, case, frames=4, auto_exposure=False):
     """mifx_chain_execute_sharded with the in-library communicator of one process (mifx_comm_create_local_group: csrc/api_comm.cpp -- the same code that decides which rows
     go to whom for the RCCL transport, with a copy in place of ncclSend / ncclRecv): one thread per rank, against the unsharded chain object, for equality
     (tests/test_comm.py::test_sharded_execute_in_process_group on the CPU build)."""
@@ -244,6 +244,8 @@ def local_group_case(lib, case, frames=4):
             da.MaxCircleOfConfusion = 0.02
             c.set_depth_of_field(da, 3)
             DEVICE.dof_attribs = bytes(da)
+        if auto_exposure:
+            c.set_auto_exposure(True)
     if mode == "depth of field":
         for f in fr:
             f["camera"].fFocusDistance, f["camera"].fFStop, f["camera"].fFocalLength = 12.0, 1.2, 135.0
@@ -267,7 +269,7 @@ def local_group_case(lib, case, frames=4):
             except Exception as e:  # noqa: BLE001
                 errors.append((r, repr(e)))
 
-        threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+        threads = [threading.Thread(target=run, args=(r,), name=f"rank {r}") for r in range(world)]
         for t in threads:
             t.start()
         for t in threads:
@@ -290,9 +292,11 @@ def local_group_case(lib, case, frames=4):
     return stats, infos
 
 
-def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, size=(96, 64)):
+def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, size=(96, 64), track=None, reset_at=None, edges=None, fail_at=None, fail="taa", outs=None):
     """One chain object, `frames` frames queued without a host synchronisation in between (as bench.py queues them), under tests/cpu_product/order.py: returns the LaneOrder
-    with its findings and the index range of the hipStreamWaitEvent calls of the last frame.  band = (y0, y1): mifx_chain_execute_band on that row band instead."""
+    with its findings and the index range of the hipStreamWaitEvent calls of the last frame.  band = (y0, y1): mifx_chain_execute_band on that row band instead.
+    track: a LaneOrder of the caller's (call_trace below); reset_at: reset_history before that frame; edges: mifx_chain_set_lane_edges; fail_at: the `fail` launch of that frame
+    fails (device.py fail_next), and `outs` receives every frame's output, or the error its execute raised."""
     import chain_util
     import order as O
     from diligentfx_amd import synth
@@ -305,7 +309,7 @@ def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, s
     shade = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
     scene = synth.Scene()
     fr = [synth.make_frame(scene, 16 + i, W, H, torch.device("cpu")) for i in range(frames)]
-    track = O.LaneOrder()
+    track = track or O.LaneOrder()
     track.drop_wait = drop_wait
     cb = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)(track.runtime)
     lib.mifx_cpu_set_runtime_callback(cb)
@@ -323,13 +327,30 @@ def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, s
         if band:
             chain.set_row_band(band[0], band[1], 12)
         chain.set_overlap(mode)
+        if edges:
+            chain.set_lane_edges(edges)
         out = torch.zeros(H, W, 4)
         last = (0, 0)
         for i, f in enumerate(fr):
+            if i == reset_at:
+                chain.reset_history()
             DEVICE.cam, DEVICE.prev_cam = bytes(f["camera"]), bytes(f["prev_camera"])
+            DEVICE.fail_next = fail if i == fail_at else None
+            if i == fail_at and hasattr(track, "note"):
+                track.note("the failing frame begins", "", ())
             w0 = track.waits
             b = chain.bind_frame(16 + i, f, ibl, shade, out)
-            (chain.execute_band if band else chain.execute)(b)
+            try:
+                (chain.execute_band if band else chain.execute)(b)
+            except B.MifxError as e:
+                if i != fail_at:
+                    raise
+                out = str(e)
+                if hasattr(track, "note"):
+                    track.note("the failing frame returns", "", ())
+            if outs is not None:
+                outs.append(out if isinstance(out, str) else out.clone())
+            out = torch.zeros(H, W, 4) if isinstance(out, str) else out
             last = (w0, track.waits)
         chain.set_overlap(0)
         chain.close()
@@ -337,6 +358,117 @@ def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, s
         cpu_device.TRACK = None
         lib.mifx_cpu_set_runtime_callback(ctypes.cast(None, ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)))
     return track, last
+
+
+def call_trace(check_order=True):
+    """order.py's LaneOrder that also writes down what the host code asks of the runtime, per calling thread (by thread name): event records, stream waits, host
+    synchronisations, asynchronous copies / fills and launches (name + stream), as tuples in `calls[thread]`.  Streams and events are numbered by first appearance in the
+    thread's own sequence; creations and destructions are left out (a creation makes the address a new handle).  check_order off: the trace alone (ranks on threads)."""
+    import threading
+
+    import order as O
+
+    names = {O.RT_EVENT_RECORD: ("record", "es"), O.RT_STREAM_WAIT: ("wait", "se"), O.RT_STREAM_SYNC: ("stream sync", "s"), O.RT_EVENT_SYNC: ("event sync", "e"),
+             O.RT_WRITE: ("write", "-s"), O.RT_READ: ("read", "-s")}
+
+    class CallTrace(O.LaneOrder):
+        def __init__(self):
+            super().__init__()
+            self.calls, self.ids, self.lock = {}, {}, threading.Lock()
+
+        def note(self, what, kinds, handles, n=None):
+            with self.lock:
+                ids = self.ids.setdefault(threading.current_thread().name, {})
+                args = []
+                for k, h in zip(kinds, handles):
+                    if k != "-":
+                        if (k, h) not in ids:
+                            ids[k, h] = ids[k] = ids.get(k, -1) + 1  # (ids[k]: the last number given to a handle of that kind)
+                        args.append(f"{k}{ids[k, h]}")
+                self.calls.setdefault(threading.current_thread().name, []).append((what, *args) + ((n,) if n is not None else ()))
+
+        def runtime(self, op, a, b, n):
+            if op in (O.RT_STREAM_CREATE, O.RT_EVENT_CREATE):
+                with self.lock:
+                    for ids in self.ids.values():
+                        ids.pop(("s" if op == O.RT_STREAM_CREATE else "e", a or 0), None)
+            elif op in names:
+                self.note(names[op][0], names[op][1], (a or 0, b or 0), n if op in (O.RT_WRITE, O.RT_READ) else None)
+            if check_order:
+                super().runtime(op, a, b, n)
+
+        def begin_launch(self, stream, name):
+            self.note("launch " + name, "s", (stream,))
+            if check_order:
+                super().begin_launch(stream, name)
+
+        def access(self, img, write):
+            if check_order:
+                super().access(img, write)
+
+    return CallTrace()
+
+
+def trace_configurations(lib):
+    """What run.py `trace` runs: (name, function of a CallTrace) for every frame path of the chain -- mifx_chain_execute in every stream mode with the default fusions, all and
+    none (reset_history before frame 4: the lanes fork again; depth of field on for one mask per mode; modes 4 and 5 once more with lane edges), mifx_chain_execute_band,
+    mifx_chain_execute_sharded over the in-library group (per rank), and the synchronous five-plane exchange with the luminance gather, with and without Bloom's level-0 halos."""
+    import order as O
+
+    rt_type = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)
+
+    def group(t, case, env, **kw):
+        cb = rt_type(t.runtime)
+        lib.mifx_cpu_set_runtime_callback(cb)
+        cpu_device.TRACK = t
+        os.environ.update(env)
+        try:
+            local_group_case(lib, case, **kw)
+        finally:
+            for k in env:
+                del os.environ[k]
+            cpu_device.TRACK = None
+            lib.mifx_cpu_set_runtime_callback(ctypes.cast(None, rt_type))
+
+    edges = "ssao_compute_ao_kernel<ssr_intersection_kernel@1,taa_kernel<pbr_shade_ssr_mask_kernel@0"
+    out = []
+    for m in range(6):
+        for j, k in enumerate((31, 63, 0)):
+            dof = j == m % 3
+            out.append((f"execute, overlap {m}, fusion mask {k}{', depth of field' if dof else ''}", lambda t, m=m, k=k, dof=dof: order_run(lib, m, k, dof=dof, track=t, reset_at=4)))
+    for m in (4, 5):
+        out.append((f"execute, overlap {m}, lane edges", lambda t, m=m: order_run(lib, m, 31, track=t, reset_at=4, edges=edges)))
+    for m in (0, 2, 3):
+        out.append((f"execute_band (20, 44), overlap {m}", lambda t, m=m: order_run(lib, m, 31, band=(20, 44), track=t)))
+    for case in range(len(GROUP_CASES)):
+        out.append((f"execute_sharded, group case {case} {GROUP_CASES[case]}", lambda t, case=case: group(t, case, {})))
+    sync = {"MIFX_SHARD_ASYNC_HALOS": "0"}
+    out.append(("execute_sharded, group case 1, auto exposure, synchronous halos", lambda t: group(t, 1, sync, auto_exposure=True)))
+    out.append(("execute_sharded, group case 1, auto exposure, synchronous halos, no Bloom level-0 halo", lambda t: group(t, 1, dict(sync, MIFX_SHARD_BLOOM_HALO="0"), auto_exposure=True)))
+    return [(name, fn, "execute_sharded" not in name) for name, fn in out]
+
+
+def lane_error(lib, mode, band, fail="taa"):
+    """Frames 0 - 2 under order.py with the `fail` launch of frame 1 failing (taa: late in the frame, on whichever lane the mode runs it; postfx_prep in modes 1 and 2: on the
+    side stream, between the fork and the frame's own join -- the window in which the parent left the context's stream unordered): the execute returns the launcher's status; between the failing launch and the return every lane
+    the frame used gets a record and the context's stream (handle 0) a wait for it; frame 2 has no unordered pair and equals the frame 2 of a one-stream chain object given
+    the same failure (the failed frame leaves TAA's history unwritten: the CPU chain has no such state)."""
+    t, outs, want = call_trace(), [], []
+    order_run(lib, mode, 31, frames=3, band=band, track=t, fail_at=1, fail=fail, outs=outs)
+    order_run(lib, 0, 31, frames=3, band=band, fail_at=1, fail=fail, outs=want)
+    assert isinstance(outs[1], str) and outs[1].startswith("MIFX_ERR_HIP") and outs[1] == want[1], (outs[1], want[1])
+    calls = t.calls["MainThread"]
+    begin, fail, end = ([c[0] for c in calls].index(what) for what in ("the failing frame begins", f"launch {fail} (fails)", "the failing frame returns"))
+    main = f"s{t.ids['MainThread']['s', 0]}"
+    used = {a for c in calls[begin:fail] for a in c[1:] if str(a).startswith("s")} - {main}
+    assert len(used) == (3 if band else 1 if mode <= 2 else 2), (mode, band, used)
+    after = calls[fail + 1:end]
+    for lane in sorted(used):
+        events = [(i, c[1]) for i, c in enumerate(after) if c[0] == "record" and c[2] == lane]
+        assert any(("wait", main, e) in after[i + 1:] for i, e in events), f"overlap {mode}{', band' if band else ''}: after the failing launch, lane {lane} is not joined: {after}"
+    assert not t.findings, t.describe()[:6]
+    assert torch.equal(outs[2], want[2]) and torch.equal(outs[0], want[0]), f"overlap {mode}: frame 2 differs from the one-stream chain's after the same failure"
+    return len(used), len(after)
 
 
 def run_cpu_frame(cpu, chain_util, g, cam, prev, frame_index, ibl, sa, ssao_attribs):
@@ -451,6 +583,26 @@ def main():
             assert needed, f"overlap {mode}: no dropped wait was noticed -- the check sees nothing"
             print(f"cpu product: order control: overlap {mode}{', band' if band else ''}{', depth of field' if dof else ''}: of the {last[1] - last[0]} waits of a steady-state frame, dropping "
                   f"{len(needed)} leaves an unordered pair {needed}; {len(silent)} are implied by others or guard what this configuration does not touch {silent}", flush=True)
+    elif what == "trace":
+        # every stream / event call and launch of every frame path, per calling thread: diffed between two builds of the host code (a refactor keeps it identical)
+        for name, fn, check in trace_configurations(lib):
+            if len(sys.argv) > 2 and sys.argv[2] not in name:
+                continue
+            t = call_trace(check)
+            fn(t)
+            for thread in sorted(t.calls):
+                print(f"== {name} | {thread}: {len(t.calls[thread])} calls")
+                print("\n".join(" ".join(str(a) for a in c) for c in t.calls[thread]), flush=True)
+    elif what == "lane_errors":
+        for mode, band, fail in ((5, None, "taa"), (3, None, "taa"), (2, None, "taa"), (3, (16, 48), "taa"), (1, None, "postfx_prep"), (2, None, "postfx_prep")):
+            lanes, calls = lane_error(lib, mode, band, fail)
+            print(f"cpu product: lane error OK: overlap {mode}{', band' if band else ''}, {fail} fails: {lanes} lane(s) joined in the {calls} runtime calls after the failing launch; frame 2 ordered and equal", flush=True)
+    elif what == "auto_exposure":
+        # the auto-exposure handlers of device.py under mifx_chain_execute_sharded: three ranks, the luminance rows gathered, the five history planes exchanged at the end of
+        # the frame (MIFX_SHARD_ASYNC_HALOS=0) -- bands and histories equal the unsharded chain object's, whose average comes from the one-launch handler
+        os.environ["MIFX_SHARD_ASYNC_HALOS"] = "0"
+        local_group_case(lib, 1, auto_exposure=True)
+        print("cpu product: in-library group OK: auto exposure, synchronous halos", flush=True)
     elif what == "order_random":
         # the random chain sequences (sizes, frame indices, resets, flag sets, the fusion mask and the stream mode changing from frame to frame) under order.py: what the
         # library queues on the context's stream between frames -- history fills of a reset, re-allocations of a resize -- against the lanes of the frames around it

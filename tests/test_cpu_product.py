@@ -108,6 +108,22 @@ def test_the_order_of_the_lanes_has_no_unordered_pair(cpu_lib):
     assert "overlap 3, band: of the 7 waits of a steady-state frame, dropping 7 leaves an unordered pair" in out, out  # (the SSAO lane and the depth-hierarchy lane)
 
 
+def test_a_failing_launch_leaves_the_context_stream_behind_every_lane(cpu_lib):
+    """The error path of the lanes (mifx_objects.h LaneJoin): modes 5, 3 and 2 of mifx_chain_execute and mifx_chain_execute_band under three lanes, frames 0 - 2 at 96x64 under
+    order.py, the `taa` launch of frame 1 failing (the launch callback's return value is the launcher's status).  The execute returns that error; between the failing launch and
+    the return every lane the frame used gets an event record and the context's stream a wait for it; frame 2 has no unordered pair and equals frame 2 of a one-stream chain
+    object given the same failure (tests/cpu_product/run.py lane_error).  Modes 1 and 2 once more with the `postfx_prep` launch failing: on the side stream, between the fork
+    and the frame's own join through evPrep / evSsao -- the window in which the context's stream used to be left unordered."""
+    assert run(cpu_lib, "lane_errors").count("cpu product: lane error OK") == 6
+
+
+def test_auto_exposure_in_the_sharded_frame_on_the_cpu(cpu_lib):
+    """mifx_chain_execute_sharded with auto exposure on and the halos exchanged at the end of the frame (MIFX_SHARD_ASYNC_HALOS=0), three ranks of the in-library group: the
+    luminance rows of every band are gathered and reduced on every rank -- bands and history planes equal the unsharded chain object's, whose average luminance comes from
+    the one-launch path (tests/cpu_product/device.py: the low-resolution luminance is the reference's pass, the mip chain and the blend are restated there)."""
+    assert "cpu product: in-library group OK: auto exposure" in run(cpu_lib, "auto_exposure")
+
+
 def test_random_chain_sequences_keep_the_lanes_ordered(cpu_lib):
     """The random sequences of test_random_sequences_through_the_chain_object_on_the_cpu (sizes, frame indices, history resets, flag sets, the fusion mask and the stream mode
     changing from frame to frame) under order.py: the fills and re-allocations the library queues on the context's stream between frames against the lanes around them."""
