@@ -552,6 +552,105 @@ class ProcessSelection:
         return out
 
 
+OIT_SLICE_PLANES = ("depth", "base_color", "material", "radiance", "specular_ibl", "color_alpha")  # the members of mifx_oit_slice, in order
+OIT_TARGETS = ("color", "base_color", "material", "ibl")  # the members of mifx_oit_targets, in order
+
+
+class OITResources:
+    """== PBR_Renderer's OITResources (PBR_Renderer::CreateOITResources): K packed layers per pixel plus the tail, and the per-texel passes of the reference's layered
+    order-independent transparency over them (include/mifx.h, "layered order-independent transparency").  A transparent draw is a slice: a dict with the planes of
+    OIT_SLICE_PLANES (radiance / specular_ibl = what pbr_shade() returns for the slice's G-buffer; color_alpha optional; the layer entries read depth and base_color
+    only).  targets: a dict with the four planes of OIT_TARGETS, blended in place."""
+
+    def __init__(self, ctx: "PostFXContext", width, height, layer_count):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.width, self.height, self.layer_count = width, height, layer_count
+        self.handle = ctypes.c_void_p()
+        B.check(self.lib.mifx_oit_create(ctx.handle, ctypes.c_uint32(width), ctypes.c_uint32(height), ctypes.c_uint32(layer_count), ctypes.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            self.lib.mifx_oit_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _slices(slices):
+        imgs = [{k: B.image(s[k]) for k in OIT_SLICE_PLANES if s.get(k) is not None} for s in slices]  # (kept alive by the caller's frame)
+        arr = (B.OITSlice * max(len(slices), 1))(*[B.OITSlice(*[ctypes.pointer(m[k]) if k in m else None for k in OIT_SLICE_PLANES]) for m in imgs])
+        return arr, imgs
+
+    @staticmethod
+    def _targets(targets):
+        imgs = [B.image(targets[k]) for k in OIT_TARGETS]
+        return B.OITTargets(*[ctypes.pointer(i) for i in imgs]), imgs
+
+    def clear_layers(self):
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_clear_layers(self.handle))
+
+    def update_layers(self, slice_, camera: B.CameraAttribs, opaque_depth=None):
+        arr, keep = self._slices([slice_])
+        od = B.image(opaque_depth) if opaque_depth is not None else None
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_update_layers(self.handle, arr, ctypes.byref(od) if od is not None else None, ctypes.byref(camera)))
+
+    def apply_attenuation(self, targets):
+        t, keep = self._targets(targets)
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_apply_attenuation(self.handle, ctypes.byref(t)))
+
+    def blend(self, slice_, camera: B.CameraAttribs, targets, opaque_depth=None):
+        arr, keep = self._slices([slice_])
+        t, keep_t = self._targets(targets)
+        od = B.image(opaque_depth) if opaque_depth is not None else None
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_blend(self.handle, arr, ctypes.byref(od) if od is not None else None, ctypes.byref(camera), ctypes.byref(t)))
+
+    def build_layers(self, slices, camera: B.CameraAttribs, opaque_depth=None):
+        arr, keep = self._slices(slices)
+        od = B.image(opaque_depth) if opaque_depth is not None else None
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_build_layers(self.handle, arr, ctypes.c_uint32(len(slices)), ctypes.byref(od) if od is not None else None, ctypes.byref(camera)))
+
+    def resolve(self, slices, camera: B.CameraAttribs, targets, opaque_depth=None):
+        arr, keep = self._slices(slices)
+        t, keep_t = self._targets(targets)
+        od = B.image(opaque_depth) if opaque_depth is not None else None
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_resolve(self.handle, arr, ctypes.c_uint32(len(slices)), ctypes.byref(od) if od is not None else None, ctypes.byref(camera), ctypes.byref(t)))
+
+    def render(self, slices, targets, camera: B.CameraAttribs, opaque_depth=None):
+        """HnBeginOITPassTask -> the transparent draws -> HnEndOITPassTask for up to binding.OIT_MAX_SLICES slices: build_layers, then resolve (the fused kernels, or the
+        reference's sequence of launches: mifx_oit_set_fusion).  The targets are blended in place and returned."""
+        self.build_layers(slices, camera, opaque_depth)
+        self.resolve(slices, camera, targets, opaque_depth)
+        return targets
+
+    def get_layers(self):
+        """The layers buffer as an int32 view (height, width, layer_count) of the uint32 words, valid until close()."""
+        data, words = ctypes.c_void_p(), ctypes.c_uint64()
+        B.check(self.lib.mifx_oit_get_layers(self.handle, ctypes.byref(data), ctypes.byref(words)))
+
+        class _Holder:  # __cuda_array_interface__ provider
+            pass
+
+        h = _Holder()
+        h.__cuda_array_interface__ = {"shape": (words.value,), "typestr": "<i4", "data": (data.value, False), "version": 2}
+        return torch.as_tensor(h, device=self.ctx.device).view(self.height, self.width, self.layer_count)
+
+    def get_tail(self):
+        """The tail plane (height, width, 2): the count in steps of 1 / 255, the transmittance product"""
+        d = B.Image2D()
+        B.check(self.lib.mifx_oit_get_tail(self.handle, ctypes.byref(d)))
+        return _view(d, self.ctx.device)
+
+
 def _export_history(fx, channel_shapes):
     """mifx_<effect>_export_history into fresh tensors of the prepared size; returns (*planes, frame_index)."""
     # (a plane of the prepared size; not the SSR output: inside a chain that plane may be deferred, mifx_ssr_run_deferred_cleanup)

@@ -335,6 +335,17 @@ def filterable_shadow_map(t) -> FilterableShadowMap:
     return FilterableShadowMap(t.data_ptr(), t.shape[2], t.shape[1], t.shape[0], FORMAT_F32X2 if t.shape[3] == 2 else FORMAT_F32X4, t.stride(1) * 4, t.stride(0) * 4)
 
 
+OIT_MAX_SLICES, OIT_MAX_LAYERS = 32, 16  # MIFX_OIT_MAX_SLICES, MIFX_OIT_MAX_LAYERS
+
+
+class OITSlice(ctypes.Structure):  # mifx_oit_slice: one transparent draw
+    _fields_ = [("depth", PImage), ("base_color", PImage), ("material", PImage), ("radiance", PImage), ("specular_ibl", PImage), ("color_alpha", PImage)]
+
+
+class OITTargets(ctypes.Structure):  # mifx_oit_targets: blended in place
+    _fields_ = [("color", PImage), ("base_color", PImage), ("material", PImage), ("ibl", PImage)]
+
+
 class ChainFrame(ctypes.Structure):
     _fields_ = [("frame", FrameDesc), ("gbuffer", GBuffer), ("motion", PImage), ("prev_depth", PImage),
                 ("curr_camera", ctypes.POINTER(CameraAttribs)), ("prev_camera", ctypes.POINTER(CameraAttribs)),
@@ -371,7 +382,29 @@ def load():
         _lib.mifx_abi_version.restype = c_u
         _lib.mifx_storage_mode.restype = c_u
         assert bool(_lib.mifx_storage_mode()) == STORAGE_H4 or os.environ.get("MIFX_LIB_PATH"), "the loaded library is not the storage build MIFX_STORAGE asks for"
+        if hasattr(_lib, "mifx_oit_create"):  # (an alternative build of the host objects alone, MIFX_LIB_PATH, has no OIT entries: they live beside their kernels)
+            _declare_oit(_lib)
     return _lib
+
+
+def _declare_oit(lib):
+    """Prototypes of the order-independent-transparency entries (include/mifx.h)"""
+    PS, PT, PC, u = ctypes.POINTER(OITSlice), ctypes.POINTER(OITTargets), ctypes.POINTER(CameraAttribs), c_u
+    lib.mifx_oit_create.argtypes = [c_p, u, u, u, ctypes.POINTER(c_p)]
+    lib.mifx_oit_destroy.argtypes, lib.mifx_oit_destroy.restype = [c_p], None
+    lib.mifx_oit_clear_layers.argtypes = [c_p]
+    lib.mifx_oit_update_layers.argtypes = [c_p, PS, PImage, PC]
+    lib.mifx_oit_apply_attenuation.argtypes = [c_p, PT]
+    lib.mifx_oit_blend.argtypes = [c_p, PS, PImage, PC, PT]
+    lib.mifx_oit_build_layers.argtypes = [c_p, PS, u, PImage, PC]
+    lib.mifx_oit_resolve.argtypes = [c_p, PS, u, PImage, PC, PT]
+    lib.mifx_oit_get_layers.argtypes = [c_p, ctypes.POINTER(c_p), ctypes.POINTER(ctypes.c_uint64)]
+    lib.mifx_oit_get_tail.argtypes = [c_p, PImage]
+    lib.mifx_oit_set_fusion.argtypes, lib.mifx_oit_set_fusion.restype = [c_i], c_i
+    lib.mifx_oit_create_check.argtypes = [u, u, u]
+    lib.mifx_oit_frame_check.argtypes = [u, u, PS, u, PImage, PC, PT]
+    for name in ("create", "clear_layers", "update_layers", "apply_attenuation", "blend", "build_layers", "resolve", "get_layers", "get_tail", "create_check", "frame_check"):
+        getattr(lib, "mifx_oit_" + name).restype = c_i
 
 
 def device_code_sha16(path=None):
@@ -432,7 +465,7 @@ class CommStats(ctypes.Structure):  # mifx_comm_stats
                 ("timed_groups", ctypes.c_uint32), ("exchange_ms_total", ctypes.c_float), ("exchange_ms_max", ctypes.c_float)]
 
 
-SIZEOF_NAMES.update({"shard_info": ShardInfo, "comm_stats": CommStats})
+SIZEOF_NAMES.update({"shard_info": ShardInfo, "comm_stats": CommStats, "oit_slice": OITSlice, "oit_targets": OITTargets})
 
 
 class MifxError(RuntimeError):

@@ -248,6 +248,8 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("ibl", mifx_ibl);
     MIFX_SZ("shard_info", mifx_shard_info);
     MIFX_SZ("comm_stats", mifx_comm_stats);
+    MIFX_SZ("oit_slice", mifx_oit_slice);
+    MIFX_SZ("oit_targets", mifx_oit_targets);
 #undef MIFX_SZ
     return 0;
 }

@@ -955,6 +955,83 @@ MIFX_API mifx_status mifx_shadow_map_filter(mifx_postfx* ctx, const mifx_image2d
                                             const mifx_shadow_filter_params* params, const mifx_shadow_map_array* shadow_map,
                                             const mifx_filterable_shadow_map* filterable_map, const mifx_image2d* out_light_amount, const mifx_image2d* out_cascade);
 
+/* ------------------------------------------------------------------------------------------------ layered order-independent transparency (PBR_Renderer OIT, Shaders/Common/public/OIT.fxh) */
+/* The per-texel half of the reference's layered OIT (PBR_Renderer::CreateInfo::OITLayerCount, PBR/interface/PBR_Renderer.hpp:250-252; Hydrogent's HnBeginOITPassTask ->
+ * transparent draws -> HnEndOITPassTask): K packed (24-bit depth, 8-bit transmittance) layers per pixel plus a tail, the attenuation of the opaque background and the
+ * additive blend of the transparent surfaces into the four targets the post-process chain consumes (Color, BaseColor, Material, IBL: HnEndOITPassTask.cpp:68-79).
+ * A transparent DRAW is a SLICE: full-frame planes with at most one fragment per pixel (a mesh that overlaps itself is two slices).  Slices are applied in submission
+ * order and pixels never interact, so the results are deterministic; the reference's InterlockedMin loop (UpdateOITLayers.psh:78-92) becomes a serial chain over the
+ * pixel's K words with the same outcome.  A slice is shaded with the existing mifx_pbr_shade_execute* entries, unchanged.
+ * Conventions pinned here:
+ *   - coverage: a pixel of a slice has a fragment iff its depth FAILS the shade's background test (depth >= 1 - 1e-6; with reversed depth, depth < 1e-6: what
+ *     mifx_pbr_shade_execute writes `background` for).  Reversed depth is camera->fNearPlaneDepth > camera->fFarPlaneDepth, the reference's own test;
+ *   - depth test (UpdateOITLayers.psh:57-62; the hardware's test in the colour pass): with S = +1 where fNearPlaneDepth < fFarPlaneDepth and -1 otherwise, the fragment
+ *     is dropped where D * S >= opaque * S.  opaque_depth may be NULL: no test;
+ *   - reversed depth: D = 1 - D before it is packed or compared (UpdateOITLayers.psh:64-67, RenderPBR.psh:552-555);
+ *   - tail: two fp32 values per pixel (F32X2): x = the count, accumulated as repeated + 1.0 / 255.0, y = the transmittance product.  Not quantised to RGBA8_UNORM
+ *     (USD_Renderer::OITTailFmt) and not saturated at 255 layers, like every other plane of the fp32 build;
+ *   - a blend is dst = src * sf + dst * df, evaluated in fp32 in that order;
+ *   - the attenuation discards where the total transmittance == 1.0: the texel is left untouched.  A fragment with base_color.a <= OIT_OPACITY_THRESHOLD (1 / 255)
+ *     inserts nothing and still blends, with transmittance 1 (RenderPBR.psh:544-559).
+ * Identity at their defaults and not modelled: highlight colour, loading animation, in-shader tone mapping, debug views (RenderPBR.psh:530-630). */
+#define MIFX_OIT_MAX_SLICES 32 /* slices per mifx_oit_build_layers / mifx_oit_resolve call (the kernels' argument table); more draws go through update_layers / blend, whose layers persist */
+#define MIFX_OIT_MAX_LAYERS 16
+typedef struct mifx_oit_slice
+{
+    const mifx_image2d* depth;        /* F32: the fragment's SV_Position.z; a pixel without a fragment holds the shade's background value                     */
+    const mifx_image2d* base_color;   /* F32X4: GetBaseColor: rgb, a = opacity                                 (the layer entries read .a only)               */
+    const mifx_image2d* material;     /* F32X4: xy = MaterialData of the USD footer (USD_Renderer.cpp:98)      (colour entries; may be NULL for the layer entries) */
+    const mifx_image2d* radiance;     /* F32X4: out_radiance of mifx_pbr_shade_execute* run on this slice's G-buffer                         (colour entries) */
+    const mifx_image2d* specular_ibl; /* F32X4: out_specular_ibl of the same call                                                            (colour entries) */
+    const mifx_image2d* color_alpha;  /* F32 or NULL: OutColor.a; NULL = base_color.a; 1 - Transmission with ENABLE_TRANSMISSION (RenderPBR.psh:515-523)      */
+} mifx_oit_slice;
+typedef struct mifx_oit_targets /* F32X4, blended in place */
+{
+    const mifx_image2d* color;
+    const mifx_image2d* base_color;
+    const mifx_image2d* material;
+    const mifx_image2d* ibl;
+} mifx_oit_targets;
+typedef struct mifx_oit mifx_oit;
+/* PBR_Renderer::CreateOITResources (PBR/src/PBR_Renderer.cpp, OITResources: Layers = width * height * layer_count uint32, Tail).  layer_count 1 .. MIFX_OIT_MAX_LAYERS,
+ * width and height 1 .. 16384.  The layers and the tail are NOT cleared.  MIFX_ERR_NOT_IMPLEMENTED in the native-storage build of the library (every entry below,
+ * after the same argument checks). */
+MIFX_API mifx_status mifx_oit_create(mifx_postfx* ctx, uint32_t width, uint32_t height, uint32_t layer_count, mifx_oit** out);
+MIFX_API void        mifx_oit_destroy(mifx_oit* oit);
+/* The reference's sequence, one launch each (kernel-timing names "oit_clear_kernel", "oit_update_kernel", "oit_attenuate_kernel", "oit_blend_kernel").
+ * clear_layers:      ClearOITLayers.csh (every word 0xFFFFFFFF) and the tail's clear value (count 0, transmittance 1: HnBeginOITPassTask.cpp:139-144).
+ * update_layers:     one draw of UpdateOITLayers.psh:54-109 with BS_UpdateOITTail (PBR_Renderer.cpp:1849-1865); reads slice->depth and slice->base_color.a.
+ *                    The layers persist from call to call: any number of draws, in any number of calls, between a clear and the attenuation.
+ * apply_attenuation: ApplyOITAttenuation.psh with BS_OITAttenuation (PBR_Renderer.cpp:2309-2324) on the four targets.
+ * blend:             one transparent draw of the colour pass: GetOITTransmittance (RenderPBR.psh:388-418), OutColor.rgb *= BaseColor.a (:547), *= Transmittance (:632),
+ *                    the USD footer (USD_Renderer.cpp:122-167) and the blend state rgb One / One, alpha One / InvSrcAlpha (PBR_Renderer.cpp:2096-2127). */
+MIFX_API mifx_status mifx_oit_clear_layers(mifx_oit* oit);
+MIFX_API mifx_status mifx_oit_update_layers(mifx_oit* oit, const mifx_oit_slice* slice, const mifx_image2d* opaque_depth, const mifx_camera_attribs* camera);
+MIFX_API mifx_status mifx_oit_apply_attenuation(mifx_oit* oit, const mifx_oit_targets* targets);
+MIFX_API mifx_status mifx_oit_blend(mifx_oit* oit, const mifx_oit_slice* slice, const mifx_image2d* opaque_depth, const mifx_camera_attribs* camera, const mifx_oit_targets* targets);
+/* The same over `count` <= MIFX_OIT_MAX_SLICES slices in submission order, one launch each ("oit_build_kernel", "oit_resolve_kernel"):
+ * build_layers = clear_layers, then update_layers of every slice (the K words stay in registers; the layers buffer is written once and never read);
+ * resolve      = apply_attenuation, then blend of every slice (the layers, the tail and each target are read once, each target is written once; a pixel that
+ *                nothing touches is not written).
+ * Bit-identical to the sequence, which they become for a layer count without a fused kernel (one exists for 1, 2, 3, 4 and 8) and with mifx_oit_set_fusion(0).
+ * count == 0 is allowed (build: the clear; resolve: nothing changes). */
+MIFX_API mifx_status mifx_oit_build_layers(mifx_oit* oit, const mifx_oit_slice* slices, uint32_t count, const mifx_image2d* opaque_depth, const mifx_camera_attribs* camera);
+MIFX_API mifx_status mifx_oit_resolve(mifx_oit* oit, const mifx_oit_slice* slices, uint32_t count, const mifx_image2d* opaque_depth, const mifx_camera_attribs* camera,
+                                      const mifx_oit_targets* targets);
+/* The object's buffers (device memory, valid until mifx_oit_destroy): width * height * layer_count uint32 words, pixel (x, y) at (y * width + x) * layer_count
+ * (GetOITLayerDataOffset, OIT.fxh:20); the tail plane, MIFX_FORMAT_F32X2. */
+MIFX_API mifx_status mifx_oit_get_layers(mifx_oit* oit, void** out_data, uint64_t* out_words);
+MIFX_API mifx_status mifx_oit_get_tail(mifx_oit* oit, mifx_image2d* out);
+/* Internal A/B switch of build_layers / resolve: 1 = the fused kernels, 0 = the sequence; returns the previous value.  Default 1: the fused kernels are 2.0 - 3.3 times
+ * faster at 3840 x 2160, K = 4, L = 2 .. 8 (profiles/oit_bench.json, tools/oit_bench.py). */
+MIFX_API int32_t mifx_oit_set_fusion(int32_t enable);
+/* The argument checks alone -- no context, no device, nothing read but the descriptors and the camera.  create_check: those of mifx_oit_create.  frame_check: those
+ * of every other entry for an object of width x height: `targets` NULL = the layer entries (update_layers / build_layers: a slice needs depth and base_color),
+ * otherwise the colour entries (blend / resolve: every plane but color_alpha); `slices` may be NULL with count 0 (apply_attenuation). */
+MIFX_API mifx_status mifx_oit_create_check(uint32_t width, uint32_t height, uint32_t layer_count);
+MIFX_API mifx_status mifx_oit_frame_check(uint32_t width, uint32_t height, const mifx_oit_slice* slices, uint32_t count, const mifx_image2d* opaque_depth,
+                                          const mifx_camera_attribs* camera, const mifx_oit_targets* targets);
+
 /* ------------------------------------------------------------------------------------------------ whole chain (the caller: HnPostProcessTask::Execute, Hydrogent/src/Tasks/HnPostProcessTask.cpp:743-948) */
 typedef struct mifx_autoexposure mifx_autoexposure; /* auto exposure, declared below */
 typedef struct mifx_chain mifx_chain;
