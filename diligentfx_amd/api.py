@@ -744,6 +744,18 @@ class ScreenSpaceReflection(_Effect):
     def get_ssr_radiance(self):
         return self._output()
 
+    def set_clean_tiles(self, enable):
+        """Test hook (mifx_debug_ssr_set_clean_tiles): R4 clears its targets only where an 8x8 tile needs it (default) or every texel outside the mask every frame."""
+        B.check(self.lib.mifx_debug_ssr_set_clean_tiles(self.handle, ctypes.c_int32(1 if enable else 0)))
+
+    def get_tile_flags(self):
+        """(flags as an int array (tiles_y, tiles_x): 0 = the tile holds the cleared values in both ray planes, valid) (mifx_debug_ssr_get_tile_flags)."""
+        tx, ty, valid = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int32(0)
+        B.check(self.lib.mifx_debug_ssr_get_tile_flags(self.handle, None, ctypes.c_uint32(0), ctypes.byref(tx), ctypes.byref(ty), ctypes.byref(valid)))
+        buf = (ctypes.c_uint32 * (tx.value * ty.value))()
+        B.check(self.lib.mifx_debug_ssr_get_tile_flags(self.handle, buf, ctypes.c_uint32(len(buf)), ctypes.byref(tx), ctypes.byref(ty), ctypes.byref(valid)))
+        return torch.tensor(list(buf), dtype=torch.int64).reshape(ty.value, tx.value), bool(valid.value)
+
     def export_history(self):
         """(accumulated radiance, variance, frame index) (mifx_ssr_export_history)."""
         return _export_history(self, (((4,), "colour"), ((), "variance")))

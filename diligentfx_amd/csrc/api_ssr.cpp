@@ -34,9 +34,43 @@ mifx_status mifx_ssr_create(mifx_postfx* ctx, mifx_ssr** out)
     *out        = new mifx_ssr();
     (*out)->ctx = ctx;
     if (const char* e = std::getenv("MIFX_SSR_DIRECT_LEVEL0")) (*out)->direct_level0 = std::atoi(e) < 0 ? -1 : std::atoi(e) > 0 ? 1 : 0; // (A/B runs; default -1: row bands only)
+    if (const char* e = std::getenv("MIFX_SSR_CLEAN_TILES")) (*out)->clean_tiles = std::atoi(e) != 0; // (A/B runs; read here once, never per frame)
+#if defined(MIFX_R4_TWO_RAYS) && MIFX_R4_TWO_RAYS
+    (*out)->clean_tiles = false; // the two-rays-per-lane experiment kernel (ssr_trace.hip) always clears
+#endif
     return MIFX_OK;
 }
 void mifx_ssr_destroy(mifx_ssr* fx) { delete fx; }
+
+mifx_status mifx_debug_ssr_set_clean_tiles(mifx_ssr* fx, int32_t enable)
+{
+    MIFX_REQUIRE(fx != nullptr, "mifx_debug_ssr_set_clean_tiles: null argument");
+#if defined(MIFX_R4_TWO_RAYS) && MIFX_R4_TWO_RAYS
+    enable = 0;
+#endif
+    // (the words go stale while the march always clears: the next launch that uses them rebuilds them)
+    fx->clean_tiles      = enable != 0;
+    fx->tile_flags_valid = false;
+    return MIFX_OK;
+}
+
+mifx_status mifx_debug_ssr_get_tile_flags(mifx_ssr* fx, uint32_t* out, uint32_t capacity, uint32_t* out_tiles_x, uint32_t* out_tiles_y, int32_t* out_valid)
+{
+    MIFX_REQUIRE(fx != nullptr && out_tiles_x != nullptr && out_tiles_y != nullptr && out_valid != nullptr, "mifx_debug_ssr_get_tile_flags: null argument");
+    if (!fx->prepared)
+    {
+        set_error("mifx_debug_ssr_get_tile_flags: resources are not prepared");
+        return MIFX_ERR_INVALID_OP;
+    }
+    const uint32_t tx = r4_tiles_x(fx->ray_radiance.w), n = r4_tile_count(fx->ray_radiance.w, fx->ray_radiance.h);
+    *out_tiles_x = tx; *out_tiles_y = n / tx; *out_valid = fx->tile_flags_valid ? 1 : 0;
+    if (out == nullptr) return MIFX_OK; // the size only
+    MIFX_REQUIRE(capacity >= n, "mifx_debug_ssr_get_tile_flags: room for %u words, %u tiles", capacity, n);
+    MIFX_HIP_CHECK(hipSetDevice(fx->ctx->device));
+    MIFX_HIP_CHECK(hipStreamSynchronize(fx->ctx->stream));
+    MIFX_HIP_CHECK(hipMemcpy(out, fx->tile_flags.data, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MIFX_OK;
+}
 
 static mifx_status clear_history(mifx_ssr* fx)
 {
@@ -96,6 +130,12 @@ mifx_status mifx_ssr_prepare(mifx_ssr* fx, mifx_postfx* ctx, uint32_t feature_fl
     MIFX_CHECK(fx->output.alloc(W, H, MIFX_FORMAT_F32X4));
     fx->w = W; fx->h = H; fx->flags = feature_flags;
     MIFX_CHECK(clear_history(fx));
+    // R4's clean-tile words, with the ray planes.  New device memory holds anything, so the words start out not valid (the first whole-plane march writes every texel and
+    // rebuilds them); they are zeroed all the same, for whoever reads them before that (mifx_debug_ssr_get_tile_flags).
+    const size_t flagBytes = size_t(r4_tile_count(RW, RH)) * sizeof(uint32_t);
+    MIFX_CHECK(fx->tile_flags.reserve(flagBytes));
+    MIFX_HIP_CHECK(hipMemsetAsync(fx->tile_flags.data, 0, flagBytes, ctx->stream));
+    fx->tile_flags_valid = false;
     fx->last_frame = ~0u;
     fx->prepared   = true;
     return MIFX_OK;
@@ -217,9 +257,17 @@ mifx_status mifx_ssr::run(const mifx_ssr_render_attribs* ra, const Request& req)
             MIFX_CHECK(fx->hit_coords.alloc(fx->ray_radiance.w, fx->ray_radiance.h, MIFX_FORMAT_F32));
             coords = fx->hit_coords.view();
         }
-        MIFX_CHECK(launch_ssr_intersection(s, color, normal, fx->roughness.view(), ctx->noise_xy.view(), slab, half ? fx->mask_half.view() : fx->mask.view(), motion,
-                                           win(fx->ray_radiance.view(), half ? h4 : w4), fx->ray_dir_pdf.view(), cur, a,
-                                           (fx->flags & MIFX_SSR_FEATURE_FLAG_PREVIOUS_FRAME) != 0, half, coords, req.hit_local_rows.b, req.hit_local_rows.e));
+        // Clean tiles: a march over the whole plane trusts the words if they describe the planes and rebuilds them if not; a row window (whose tile grid starts at its
+        // first row) and the sharded frame (whose hit fetch writes the ray planes behind the march) always clear and leave the words stale.
+        const Img  rays  = win(fx->ray_radiance.view(), half ? h4 : w4);
+        const bool whole = rays.y0 == 0 && window_rows(rays) == rays.h && !req.after_trace;
+        slab.clearMode = !whole || !fx->clean_tiles ? kR4ClearAlways : fx->tile_flags_valid ? kR4ClearTrust : kR4ClearRebuild;
+        slab.tileFlags = static_cast<uint32_t*>(fx->tile_flags.data);
+        fx->tile_flags_valid = false; // (until the launch is queued)
+        MIFX_CHECK(launch_ssr_intersection(s, color, normal, fx->roughness.view(), ctx->noise_xy.view(), slab, half ? fx->mask_half.view() : fx->mask.view(), motion, rays,
+                                           fx->ray_dir_pdf.view(), cur, a, (fx->flags & MIFX_SSR_FEATURE_FLAG_PREVIOUS_FRAME) != 0, half, coords, req.hit_local_rows.b,
+                                           req.hit_local_rows.e));
+        fx->tile_flags_valid = slab.clearMode != kR4ClearAlways;
     }
     if (req.after_trace) MIFX_CHECK(req.after_trace(win(fx->ray_radiance.view(), half ? h4 : w4), fx->hit_coords.view()));
     // R5

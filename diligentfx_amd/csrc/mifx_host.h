@@ -166,7 +166,15 @@ struct HizSlab
     // pitch[0] the plane's own pitch).  The copy is 86 % of the hierarchy pass' bytes; a row band of a sharded frame builds the WHOLE hierarchy on every rank.
     const unsigned char* base0;
     uint32_t             bytes0;
+    // The march clears its two targets only where a tile needs it (ssr_trace.hip "clean tiles"): one 32-bit word per 8 x 8 tile of the ray planes,
+    // 0 = every texel of the tile holds the cleared values.  clearMode: kR4ClearAlways / Rebuild / Trust.  (The two ride in this block -- the march's by-value
+    // argument block -- so that the launcher keeps its argument list.)
+    uint32_t  clearMode;
+    uint32_t* tileFlags;
 };
+enum : uint32_t { kR4ClearAlways = 0, kR4ClearRebuild = 1, kR4ClearTrust = 2 };
+inline uint32_t r4_tiles_x(uint32_t w) { return (w + 7u) / 8u; }
+inline uint32_t r4_tile_count(uint32_t w, uint32_t h) { return r4_tiles_x(w) * ((h + 7u) / 8u); }
 
 // grow-only device buffer for per-call working data (stream-ordered reuse; growing frees the old block, which waits for the device)
 struct DeviceScratch

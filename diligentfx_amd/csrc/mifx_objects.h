@@ -203,6 +203,13 @@ struct mifx_ssr
         return mifx::rows_hull(w4, mifx::rows_clip(mifx::Rows{2 * h4.b, 2 * h4.e + 1}, H));
     }
     mifx::Plane ray_radiance, ray_dir_pdf;                 // R4
+    // R4 clears its targets only where a tile needs it (ssr_trace.hip "clean tiles"): one word per 8 x 8 tile of the ray planes, 0 = the tile holds the cleared values.
+    // tile_flags_valid: the words describe the planes -- true after a whole-plane launch that wrote them (rebuild or trust), false once anything else has written the
+    // planes (a row-window launch, the sharded hit fetch) or they are new (fresh device memory holds anything): the next whole-plane launch then rebuilds the words while
+    // it clears as before.  clean_tiles = false: always clear, the words are not touched (mifx_debug_ssr_set_clean_tiles, MIFX_SSR_CLEAN_TILES=0; A/B runs and tests).
+    mifx::DeviceScratch tile_flags;
+    bool                tile_flags_valid = false;
+    bool                clean_tiles      = true;
     mifx::Plane res_radiance, res_variance, res_depth;     // R5
     mifx::Plane hist_radiance[2], hist_variance[2];        // R6 ping-pong
     mifx::Plane output;                                    // R7

@@ -260,6 +260,16 @@ __global__ __launch_bounds__(256) MIFX_R4_OCC MIFX_R4_SGPR_CAP void ssr_intersec
     int x, y;
     const bool  inImage   = tiled_xy_xcd(outSpec, x, y);
     const float maskValue = ld<mask_t>(mask, min(x, outSpec.w - 1), min(y, row_end(outSpec) - 1));
+    // Clean tiles.  A wave is one 8 x 8 tile of the ray planes and owns one word of hizSlab.tileFlags: 0 = every texel of the tile (inside the plane)
+    // holds the cleared values in both targets -- one way only, a set word over a clean tile is allowed.  A texel outside the mask is cleared to 0 every frame by the
+    // reference, and a tile that lies outside the mask now nearly always did so the frame before: under kR4ClearTrust a wave with no texel inside the mask whose word
+    // is 0 stores nothing (32 B per texel of zeros over zeros).  The word is requested with the mask (one round trip for both), read and written by this wave alone,
+    // launches on these planes are ordered on one stream: plain loads and stores.  Whole-plane launches only (api_ssr.cpp: the tile grid starts at the window's first row).
+    const unsigned clearMode   = hizSlab.clearMode;
+    const bool     tileInImage = (x & ~7) < outSpec.w; // wave-uniform; the grid's rows always reach into the window
+    const unsigned tile        = blockIdx.y * unsigned((outSpec.w + 7) >> 3) + unsigned(x >> 3);
+    unsigned       tileFlag    = 1u;
+    if (clearMode == kR4ClearTrust && tileInImage) tileFlag = *(const MIFX_GLOBAL unsigned*)(hizSlab.tileFlags + tile);
     if (threadIdx.x < unsigned(SSR_MAX_MIP + 2))
     {
         const unsigned m = threadIdx.x == 0u ? 0u : threadIdx.x - 1u; // entry 0 = a second copy of level 0
@@ -270,11 +280,23 @@ __global__ __launch_bounds__(256) MIFX_R4_OCC MIFX_R4_SGPR_CAP void ssr_intersec
     __syncthreads();
     const HizLds hiz{__builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(hizSlab.base), 0, int(hizSlab.bytes), 0x00020000), hizLv,
                      __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(DIRECT0 ? hizSlab.base0 : hizSlab.base), 0, int(DIRECT0 ? hizSlab.bytes0 : hizSlab.bytes), 0x00020000)};
+    bool skipClear = false;
+    if (clearMode != kR4ClearAlways)
+    {
+        const bool any   = __ballot(inImage && maskValue != 0.0f) != 0ull; // (the threads outside the image take no part: an edge tile is the tile within the image)
+        const bool dirty = __builtin_amdgcn_readfirstlane(int(tileFlag)) != 0;
+        skipClear        = clearMode == kR4ClearTrust && !any && !dirty;
+        // rebuild: the exact word, whatever was there; trust: the word only where it changes (0 -> 1 before this wave's rays are stored, 1 -> 0 with the zeros below)
+        if (tileInImage && (clearMode == kR4ClearRebuild || any != dirty) && (threadIdx.x & 63u) == 0u) *(MIFX_GLOBAL unsigned*)(hizSlab.tileFlags + tile) = any ? 1u : 0u;
+    }
     if (!inImage) return;
     if (maskValue == 0.0f)
     {
-        st<v4>(outSpec, x, y, mk4(0.0f)); // both targets are cleared to 0 (ScreenSpaceReflection.cpp:993-994)
-        st<v4>(outDirPdf, x, y, mk4(0.0f));
+        if (!skipClear)
+        {
+            st<v4>(outSpec, x, y, mk4(0.0f)); // both targets are cleared to 0 (ScreenSpaceReflection.cpp:993-994)
+            st<v4>(outDirPdf, x, y, mk4(0.0f));
+        }
         if (hitCoords.p != nullptr) st<float>(hitCoords, x, y, __uint_as_float(0xffffffffu));
         return;
     }

@@ -415,6 +415,13 @@ MIFX_API mifx_status mifx_ssr_import_history(mifx_ssr* fx, const mifx_image2d* r
 /* Names: "hiz<1..6>", "roughness", "mask", "ray_radiance", "ray_dir_pdf", "res_radiance", "res_variance", "res_depth",
  * "hist_radiance", "hist_variance" (current slot). */
 MIFX_API mifx_status mifx_ssr_get_intermediate(mifx_ssr* fx, const char* name, mifx_image2d* out);
+/* Test hook: the ray march (R4) clears its two targets only where an 8 x 8 tile needs it (default; one word per tile says whether the tile already holds the cleared values)
+ * or stores the zeros of every texel outside the reflection mask every frame, as the reference's per-frame clear does; every texel of "ray_radiance" / "ray_dir_pdf" gets
+ * the same bits either way.  Default from MIFX_SSR_CLEAN_TILES (0 = off), read when the object is created. */
+MIFX_API mifx_status mifx_debug_ssr_set_clean_tiles(mifx_ssr* fx, int32_t enable);
+/* The tile words (row-major, *out_tiles_x per row; 0 = every texel of the tile holds 0 in both ray targets) after everything queued so far; *out_valid = the next
+ * whole-plane march will trust them.  out == NULL: the geometry only. */
+MIFX_API mifx_status mifx_debug_ssr_get_tile_flags(mifx_ssr* fx, uint32_t* out, uint32_t capacity, uint32_t* out_tiles_x, uint32_t* out_tiles_y, int32_t* out_valid);
 
 /* ------------------------------------------------------------------------------------------------ TemporalAntiAliasing */
 typedef struct mifx_taa mifx_taa; /* TemporalAntiAliasing.hpp:60-214 */
