@@ -830,6 +830,10 @@ class TemporalAntiAliasing(_Effect):
     def import_history(self, color, frame_index):
         _import_history(self, (color,), frame_index)
 
+    def set_history_skip(self, enable):
+        """Test hook (mifx_debug_taa_set_history_skip): pixels whose history weight is exactly zero store their current colour without fetching the history (default) or run the whole body."""
+        B.check(self.lib.mifx_debug_taa_set_history_skip(self.handle, ctypes.c_int32(1 if enable else 0)))
+
     @staticmethod
     def get_jitter_offset(frame_index, width, height):
         out = (ctypes.c_float * 2)()

@@ -293,6 +293,13 @@ mifx_status mifx_taa_reset_history(mifx_taa* fx)
     return MIFX_OK;
 }
 
+mifx_status mifx_debug_taa_set_history_skip(mifx_taa* fx, int32_t enable)
+{
+    MIFX_REQUIRE(fx != nullptr, "mifx_debug_taa_set_history_skip: null argument");
+    fx->history_skip = enable != 0;
+    return MIFX_OK;
+}
+
 // TemporalAntiAliasing::Execute (TemporalAntiAliasing.cpp:169-201, ComputeTemporalAccumulation :260-300)
 mifx_status mifx_taa_execute(mifx_taa* fx, const mifx_taa_render_attribs* ra)
 {
@@ -339,7 +346,7 @@ mifx_status mifx_taa::run(const mifx_taa_render_attribs* ra, const mifx::TaaFuse
         MifxKernelTimer timer(ctx, "taa_kernel");
         MIFX_CHECK(launch_taa(ctx->stream, color, fx->accum[pi].view(), ctx->closest_motion.view(), ctx->reproj_depth.view(), prevDepth,
                               win(fx->accum[ci].view(), ctx->needed_rows(int(fx->h))),
-                              make_camk(ctx->curr_cam), make_camk(ctx->prev_cam), a, fx->flags, fused));
+                              make_camk(ctx->curr_cam), make_camk(ctx->prev_cam), a, fx->flags | (fx->history_skip ? 0u : kTaaFullBodyEverywhere), fused));
     }
     return reset ? MIFX_NO_HISTORY : MIFX_OK;
 }

@@ -323,6 +323,9 @@ struct TaaFusedComposite
     const mifx_composite_attribs* attribs; // as for launch_composite (its `ssr` plane is not read: the cleanup is evaluated in place)
     const SsrCleanupIn*           r7;
 };
+// flags: MIFX_TAA_FEATURE_FLAG_* in bits 0 - 2; kTaaFullBodyEverywhere on top runs the whole body for pixels whose history weight is exactly zero as well
+// (mifx_debug_taa_set_history_skip 0; taa.hip "history skip")
+constexpr uint32_t kTaaFullBodyEverywhere = 1u << 31;
 mifx_status launch_taa(hipStream_t s, Img currColor, Img prevColor, Img motion, Img reprojDepth, Img prevDepth, Img out, const CamK& cur, const CamK& prev,
                        const mifx_taa_attribs& a, uint32_t flags, const TaaFusedComposite* fused = nullptr);
 // Depth of field (dof.hip)

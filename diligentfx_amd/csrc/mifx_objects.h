@@ -235,6 +235,9 @@ struct mifx_taa
     // reference's host code (oracle/refhost, round 4); bit `flags` of techniques_created = that flag set has been executed once.
     uint32_t     techniques_created = 0;
     bool         technique_ready    = false; // of this frame's flag set, as of mifx_taa_prepare
+    // History skip (taa.hip): a pixel whose motion factor is exactly 0 weights its history with exactly 0; the kernel stores its current colour without fetching the
+    // history or the previous depth.  false: the whole body for every pixel (mifx_debug_taa_set_history_skip; A/B runs and tests).
+    bool         history_skip       = true;
     // mifx_taa_execute = run without `fused`.  With it (the chain, MIFX_CHAIN_FUSE_COMPOSITE_INTO_TAA) the colour to accumulate is the chain's composite, which the kernel
     // evaluates itself for its colour tile (taa.hip) -- `color` of the render attribs is then not read.  Never combined with the placeholder frame (the chain asks
     // technique_ready first).

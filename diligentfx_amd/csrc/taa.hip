@@ -40,6 +40,26 @@ MIFX_D v3 sdr_to_hdr(v3 c) { return c * (mk3(1.0f) / (mk3(1.0f) - c + mk3(5.9604
 //  169 us.  Result: 215 us with the window, 191 us for the same kernel with the window switched off, 169 us for this one (profiles/r04_ab_taa_window.txt): the block
 //  reduction, the second barrier and the fill cost more than the look-ups they replace, as for SSR's R5 (ssr.hip).  Also seen on the way: a branch per tap instead of one
 //  per group of taps serialises the 20 loads (+50 us), and five instead of seven resident workgroups per CU cost 30 %.)
+//
+// History skip.  The history is weighted with alpha = prevRGBA.w * motionFactor * depthFactor (:241-250), and motionFactor = saturate(1 - |motion * (aspect, 1)| * 256)
+// is exactly 0 for a pixel that moves more than 1/256 of the frame height per frame (8.4 px at 4K).  Then lerp(currY, clamped, 0) = currY + 0 * (clamped - currY) = currY
+// and the store is sdr_to_hdr(ycocg_to_rgb(currY)), ComputeCorrectedAlpha(0): a function of the pixel's own tile texel.  Such a pixel (`dead`) requests no
+// previous-depth tap, and behind the barrier stores that value and leaves: no history tap, no statistic, no clip.  The other pixels execute the statements they
+// executed, in the same order, on the same values.  Not under SkipRejection (that path blends with prevRGBA.w alone) and behind the `!inside || reset` exit, which is
+// unchanged.  mifx_debug_taa_set_history_skip(0) runs the whole body for every pixel; tests/test_gpu_taa_history_skip.py holds the two to the same bits.
+// Every pixel gets the bits it got, except:
+//   1. a component of currY that is -0.0 (only from a -0.0 colour input: max(-0, 0) may keep the sign, and the conversions pass it on; the chain's shade sums from +0
+//      and cannot produce one): the full body stores +0 or -0 by the sign of clamped - currY, the skip keeps -0.  Equal as values; the reference's result depends on
+//      the same sign.
+//   2. an infinite sampled history (colour or alpha) at a dead pixel: the full body, like the reference, turns the pixel into NaN (0 * inf); the skip stores the
+//      finite current colour.  This is the one deviation from the reference: an overflowed history under fast motion ends there instead of spreading.  (A NaN or
+//      -inf sample never got that far: max(history, 0) returns 0 for it, here as in the reference.)
+//   3. a non-finite previous-depth tap: no difference here -- the nine taps feed comparisons only (depthFactor is 0 or 1 whatever they hold), as the
+//      reference's max() over them feeds one.
+// Measured, with the registers, the shares and the all-zero-motion case: profiles/taa_history_skip_ab.txt.
+// Measured and not taken (MIFX_TAA_SKIP_DISOCCLUDED): the same exit for a pixel with a motion factor but no similar previous depth (depthFactor = 0).  It makes the
+// 20 history taps of everybody else wait for the depth compare -- a fourth dependent round trip -- to spare the few pixels the first exit leaves: 120.9 us on the
+// orbit against 120.8 without (section 3 of that file).  Nothing gained, so it stays off.
 constexpr int kTaaBX = 32, kTaaBY = 8, kTaaTW = kTaaBX + 2, kTaaTH = kTaaBY + 2;
 // Round 5: the chain's composite (M1, with SSR's cleanup R7 inside: mifx_composite.h) evaluated HERE, for the 34 x 10 texels of the block's colour tile, instead of a
 // pass of its own that writes a plane this kernel is the only reader of.  COMPOSITE = false: `currColor` is read (the stand-alone effect, the chain with the fusion
@@ -61,7 +81,7 @@ template <bool GAUSS, bool BICUBIC, bool YCOCG, bool COMPOSITE>
 #define MIFX_TAA_WAVES 5
 #endif
 __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img currColor, Img prevColor, Img motionTex, Img currDepth /*reprojected*/, Img prevDepth, Img out, CamK cur, CamK prev,
-                                                  float stability, int reset, int skipRejection, TaaCompositeIn ci)
+                                                  float stability, int reset, int skipRejection, int historySkip, TaaCompositeIn ci)
 {
     __shared__ v4 tile[kTaaTH * kTaaTW];
     const int by0 = int(blockIdx.y) * kTaaBY + out.y0; // first row of this block (row window of `out`)
@@ -85,8 +105,14 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
     // the image, whose values nobody uses); the nine depth taps are requested as soon as the motion vector is there, before the tile is converted, and pinned in front
     // of the barrier; the history taps follow it.  Same loads, same arithmetic, three round trips.
     const bool inImage = x < out.w && y < row_end(out);
+    auto motion_factor = [&](v2 mv) { // saturate(1 - length(motion * (aspect, 1)) * TAA_MOTION_VECTOR_DIFF_FACTOR) :241-243
+        const v2    motion{mv.x * 0.5f, mv.y * -0.5f};
+        const float aspect = cur.vw * cur.ivh;
+        return saturate(1.0f - length(v2{motion.x * aspect, motion.y}) * 256.0f);
+    };
     v2    m;
     float cd;
+    bool  dead = false; // history skip (header comment): this pixel's history weight is exactly zero
     v3    ownColor = mk3(0.0f); // COMPOSITE: SampleCurrColor of this thread's own pixel (the tile holds it converted only)
     float dtap[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}; // (!COMPOSITE) the previous-depth taps around int(PrevPosition), dy outer / dx inner
     {
@@ -124,6 +150,8 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
             v4 raw0 = ld<v4>(currColor, clampi(ox + i0 % kTaaTW, 0, W - 1), clampi(oy + i0 / kTaaTW, 0, H - 1));
             v4 raw1 = ld<v4>(currColor, clampi(ox + i1 % kTaaTW, 0, W - 1), clampi(oy + i1 / kTaaTW, 0, H - 1));
             keep_here(m); // (the motion vector is the oldest request: this waits for it alone)
+            dead = historySkip && motion_factor(m) == 0.0f;
+            if (!dead) // (one branch around the group of nine requests, none around the barrier)
             {
                 const v2 mo{m.x * 0.5f, m.y * -0.5f};
                 const v2 pp{(float(x) + 0.5f) - mo.x * cur.vw, (float(y) + 0.5f) - mo.y * cur.vh};
@@ -159,8 +187,17 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
         st<v4>(out, x, y, mk4(COMPOSITE ? ownColor : sample_curr(x, y), 0.5f));
         return;
     }
-    const float aspect       = cur.vw * cur.ivh;
-    const float motionFactor = saturate(1.0f - length(v2{motion.x * aspect, motion.y}) * 256.0f); // TAA_MOTION_VECTOR_DIFF_FACTOR
+    const float motionFactor = motion_factor(m);
+    auto corrected_alpha = [&](float a) { return fminf(stability, saturate(fdiv(1.0f, 2.0f - a))); }; // ComputeCorrectedAlpha :224-227
+    // History skip: alpha below is exactly 0, the blend returns the pixel's own tile texel and nothing fetched or computed from here on can change a bit of the store
+    // (the three corners in the header comment).  `dead` of the stand-alone instance is this condition, evaluated in front of the barrier.
+    auto store_current_only = [&]() { st<v4>(out, x, y, mk4(sdr_to_hdr(ycocg_to_rgb<YCOCG>(tile_at(0, 0))), corrected_alpha(0.0f))); };
+    if (COMPOSITE) dead = historySkip && motionFactor == 0.0f;
+    if (dead)
+    {
+        store_current_only();
+        return;
+    }
 
     // ComputeDepthDisocclusion :117-136 (3x3 around int(PrevPosition), unclamped loads -> 0).  Only the threshold on the maximum is used:
     //   max_i exp(-|lc - lp_i| / max(lc, lp_i, 1e-6)) > 0.9   <=>   exists i : |lc - lp_i| < k * max(lc, lp_i, 1e-6),  k = -ln(0.9)
@@ -184,6 +221,15 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
             }
     }
     const float depthFactor = similar ? 1.0f : 0.0f; // TAA_DEPTH_DISOCCLUSION_THRESHOLD = 0.9
+#ifdef MIFX_TAA_SKIP_DISOCCLUDED
+    // The same exit for a pixel without a similar previous depth (alpha = w * motionFactor * 0): its 20 history taps are not issued -- and everybody else's wait
+    // for the depth compare, one more dependent round trip.  Numbers in the header comment.
+    if (historySkip && !similar)
+    {
+        store_current_only();
+        return;
+    }
+#endif
     v4 prevRGBA;
     if (BICUBIC)
     {
@@ -215,7 +261,6 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
 
     const v3 currY = tile_at(0, 0); // rgb_to_ycocg(hdr_to_sdr(SampleCurrColor(x, y)))
     const v3 prevY = rgb_to_ycocg<YCOCG>(hdr_to_sdr(xyz(prevRGBA)));
-    auto corrected_alpha = [&](float a) { return fminf(stability, saturate(fdiv(1.0f, 2.0f - a))); }; // ComputeCorrectedAlpha :224-227
 
     if (skipRejection)
     {
@@ -262,6 +307,8 @@ mifx_status launch_taa(hipStream_t s, Img currColor, Img prevColor, Img motion, 
                        const mifx_taa_attribs& a, uint32_t flags, const TaaFusedComposite* fused)
 {
     const dim3 block(kTaaBX, kTaaBY, 1), grid = grid2d(out, block);
+    // SkipRejection blends with the history's own alpha, not with the motion factor: nothing has zero weight there
+    const int historySkip = (flags & kTaaFullBodyEverywhere) == 0 && a.SkipRejection == 0 ? 1 : 0;
     TaaCompositeIn ci{};
     if (fused)
     {
@@ -283,7 +330,7 @@ mifx_status launch_taa(hipStream_t s, Img currColor, Img prevColor, Img motion, 
         ci.r7 = *fused->r7;
     }
 #define MIFX_TAA_C(G, B, Y, C) hipLaunchKernelGGL((taa_kernel<G, B, Y, C>), grid, block, 0, s, currColor, prevColor, motion, reprojDepth, prevDepth, out, cur, prev, \
-                                                  a.TemporalStabilityFactor, a.ResetAccumulation, a.SkipRejection, ci)
+                                                  a.TemporalStabilityFactor, a.ResetAccumulation, a.SkipRejection, historySkip, ci)
 #define MIFX_TAA(G, B, Y) do { if (fused) MIFX_TAA_C(G, B, Y, true); else MIFX_TAA_C(G, B, Y, false); } while (0)
     switch (flags & 7u)
     {

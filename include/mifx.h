@@ -451,6 +451,10 @@ MIFX_API mifx_status mifx_taa_reset_history(mifx_taa* fx);
 /* Temporal state, as mifx_ssao_export_history / _import_history: the accumulation buffer (F32X4, alpha = accumulated weight; TemporalAntiAliasing.cpp:123-143, 272-274). */
 MIFX_API mifx_status mifx_taa_export_history(mifx_taa* fx, const mifx_image2d* out_color, uint32_t* out_frame_index);
 MIFX_API mifx_status mifx_taa_import_history(mifx_taa* fx, const mifx_image2d* color, uint32_t frame_index);
+/* Test hook: a pixel whose motion factor is exactly 0 (it moves more than 1/256 of the frame height per frame) weights its history with exactly 0; the kernel stores
+ * its current colour without fetching the history or the previous depth (default), or runs the whole body for every pixel (0).  The stored bits are the same
+ * either way apart from the corners listed in taa.hip (a -0.0 colour, a history sample that is or overflows to +inf).  A chain's TAA follows the setting of its effect object. */
+MIFX_API mifx_status mifx_debug_taa_set_history_skip(mifx_taa* fx, int32_t enable);
 /* Halton(2,3) jitter in NDC units, 16-sample cycle -- TemporalAntiAliasing::GetJitterOffset, .cpp:63-78 (static form) */
 MIFX_API mifx_status mifx_taa_get_jitter_offset(uint32_t frame_index, uint32_t width, uint32_t height, float out_jitter[2]);
 /* GetJitteredProjMatrix, TemporalAntiAliasing.hpp:138-155 */
