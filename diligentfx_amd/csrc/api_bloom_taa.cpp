@@ -123,7 +123,11 @@ mifx_status mifx_bloom::run(const mifx_bloom_render_attribs* ra, int phase, cons
     hipStream_t s = c->stream;
     const Rows need = c->needed_rows(int(h));
     const Plan p    = make_plan(c->band, need, mipCount, req.halo_level0);
-    MIFX_REQUIRE(phase == 0 || p.G >= 0, "mifx_bloom_execute: phased execution needs a row band (mifx_chain_set_row_band)");
+    // (make_plan gives no plan, G < 0, for a band whose pyramid is too short to split -- mipCount - 1 <= kGatherLevel, e.g. Radius 0.4 on a 160x192 frame or 0.2 at 8K --,
+    //  for a band that is the whole frame, and for a pyramid of more than 16 levels.  In all three the two phases go down and up the whole levels with nothing to gather
+    //  in between: shard_rows (api_chain.cpp) then asks for the whole frame in front of Bloom, the tail of small levels runs in the second phase, and the callers of
+    //  gather_level (api_comm.cpp, sharded.py) skip the gather)
+    MIFX_REQUIRE(phase == 0 || !c->band.empty(), "mifx_bloom_execute: phased execution needs a row band (mifx_chain_set_row_band)");
     MIFX_REQUIRE(phase != 0 || p.G < 0, "mifx_bloom_execute: a row band is set; run the two phases around the gather of down[%d]", p.G);
     auto dwin = [&](int i) { return p.G >= 0 ? win(down[i]->view(), p.down[i]) : down[i]->view(); };
     auto uwin = [&](int i) { return p.G >= 0 ? win(up[i]->view(), p.up[i]) : up[i]->view(); };

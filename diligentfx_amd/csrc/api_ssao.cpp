@@ -212,7 +212,7 @@ mifx_status mifx_ssao::run(const mifx_ssao_render_attribs* ra, const Request& re
     if (!ctx->band.empty() && !half)
     {
         const double reach0 = std::exp2(0.5 + double(a.DepthMIPSamplingOffset)); // sqrt of the first threshold of tap_mip (mifx_effects.h: MipLenSq[0] = 2^(1 + 2 offset))
-        const Rows   a3     = rows_expand(rows_align(rows_expand(rows_expand(ctx->needed_rows(int(H)), int(std::ceil(a.SpatialReconstructionRadius)) + 1, int(H)), 48, int(H)), mifx_ssao::kWindowAlign, int(H)), 1, int(H));
+        const Rows   a3     = rows_expand(mifx_ssao::accum_rows(a, ctx->needed_rows(int(H)), int(H), false), 1, int(H)); // (w3 below with the wider of A7's two reaches)
         zbuild.l[0] = win(zpyr.l[0], rows_align(rows_expand(a3, int(std::ceil(reach0)) + 2, int(H)), 2, int(H))); // (48: the wider of the two A7 reaches below -- a superset is always safe here)
         if (pyramid_fusable_levels(int(W), int(H), mifx_ssao::kMips - 1) == mifx_ssao::kMips - 1)
             for (int k = 1; k < mifx_ssao::kMips - 1; ++k)
@@ -252,9 +252,9 @@ mifx_status mifx_ssao::run(const mifx_ssao_render_attribs* ra, const Request& re
     //   A5 reads the 3x3 neighbourhood of the current AO; its history taps are covered by the halo exchange of the history planes.
     const int  iH = int(H);
     const Rows w8 = ctx->needed_rows(iH);
-    const Rows w7 = rows_expand(w8, int(std::ceil(a.SpatialReconstructionRadius)) + 1, iH);
+    const Rows w7 = mifx_ssao::resample_rows(a, w8, iH);
     const bool centredTaps = int(cur.vw) == int(W) && int(cur.vh) == iH && W % 16u == 0u && H % 16u == 0u && !half; // the condition of launch_ssao_resample
-    const Rows w5 = rows_align(rows_expand(w7, centredTaps ? 24 : 48, iH), mifx_ssao::kWindowAlign, iH);
+    const Rows w5 = mifx_ssao::accum_rows(a, w8, iH, centredTaps); // (mifx_objects.h: the reaches of A8 and A7; the chain's history halo is derived from the same function)
     const Rows w3 = rows_expand(w5, 1, iH);
     MIFX_REQUIRE(ctx->prep_rows.empty() || rows_contain(ctx->prep_rows, w5), "mifx_ssao_execute: PostFX prep covered rows [%d, %d), needed [%d, %d)", ctx->prep_rows.b,
                  ctx->prep_rows.e, w5.b, w5.e);

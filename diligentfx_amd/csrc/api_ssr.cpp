@@ -232,7 +232,7 @@ mifx_status mifx_ssr::run(const mifx_ssr_render_attribs* ra, const Request& req)
     //   the whole depth hierarchy, normals and scene colour (all-gathered), R2 is pointwise.
     const int  iH = int(fx->h);
     const Rows w7 = ctx->needed_rows(iH);
-    const Rows w6 = rows_expand(w7, 3, iH);
+    const Rows w6 = mifx_ssr::accum_rows(w7, iH);
     const Rows w5 = rows_expand(w6, 1, iH);
     const bool half = (fx->flags & MIFX_SSR_FEATURE_FLAG_HALF_RESOLUTION) != 0;
     const Rows w4 = mifx_ssr::march_rows(a, w7, iH, half); // full resolution: rows_expand(w5, radius + 1)

@@ -133,6 +133,15 @@ struct mifx_ssao
     // Row-band sharding: A5's / A6's row window starts and ends on a multiple of this many rows -- one row of A6's last level, what the fused pyramid kernel needs
     // (mifx_pyramid.h first_row(); 32 until round 5, when a launch had to start on one of its own 16-row blocks of level 1)
     static constexpr int kWindowAlign = 1 << (kMips - 1);
+    // The row windows behind the rows `need` of the resolved AO (derivation in mifx_ssao_execute), for the effect itself and for the history halo the chain reports
+    // (mifx::chain_shard_info) -- one formula for both.  resample_rows: the rows of A7's output that A8 reads -- Poisson taps of radius <= SpatialReconstructionRadius
+    // (|xi| <= 1; + 1 row for the truncation of the tap position).  accum_rows: the rows of A5 / A6 under them -- A7's reach into the box pyramids (24 rows when its taps sit
+    // on texel centres, `centredTaps`; 48 for the general linear tap), on whole rows of A6's last level.
+    static mifx::Rows resample_rows(const mifx_ssao_attribs& a, mifx::Rows need, int H) { return mifx::rows_expand(need, int(std::ceil(a.SpatialReconstructionRadius)) + 1, H); }
+    static mifx::Rows accum_rows(const mifx_ssao_attribs& a, mifx::Rows need, int H, bool centredTaps)
+    {
+        return mifx::rows_align(mifx::rows_expand(resample_rows(a, need, H), centredTaps ? 24 : 48, H), kWindowAlign, H);
+    }
     mifx::Plane prefiltered_depth[kMips];      // A2 (mip 0 = copy of the depth)
     mifx::Plane prefiltered_camz[kMips];       // depth_to_camera_z of every level of the depth pyramid (level 0 = of the depth buffer): views into camz_slab
     mifx::DeviceScratch camz_slab;             // one allocation, so that an A3 tap addresses any level with a 32-bit offset from a uniform base
@@ -190,6 +199,9 @@ struct mifx_ssr
     // rows of the ray march / of R2 for the rows `need` of the output (derivation in mifx_ssr_execute); the chain's shade covers them when it provides the mask
     // Half resolution: R5's taps of a full-size row y land on the half-size rows int(0.5 (floor(y) +- reach) + 0.5); R4 / R3 run on those (half_rows), and R3 / R4 read
     // the roughness, normal and depth of the 2 x 2 (3 rows at an odd height) full-size block of every such texel: the full-size rows cover them as well.
+    // The rows of R6's output (the accumulated radiance / variance: the two history planes) behind the rows `need` of R7's: R7 filters +-2 texels and takes quad
+    // derivatives (+-1).  No attribute sizes it.  For the effect itself (w6 of mifx_ssr_execute) and for the history halo the chain reports (mifx::chain_shard_info).
+    static mifx::Rows accum_rows(mifx::Rows need, int H) { return mifx::rows_expand(need, 3, H); }
     static mifx::Rows half_rows(const mifx_ssr_attribs& a, mifx::Rows w5, int H)
     {
         const int reach = int(std::ceil(a.SpatialReconstructionRadius)) + 1;

@@ -44,6 +44,11 @@ class CpuChain:
         self.lib, self.p = lib, prefix
         self.algorithm, self.taa_flags = algorithm, taa_flags
         self.reversed_depth = reversed_depth
+        # The attribute blocks of a whole frame, under the names api.Chain keeps them by (tests/chain_util.py run_frame_inputs runs the frame from them; None = the
+        # struct's default()).  ssao_flags / ssr_flags: 2 = FEATURE_FLAG_HALF_RESOLUTION; dof_attribs: depth of field between TAA and Bloom with dof_flags.
+        self.ssao_attribs = self.ssr_attribs = self.taa_attribs = self.bloom_attribs = self.tone_mapping = self.dof_attribs = None
+        self.tonemap_flags, self.ave_log_lum, self.ssr_scale, self.ssao_scale = 1, 0.3, 1.0, 1.0
+        self.ssao_flags = self.ssr_flags = self.dof_flags = 0
         self.reset_history()
 
     def reset_history(self):

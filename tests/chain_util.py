@@ -46,16 +46,22 @@ def shade_attribs(last_mip):
 
 
 def run_frame(chain: cpu_chain.CpuChain, scene, frame_index, w, h, ibl, keep=None, tonemap_mode=4):
-    """One frame of the canonical chain (HnPostProcessTask order): shade -> prep -> SSR -> SSAO -> composite -> TAA -> Bloom -> ToneMap."""
+    """One frame of the canonical chain (HnPostProcessTask order): shade -> prep -> SSR -> SSAO -> composite -> TAA -> [depth of field] -> Bloom -> ToneMap."""
     f = synth.make_frame(scene, frame_index, w, h, torch.device("cpu"), reversed_depth=getattr(chain, "reversed_depth", False))
+    if chain.dof_attribs is not None or chain.ssr_attribs is not None:  # (a set of tests/attrib_sets.py: the lens of depth of field, the roughness where the set reads it)
+        import attrib_sets
+
+        attrib_sets.prepare_frame(f, chain.dof_attribs is not None, chain.ssr_attribs.RoughnessChannel if chain.ssr_attribs is not None else 0)
     g = {k: v.numpy() for k, v in f.items() if isinstance(v, torch.Tensor)}
     return run_frame_inputs(chain, g, bytes(f["camera"]), bytes(f["prev_camera"]), frame_index, ibl, shade_attribs(len(ibl["prefiltered"]) - 1), keep, tonemap_mode)
 
 
 def run_frame_inputs(chain: cpu_chain.CpuChain, g, cam, prev, frame_index, ibl, sa, keep=None, tonemap_mode=4, shade=None):
     """Same as run_frame, on caller-provided inputs (g: dict of numpy planes; cam / prev: CameraAttribs bytes; sa: PBRShadeAttribs).  shade: a callable (g, cam, sa) ->
-    (radiance, specular IBL) in place of the default permutation of the shade (the layered permutations: tests/test_gpu_pbr_layers.py)."""
+    (radiance, specular IBL) in place of the default permutation of the shade (the layered permutations: tests/test_gpu_pbr_layers.py).
+    The attribute blocks are the chain object's (cpu_chain.CpuChain: ssao_attribs, ..., the struct defaults unless tests/attrib_sets.py apply() has set them)."""
     h, w = g["depth"].shape
+    attribs = lambda name, default: getattr(chain, name) if getattr(chain, name) is not None else default  # noqa: E731
     radiance, spec_ibl = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
     if shade is not None:
         radiance, spec_ibl = shade(g, cam, sa)
@@ -63,14 +69,17 @@ def run_frame_inputs(chain: cpu_chain.CpuChain, g, cam, prev, frame_index, ibl, 
         chain.call("pbr_shade", [g["base_color"], g["normal"], g["material"], g["depth"], None, None, ibl["lut"], ibl["irradiance"], ibl["prefiltered"]],
                    [radiance, spec_ibl], cam0=cam, attribs=bytes(sa), fval=[0.02, 0.03, 0.05, 0.0])
     pf = chain.postfx(frame_index, g["depth"], g["prev_depth"], g["motion"], cam, prev, blue_noise_tables())
-    ssr = chain.ssr(pf, radiance, g["depth"], g["normal"], g["material"], g["motion"], B.SSRAttribs.default(), keep)
-    ssao = chain.ssao(pf, g["depth"], g["normal"], B.SSAOAttribs.default(), keep)
+    ssr = chain.ssr(pf, radiance, g["depth"], g["normal"], g["material"], g["motion"], attribs("ssr_attribs", B.SSRAttribs.default()), keep, half_resolution=bool(chain.ssr_flags & 2))
+    ssao = chain.ssao(pf, g["depth"], g["normal"], attribs("ssao_attribs", B.SSAOAttribs.default()), keep, half_resolution=bool(chain.ssao_flags & 2))
     comp = np.zeros((h, w, 4), np.float32)
-    chain.call("composite", [radiance, spec_ibl, ssr, ssao, g["normal"], g["base_color"], g["material"], ibl["lut"]], [comp], cam0=cam, fval=[1.0, 1.0])
-    taa = chain.taa(pf, comp, B.TAAAttribs.default(), keep)
-    bloom = chain.bloom(taa, B.BloomAttribs.default(), keep)
+    chain.call("composite", [radiance, spec_ibl, ssr, ssao, g["normal"], g["base_color"], g["material"], ibl["lut"]], [comp], cam0=cam, fval=[chain.ssr_scale, chain.ssao_scale])
+    taa = chain.taa(pf, comp, attribs("taa_attribs", B.TAAAttribs.default()), keep)
+    post = taa
+    if chain.dof_attribs is not None:  # DepthOfField::Execute between TAA and Bloom (HnPostProcessTask.cpp:899-909)
+        post = chain.dof(pf, taa, g["depth"], chain.dof_attribs, chain.dof_flags, keep)
+    bloom = chain.bloom(post, attribs("bloom_attribs", B.BloomAttribs.default()), keep)
     final = np.zeros((h, w, 4), np.float32)
-    chain.call("tonemap", [bloom], [final], attribs=bytes(B.ToneMappingAttribs.default(tonemap_mode)), fval=[0.3], ival=[1])
+    chain.call("tonemap", [bloom], [final], attribs=bytes(attribs("tone_mapping", B.ToneMappingAttribs.default(tonemap_mode))), fval=[chain.ave_log_lum], ival=[chain.tonemap_flags])
     if keep is not None:
         keep.update({"gbuffer": g, "camera": cam, "prev_camera": prev, "radiance": radiance, "specular_ibl": spec_ibl, "postfx": pf, "composite": comp,
                      "final": final, "shade_attribs": sa})

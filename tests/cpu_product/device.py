@@ -90,6 +90,7 @@ class Device:
         self.algorithm = "gtao"
         self.taa_flags_seen = None
         self.fail_next = None  # the name of a launch that fails once (MIFX_ERR_HIP) instead of running
+        self.composite_rows = []  # (row_begin, row_end) of every composite launch: the rows a band reads of SSAO's and SSR's outputs (run.py sharded_case empties and reads it)
 
     def chain(self, rev):
         return cpu_chain.CpuChain(self.lib, self.prefix, reversed_depth=bool(rev))
@@ -234,8 +235,9 @@ class Device:
         ch.call("ssao_resampled_history", [[tight(view(ap.l[i])) for i in range(ap.levels)], [tight(view(dp.l[i])) for i in range(dp.levels)], tight(view(hist_len.img)),
                                            tight(view(normal.img, 4))], [res], cam0=self.camera(k))
         store(r.resampled, res)
+        # (A8 reads the PLANE, as the kernel does: outside the row window of A7 it holds what earlier frames left, so a window that is too short for A8's taps shows)
         o = cpu_chain.f32((h, w))
-        ch.call("ssao_spatial_reconstruction", [res, tight(view(hist_len.img)), tight(view(r.depth)), tight(view(normal.img, 4))], [o], cam0=self.camera(k), attribs=ab)
+        ch.call("ssao_spatial_reconstruction", [tight(view(r.resampled)), tight(view(hist_len.img)), tight(view(r.depth)), tight(view(normal.img, 4))], [o], cam0=self.camera(k), attribs=ab)
         store(r.out, o)
         if r.out2.p:
             store(r.out2, o)
@@ -534,6 +536,7 @@ class Device:
         h, w = oi.height, oi.width
         o = self.composite_image(attribs.p, r7.p, h, w)
         rb, re_ = int(row_begin.i), int(row_end.i)
+        self.composite_rows.append((rb, re_))
         store(Img(oi.data, w, h, oi.pitch_bytes, rb, re_ - rb if re_ > rb else 0), o, 4)  # (the rows of the band's window)
 
     def composite_image(self, attribs_p, r7_p, h, w):

@@ -143,8 +143,13 @@ def chain_random(lib, seed, exact, steps=14):
 SHARD_CASES = [(2, 160, 192, None, 0), (3, 160, 192, (0, 70, 130, 192), 0), (4, 128, 256, None, 0), (2, 150, 186, (0, 90, 186), 0), (3, 160, 192, None, 2),
                (4, 160, 192, (0, 85, 93, 103, 192), 0),  # two bands of 8 and 10 rows: thinner than every history halo, ghost rows come from two ranks away
                (3, 160, 192, None, "dof"), (2, 150, 186, (0, 90, 186), "dof"),  # depth of field (temporal + Karis) between TAA and Bloom
-               (4, 64, 640, None, "wide ao")]  # a tall frame and an effect radius of 8: taps of every pyramid level, bands + reaches well inside the frame -- the per-level store
-#                                                windows of SSAO's depth pyramid (api_ssao.cpp) bind (with an eighth of the reach this case fails)
+               (4, 64, 640, None, "wide ao"),  # a tall frame and an effect radius of 8: taps of every pyramid level, bands + reaches well inside the frame -- the per-level store
+               #                                 windows of SSAO's depth pyramid (api_ssao.cpp) bind (with an eighth of the reach this case fails)
+               # the chain-wide attribute sets of tests/attrib_sets.py: every attribute that sizes a row window below ("narrow") and above its default ("wide": on half-resolution
+               # SSAO / SSR and an odd half size; "dof": the widest circle of confusion, a fractional SSAO radius).  "narrow" twice: at 160x192 Bloom builds two levels only and
+               # is not split (gather_level -1), at 64x640 it builds three
+               (3, 160, 192, (0, 70, 130, 192), "set narrow"), (2, 150, 186, (0, 90, 186), "set wide"), (3, 160, 192, (0, 70, 130, 192), "set dof"), (4, 64, 640, None, "set narrow"),
+               (3, 160, 192, (0, 70, 130, 192), "set wide at full resolution")]  # (the radii of "wide" in the full-resolution windows: mifx_ssr::march_rows without half_rows)
 
 
 def sharded_case(lib, case, frames=4, max_motion_rows=12, skip=()):
@@ -166,8 +171,18 @@ def sharded_case(lib, case, frames=4, max_motion_rows=12, skip=()):
     shade = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
     ref_chain = api.Chain(0, sobol, tile)
     ranks = [api.Chain(0, sobol, tile) for _ in range(world)]
-    dof, wide, half = half == "dof", half == "wide ao", 0 if half in ("dof", "wide ao") else half
+    attrib_set, _, full = half[4:].partition(" at full resolution") if str(half).startswith("set ") else (None, "", "")
+    dof, wide, half = half == "dof", half == "wide ao", 0 if half in ("dof", "wide ao") or attrib_set else half
     for c in ranks + [ref_chain]:
+        if attrib_set:
+            import attrib_sets
+
+            blocks = attrib_sets.apply(c, attrib_set)
+            if full:
+                c.set_effect_feature_flags(ssao_feature_flags=0, ssr_feature_flags=0)
+            if blocks["dof_attribs"] is not None:
+                DEVICE.dof_attribs = bytes(blocks["dof_attribs"])
+            continue
         c.set_effect_feature_flags(ssao_feature_flags=half, ssr_feature_flags=half)
         if wide:
             c.ssao_attribs.EffectRadius = 8.0
@@ -186,10 +201,29 @@ def sharded_case(lib, case, frames=4, max_motion_rows=12, skip=()):
         assert float(g["motion"][..., 1].abs().max()) * 0.5 * H < max_motion_rows
         if dof:
             g["camera"].fFocusDistance, g["camera"].fFStop, g["camera"].fFocalLength = 12.0, 1.2, 135.0
+        if attrib_set:
+            attrib_sets.frame(g, blocks)  # (the lens of depth of field, the roughness in the channel the set reads)
         DEVICE.cam, DEVICE.prev_cam = bytes(g["camera"]), bytes(g["prev_camera"])
         ref_chain.execute(ref_chain.bind_frame(fi, g, ibl, shade, out_ref))
         bounds = [c.bind_frame(fi, g, ibl, shade, o) for c, o in zip(ranks, outs)]
-        infos = S.run_sharded_frame(sharded, comm, bounds, skip=skip)
+        DEVICE.composite_rows.clear()
+
+        def effect_windows(_infos):
+            # What the equality of the bands cannot see: the windows downstream of the composite carry spare rows (one per Bloom level), so a row window of SSAO or SSR
+            # that is a few rows short spoils rows of the composite which never reach the band.  The composite launch of every rank names the rows it reads (the ranks run
+            # their phases in order, one launch each); on those rows the resolved AO must be the unsharded chain's, and R6's radiance and variance on the rows R7 reads
+            # inside the composite (3 more either side: api_ssr.cpp w6) -- before the halo exchange replaces the ghost rows with their owners'.
+            assert len(DEVICE.composite_rows) == world, DEVICE.composite_rows
+            for r, (c, (b, e)) in enumerate(zip(ranks, DEVICE.composite_rows)):
+                assert b <= sharded[r].band[0] and sharded[r].band[1] <= e, (r, b, e, sharded[r].band)
+                for name, reach, cols in (("ssao_history_ao", 0, W), ("ssr_history_radiance", 3, 4 * W), ("ssr_history_variance", 3, W)):
+                    lo, hi = max(b - reach, 0), min(e + reach, H)
+                    got, want = c.shard_plane(name)[lo:hi, :cols], ref_chain.shard_plane(name)[lo:hi, :cols]
+                    rows = (got != want).any(-1).nonzero().flatten() + lo
+                    assert rows.numel() == 0, (f"case {case} frame {fi} rank {r}/{world}: {name} differs from the unsharded chain's on rows {rows[:8].tolist()} .. {int(rows[-1])} of the "
+                                               f"rows {lo} .. {hi} the composite reads (band {sharded[r].band})")
+
+        infos = S.run_sharded_frame(sharded, comm, bounds, skip=skip, unsplit_bloom=S.bloom_is_unsplit(ref_chain, W, H), before_history_exchange=effect_windows)
         for r, sc in enumerate(sharded):
             b, e = sc.band
             assert torch.equal(outs[r][b:e], out_ref[b:e]), f"case {case} frame {fi} rank {r}/{world}: rows {(outs[r][b:e] != out_ref[b:e]).any(-1).any(-1).nonzero()[:8].flatten().tolist()} of the band differ"
@@ -203,7 +237,9 @@ def sharded_case(lib, case, frames=4, max_motion_rows=12, skip=()):
 
 GROUP_CASES = [(2, 160, 192, None, ""), (3, 160, 192, (0, 60, 130, 192), ""), (4, 128, 256, None, ""), (2, 160, 192, None, "half resolution"),
                (4, 160, 192, (0, 84, 92, 102, 192), "thin bands"), (3, 160, 192, (0, 60, 130, 192), "depth of field"),
-               (3, 160, 192, (0, 60, 130, 192), "three lanes")]  # mifx_chain_set_overlap 3: the event requests of the SSAO lane (streams do nothing here: the host logic)
+               (3, 160, 192, (0, 60, 130, 192), "three lanes"),  # mifx_chain_set_overlap 3: the event requests of the SSAO lane (streams do nothing here: the host logic)
+               # the chain-wide attribute sets of tests/attrib_sets.py (as in SHARD_CASES), here with Bloom's level-0 halo exchange and the gathered last level of SSAO's pyramid
+               (3, 160, 192, (0, 60, 130, 192), "set narrow"), (2, 150, 186, (0, 90, 186), "set wide"), (3, 160, 192, (0, 60, 130, 192), "set dof"), (4, 64, 640, None, "set narrow")]
 
 
 def local_group_case(lib, case, frames=4, auto_exposure=False):
@@ -244,8 +280,17 @@ def local_group_case(lib, case, frames=4, auto_exposure=False):
             da.MaxCircleOfConfusion = 0.02
             c.set_depth_of_field(da, 3)
             DEVICE.dof_attribs = bytes(da)
+        if mode.startswith("set "):
+            import attrib_sets
+
+            blocks = attrib_sets.apply(c, mode[4:])
+            if blocks["dof_attribs"] is not None:
+                DEVICE.dof_attribs = bytes(blocks["dof_attribs"])
         if auto_exposure:
             c.set_auto_exposure(True)
+    if mode.startswith("set "):
+        for f in fr:
+            attrib_sets.frame(f, blocks)
     if mode == "depth of field":
         for f in fr:
             f["camera"].fFocusDistance, f["camera"].fFStop, f["camera"].fFocalLength = 12.0, 1.2, 135.0
@@ -517,6 +562,19 @@ def main():
         for fn in (sys.argv[2:] or ["test_chain_vs_cpu_chain", "test_chain_reversed_depth"]):
             getattr(C, fn)(lib)
             print(f"cpu product: scenario OK: chain {fn}", flush=True)
+    elif what == "chain_sets":
+        # mifx_chain_execute with each chain-wide attribute set of tests/attrib_sets.py on the chain object and on the CPU chain (tests/test_gpu_chain.py
+        # test_chain_vs_cpu_chain_at_attribute_sets, for equality): an attribute block, feature flag or depth-of-field setting that the host code does not pass on shows here
+        import attrib_sets
+        import test_gpu_chain as C
+
+        C.assert_close = exact
+        C.to_np = T.to_np
+        for name in attrib_sets.NAMES:
+            da = attrib_sets.blocks(name)["dof_attribs"]
+            DEVICE.dof_attribs = bytes(da) if da is not None else None
+            C.chain_vs_cpu_chain(frames=4, attrib_set=name)
+            print(f"cpu product: scenario OK: chain at set {name}", flush=True)
     elif what == "arguments":
         # the argument checks of round 5's entries, which need a chain object (the CPU build has one without a GPU)
         from util import blue_noise_tables
@@ -633,9 +691,31 @@ def main():
         def on_frame(g):
             DEVICE.cam, DEVICE.prev_cam = bytes(g["camera"]), bytes(g["prev_camera"])
 
-        for overlap in (0, 2, 3):
-            S.band_against_phases(torch.device("cpu"), overlap, False, make_ibl, W=160, H=192, cuts=(0, 60, 130, 192), on_frame=on_frame)
-            print(f"cpu product: execute_band OK: overlap {overlap}", flush=True)
+        def on_chain(blocks):
+            DEVICE.dof_attribs = bytes(blocks["dof_attribs"]) if blocks["dof_attribs"] is not None else None
+
+        for overlap, attrib_set in ((0, None), (2, None), (3, None), (3, "narrow"), (3, "wide"), (2, "dof")):
+            S.band_against_phases(torch.device("cpu"), overlap, False, make_ibl, W=160, H=192, cuts=(0, 60, 130, 192), on_frame=on_frame, attrib_set=attrib_set, on_chain=on_chain)
+            print(f"cpu product: execute_band OK: overlap {overlap}{', set ' + attrib_set if attrib_set else ''}", flush=True)
+    elif what == "controls":
+        # mifx_chain_get_shard_info follows each attribute that sizes a row window, one attribute at a time (tests/test_gpu_sharded.py shard_info_controls), at the sizes of the
+        # device test: host code only
+        import chain_util
+        import test_gpu_sharded as S
+
+        def make_ibl(_chain):
+            ibl_np = chain_util.make_ibl(pyref.ref_lib(), "ref_")
+            return api.IBLResources(torch.from_numpy(ibl_np["lut"]), [torch.from_numpy(m) for m in ibl_np["irradiance"]], [torch.from_numpy(m) for m in ibl_np["prefiltered"]]), len(ibl_np["prefiltered"])
+
+        def on_frame(g):
+            DEVICE.cam, DEVICE.prev_cam = bytes(g["camera"]), bytes(g["prev_camera"])
+
+        def on_chain(blocks):
+            DEVICE.dof_attribs = bytes(blocks["dof_attribs"]) if blocks["dof_attribs"] is not None else None
+
+        for name, w, h in (("narrow", 640, 768), ("narrow", 160, 192), ("wide", 600, 750), ("dof", 640, 768)):
+            S.shard_info_controls(torch.device("cpu"), name, w, h, make_ibl, on_frame=on_frame, on_chain=on_chain)
+            print(f"cpu product: shard info controls OK: set {name} at {w}x{h}", flush=True)
     elif what == "local_group":
         for case in range(int(sys.argv[2]), int(sys.argv[3])):
             local_group_case(lib, case)

@@ -76,6 +76,13 @@ def test_the_chain_object_on_the_cpu_equals_the_cpu_chain(cpu_lib):
     assert out.count("cpu product: scenario OK: chain") == 2, out
 
 
+def test_the_chain_object_at_the_attribute_sets_equals_the_cpu_chain(cpu_lib):
+    """mifx_chain_execute with each chain-wide set of tests/attrib_sets.py (every attribute block off its defaults, half-resolution SSAO / SSR, depth of field) on the
+    chain object and on the CPU chain: four frames equal bit for bit, so every block, flag and scale reaches its pass as the checker's chain hands it on."""
+    out = run(cpu_lib, "chain_sets")
+    assert out.count("cpu product: scenario OK: chain at set") == 3, out
+
+
 def test_the_pipelined_chain_on_the_cpu_equals_the_cpu_chain(cpu_lib):
     """mifx_chain_set_overlap 4 (two frames in flight: the planes between lane S and lane X alternate between two sets, traded with the effect objects' own at the start of
     every frame) over the same frames, with lane edges set: which set a kernel is handed is host logic, so it shows here; the stream ordering does not (streams do nothing
@@ -93,8 +100,10 @@ def test_argument_checks_of_the_round_5_entries(cpu_lib):
 
 def test_execute_band_on_the_cpu_equals_the_phases(cpu_lib):
     """mifx_chain_execute_band (api_comm.cpp execute_sharded_impl without a communicator: one stream, two lanes, three lanes requested) against mifx_chain_execute_phase 0 .. 4
-    on a second chain object with the same band: band rows and histories equal, nothing written outside the band."""
-    assert run(cpu_lib, "band", timeout=900).count("cpu product: execute_band OK") == 3
+    on a second chain object with the same band: band rows and histories equal, nothing written outside the band.  Three lanes and two once more at the chain-wide
+    attribute sets of tests/attrib_sets.py (narrow / wide on three lanes, depth of field on two)."""
+    out = run(cpu_lib, "band", timeout=900)
+    assert out.count("cpu product: execute_band OK") == 6 and all(f"set {n}" in out for n in ("narrow", "wide", "dof")), out
 
 
 def test_the_order_of_the_lanes_has_no_unordered_pair(cpu_lib):
@@ -148,17 +157,30 @@ def test_row_bands_on_the_cpu_product(cpu_lib):
     """Row-band sharding of the chain (mifx_chain_execute_phase) on the CPU build: 2, 3 and 4 chain objects on equal and uneven bands (down to 8 rows: thinner than the history halos), odd pyramid
     sizes, half-resolution SSAO / SSR, depth of field, the exchanges done by copying rows between their planes -- the bands' rows equal the unsharded chain object's, rows outside a band are never written, the history
     planes are equal on band + halo.  The launch handlers write only the row window each launcher was given, so a pass reading rows nobody computed would show; the run also drops
-    each of the two exchanges once and must see the bands differ."""
-    out = run(cpu_lib, "sharded", "0", "9", timeout=2400)  # (case 8: the store windows of SSAO's depth pyramid levels bind)
-    assert out.count("cpu product: sharded case OK") == 9 and out.count("exchange the bands differ, as they must") == 2, out
+    each of the two exchanges once and must see the bands differ.
+    Cases 9 - 13: the chain-wide attribute sets of tests/attrib_sets.py -- every attribute that sizes a row window (SSAO and SSR SpatialReconstructionRadius, Bloom Radius,
+    depth of field's MaxCircleOfConfusion) below and above its default, half-resolution SSAO / SSR with the wide radii, a Bloom pyramid too short to split.  Every
+    case also holds the resolved AO and SSR's accumulated radiance / variance to the unsharded chain's on ALL rows the band's composite reads, before the halo exchange: the
+    windows behind the composite carry spare rows, so the bands alone do not show a window of SSAO or SSR that is a row or two short (SSR's taps stay a row or
+    two inside the ceil(radius) + 1 rows its windows allow them: a window of its ray march that is 2 rows short changes no texel)."""
+    out = run(cpu_lib, "sharded", "0", "14", timeout=2400)  # (case 8: the store windows of SSAO's depth pyramid levels bind)
+    assert out.count("cpu product: sharded case OK") == 14 and out.count("exchange the bands differ, as they must") == 2, out
+
+
+def test_shard_info_follows_each_attribute_that_sizes_a_row_window(cpu_lib):
+    """mifx_chain_get_shard_info at the three sets of tests/attrib_sets.py, against the same set with one attribute back at its default, over 32 interior bands moved row by row
+    (tests/test_gpu_sharded.py shard_info_controls, here on the CPU build of the host code): halo_ssao follows SSAO's SpatialReconstructionRadius (on the bands where the 16-row
+    alignment of the window does not take up its 2 rows), all three halos follow depth of field, Bloom's Radius turns the gather off where the pyramid has two levels and moves
+    neither the gathered level nor the owned rows otherwise, SSR's radius moves nothing."""
+    assert run(cpu_lib, "controls").count("cpu product: shard info controls OK") == 4
 
 
 def test_execute_sharded_with_the_in_library_group_on_the_cpu(cpu_lib):
     """mifx_chain_execute_sharded over the communicator of one process (csrc/api_comm.cpp: the code that decides which rows travel to whom for the RCCL transport as well, with a
     copy in place of ncclSend / ncclRecv), one thread per rank: 2, 3 and 4 ranks, half resolution, 8-row bands whose ghost rows come from two ranks away, depth of field -- bands and
     history planes equal the unsharded chain object's (tests/test_comm.py::test_sharded_execute_in_process_group on the CPU build)."""
-    out = run(cpu_lib, "local_group", "0", "7", timeout=2400)  # (case 6: mifx_chain_set_overlap 3, the SSAO lane's event requests)
-    assert out.count("cpu product: in-library group OK") == 7, out
+    out = run(cpu_lib, "local_group", "0", "11", timeout=2400)  # (case 6: mifx_chain_set_overlap 3, the SSAO lane's event requests; 7 - 10: the sets of tests/attrib_sets.py)
+    assert out.count("cpu product: in-library group OK") == 11, out
 
 
 def test_blooms_level_0_halo_exchange_runs_and_shortens_the_history_halos(cpu_lib):

@@ -1,11 +1,12 @@
-"""Non-default attribute blocks through the C ABI: the SSAO / SSR / Bloom effects on the GPU against the CPU chain with the attribute sets of
-tests/test_oracle_attribs_vs_ref.py (where the checker itself is pinned to the reference build on them).
+"""Non-default attribute blocks through the C ABI: the SSAO / SSR / Bloom / TAA / depth-of-field effects and the tone map on the GPU against the checker with the
+attribute sets of tests/test_oracle_attribs_vs_ref.py (where the checker itself is pinned to the reference build on them; the rows live in tests/attrib_sets.py).
 
 Every case decides the suite (the round-1 "first hardware run pending" markers are gone: all of them have run on an MI355X)."""
 import numpy as np
 import pytest
 import torch
 
+import attrib_sets as A
 import cpu_chain
 from util import assert_close, blue_noise_tables, centre_tap_slack, to_np
 
@@ -105,3 +106,54 @@ def test_bloom_attribute_sweep_gpu(mifx_lib, intensity, threshold, soft, radius,
             assert_close(to_np(bloom.get_intermediate(f"down{i}")), d, what=f"Bloom frame {frame} down{i}")
         for i, u in enumerate(keep["bloom_up"]):
             assert_close(to_np(bloom.get_intermediate(f"up{i}")), u, what=f"Bloom frame {frame} up{i}", abs_slack=centre_tap_slack(keep["bloom_down"][i]))
+
+
+# ---- the TAA, depth-of-field and tone-map rows of tests/attrib_sets.py (tests/test_oracle_attribs_vs_ref.py pins the checker to the reference build on them).  The isolated
+# comparison of the two helpers -- the checker fed with the device's own inputs and history -- decides at the contract (assert_close's defaults, no outlier); their
+# end-to-end comparisons keep the budgets they have there.  The worst relative errors measured on an MI355X: profiles/attrib_sweep_parity.txt.
+@pytest.mark.parametrize("flags,stability,skip", A.TAA_SETS)
+def test_taa_attribute_sweep_gpu(mifx_lib, flags, stability, skip):
+    from diligentfx_amd import binding as B
+    from test_gpu_bloom_taa import taa_multi_frame
+
+    a = B.TAAAttribs.default()
+    a.TemporalStabilityFactor, a.SkipRejection = stability, skip
+    isolated, end_to_end = taa_multi_frame(flags, size=(176, 100), attribs=a)
+    print(f"TAA flags {flags} stability {stability} skip {skip}: max rel err isolated {isolated:.1e}, end to end {end_to_end:.1e}")
+
+
+@pytest.mark.parametrize("size", [(100, 60), (202, 118)])
+@pytest.mark.parametrize("max_coc,temporal,rings,density,alpha", A.DOF_SETS)
+def test_dof_attribute_sweep_gpu(mifx_lib, max_coc, temporal, rings, density, alpha, size):
+    """Temporal smoothing and the Karis weights on (flags 3), at the two sizes of tests/test_gpu_dof.py whose dilation levels take the odd paths."""
+    from test_gpu_dof import dof_per_pass_and_output
+
+    worst = dof_per_pass_and_output(size, 3, (rings, density), attribs=A.dof_attribs((max_coc, temporal, rings, density, alpha)))
+    print(f"DOF max CoC {max_coc} temporal {temporal} rings {rings} x {density} alpha {alpha} at {size}: max rel err {max(worst.values()):.1e} ({max(worst, key=worst.get)})")
+
+
+@pytest.mark.parametrize("row", A.TONEMAP_SETS, ids=lambda r: "-".join(str(x) for x in r))
+def test_tonemap_attribute_sweep_gpu(mifx_lib, oracle, row):
+    """mifx_tonemap_execute on the 40x56 image of the checker's own sweep -- 16 stops around 1, a zero, a 1e-12 and a 1e4 texel -- with every operator, with and without
+    the sRGB conversion, at tests/test_gpu_tonemap_prep.py::test_tonemap_all_modes' tolerance (assert_close's defaults), against the hand-written checker and the reference build."""
+    from diligentfx_amd import api
+    from test_gpu_tonemap_prep import checkers
+
+    rng = np.random.default_rng(3)
+    img = np.concatenate([np.exp2(rng.uniform(-9, 7, (40, 56, 3))), rng.random((40, 56, 1))], -1).astype(np.float32)
+    img[0, :3, :3] = [[0, 0, 0], [1e-12, 1e-12, 1e-12], [1e4, 2e4, 5e3]]
+    ctx = api.PostFXContext(0)
+    hdr = torch.from_numpy(img).to(ctx.device)
+    worst = 0.0
+    for mode in range(12):
+        attr = A.tone_mapping(mode, row)
+        for srgb in (0, 1):
+            got = to_np(ctx.tone_map(hdr, attr, row[4], flags=srgb))
+            # (with the sRGB conversion the reference's AgX operator gives NaN on the zero texel, and AgX with custom parameters on a few dark texels as
+            #  well: assert_close asks for NaN on the same texels)
+            for prefix, lib in checkers(oracle):
+                want = np.zeros_like(got)
+                lib.call(prefix + "tonemap", [img], [want], attribs=bytes(attr), fval=[row[4]], ival=[srgb])
+                worst = max(worst, assert_close(got, want, what=f"tone map mode {mode} srgb {srgb} vs {prefix}")[0])
+    print(f"tone map {row}: max rel err {worst:.1e}")
+    ctx.close()

@@ -119,9 +119,10 @@ def test_taa_multi_frame(mifx_lib, flags):
     taa_multi_frame(flags)
 
 
-def taa_multi_frame(flags, size=(176, 100)):
+def taa_multi_frame(flags, size=(176, 100), attribs=None):
     """Five frames; each frame's HIP output is compared with the checker fed with the HIP history (per-pass isolation),
-    and the checker's independent history is compared end to end."""
+    and the checker's independent history is compared end to end.  attribs: a TAAAttribs block other than the default (tests/test_gpu_attribute_sweeps.py).
+    Returns the worst relative error of the isolated and of the end-to-end comparison."""
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker(f"taa_flags{flags}")
@@ -131,8 +132,9 @@ def taa_multi_frame(flags, size=(176, 100)):
     taa = api.TemporalAntiAliasing(ctx)
     chain = cpu_chain.CpuChain(lib, pfx, taa_flags=flags)
     scene = synth.Scene()
-    attribs = B.TAAAttribs.default()
+    attribs = attribs if attribs is not None else B.TAAAttribs.default()
     prev_hist = np.zeros((h, w, 4), np.float32)
+    worst = [0.0, 0.0]
     for frame in range(5):
         f = synth.make_frame(scene, frame, w, h, ctx.device)
         color = torch.cat([f["base_color"][..., :3] * 2.0 + 0.05 * f["normal"][..., :3].abs(), f["base_color"][..., 3:4]], -1).contiguous()
@@ -154,16 +156,17 @@ def taa_multi_frame(flags, size=(176, 100)):
             lib.call(pfx + f"taa_flags{flags}", [to_np(color), prev_hist, to_np(ctx.get_closest_motion_vectors()), to_np(ctx.get_reprojected_depth()), to_np(f["prev_depth"])],
                      [want], cam0=bytes(f["camera"]), cam1=bytes(f["prev_camera"]), attribs=bytes(a))
         # disocclusion / inside-screen tests are thresholds on computed values => a few pixels may flip
-        assert_close(got, want, max_outlier_frac=0.0, what=f"TAA flags {flags} frame {frame} (isolated)")
+        worst[0] = max(worst[0], assert_close(got, want, max_outlier_frac=0.0, what=f"TAA flags {flags} frame {frame} (isolated)")[0])
         pf = chain.postfx(frame, to_np(f["depth"]), to_np(f["prev_depth"]), to_np(f["motion"]), bytes(f["camera"]), bytes(f["prev_camera"]), (sobol, tile))
         e2e = chain.taa(pf, to_np(color), attribs)
-        assert_close(got, e2e, max_outlier_frac=0.0, what=f"TAA flags {flags} frame {frame} (end to end)")
+        worst[1] = max(worst[1], assert_close(got, e2e, max_outlier_frac=0.0, what=f"TAA flags {flags} frame {frame} (end to end)")[0])
         if frame > 0:
             assert torch.equal(taa.get_accumulated_frame(is_prev_frame=True), torch.from_numpy(prev_hist).to(ctx.device))
         prev_hist = got.copy()
         assert np.isfinite(got).all()
     taa.close()
     ctx.close()
+    return tuple(worst)
 
 
 def test_taa_history_imported_into_a_fresh_object(mifx_lib):

@@ -47,8 +47,17 @@ def test_chain_vs_cpu_chain(mifx_lib):
     chain_vs_cpu_chain()
 
 
-def chain_vs_cpu_chain(size=(224, 128), frames=6):
-    """test_chain_vs_cpu_chain at any frame size and frame count (tests/test_gpu_frame_edges.py: the smallest frames the chain accepts)."""
+@pytest.mark.parametrize("attrib_set", ["narrow", "wide", "dof"])
+def test_chain_vs_cpu_chain_at_attribute_sets(mifx_lib, attrib_set):
+    """Four frames of the chain against the CPU chain with one set of tests/attrib_sets.py on both sides: an attribute block (or a feature flag, or depth of field) the
+    chain does not pass on to its effect shows here.  The final-image budget is test_chain_vs_cpu_chain's."""
+    chain_vs_cpu_chain(frames=4, attrib_set=attrib_set)
+
+
+def chain_vs_cpu_chain(size=(224, 128), frames=6, attrib_set=None):
+    """test_chain_vs_cpu_chain at any frame size and frame count (tests/test_gpu_frame_edges.py: the smallest frames the chain accepts).  attrib_set: a set of
+    tests/attrib_sets.py on the chain object and on the CPU chain."""
+    import attrib_sets
     import chain_util
     from diligentfx_amd import api, synth
 
@@ -60,12 +69,17 @@ def chain_vs_cpu_chain(size=(224, 128), frames=6):
     ibl = api.IBLResources(torch.from_numpy(ibl_np["lut"]).to(chain.device), [torch.from_numpy(m).to(chain.device) for m in ibl_np["irradiance"]],
                            [torch.from_numpy(m).to(chain.device) for m in ibl_np["prefiltered"]])
     cpu = cpu_chain.CpuChain(lib, pfx)
+    lens = lambda f: f  # noqa: E731
+    if attrib_set:
+        blocks = attrib_sets.apply(chain, attrib_set)
+        attrib_sets.apply(cpu, attrib_set)
+        lens = lambda f: attrib_sets.frame(f, blocks)  # noqa: E731  (chain_util.run_frame does the same on its side)
     scene = synth.Scene()
     sa = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
     out = torch.zeros(h, w, 4, device=chain.device)
     fracs = []
     for frame in range(frames):
-        f = synth.make_frame(scene, frame, w, h, chain.device)
+        f = lens(synth.make_frame(scene, frame, w, h, chain.device))
         chain.execute(chain.bind_frame(frame, f, ibl, sa, out))
         want = chain_util.run_frame(cpu, scene, frame, w, h, ibl_np)
         got = to_np(out)
@@ -78,7 +92,7 @@ def chain_vs_cpu_chain(size=(224, 128), frames=6):
     print("outlier fractions per frame:", [round(x, 5) for x in fracs])
     # history reset: replaying frame 0 after reset_history reproduces the first output exactly
     chain.reset_history()
-    f0 = synth.make_frame(scene, 0, w, h, chain.device)
+    f0 = lens(synth.make_frame(scene, 0, w, h, chain.device))
     first = torch.zeros_like(out)
     chain.execute(chain.bind_frame(0, f0, ibl, sa, first))
     a = first.clone()
@@ -351,7 +365,20 @@ def test_chain_all_options_together(mifx_lib):
 
 
 def test_chain_fusion_is_bit_identical(mifx_lib):
-    """mifx_chain_set_fusion_mask: the copy-frame ToneMap as the tail of Bloom's final up-sample, SSR's mask / roughness pass as a by-product of the shade, SSR's
+    fusion_is_bit_identical([((mode, srgb, channel, perceptual), 7 if mode == 4 else 3) for mode, srgb, channel, perceptual in ((4, 1, 0, 1), (7, 0, 0, 1), (0, 1, 1, 0), (10, 1, 0, 1))])
+
+
+@pytest.mark.parametrize("attrib_set,frames", [("narrow", 3), ("wide", 7), ("dof", 3)])
+def test_chain_fusion_is_bit_identical_at_attribute_sets(mifx_lib, attrib_set, frames):
+    """test_chain_fusion_is_bit_identical with a set of tests/attrib_sets.py on both chain objects: the fused kernels carry attribute blocks of their own (the cleanup's sigma
+    factor in the composite, the tone-map block, Intensity and AlphaInterpolation in Bloom's final up-sample, the roughness threshold in the shade's mask).  "wide" runs
+    seven frames, so that SSAO's history passes the thresholds of A7 and A8."""
+    fusion_is_bit_identical([(attrib_set, frames)])
+
+
+def fusion_is_bit_identical(cases):
+    """cases: ((tone-map mode, sRGB flag, roughness channel, perceptual) or the name of a set of tests/attrib_sets.py, frame count), one after the other on the same two objects.
+    mifx_chain_set_fusion_mask: the copy-frame ToneMap as the tail of Bloom's final up-sample, SSR's mask / roughness pass as a by-product of the shade, SSR's
     bilateral cleanup inside the composite, SSAO's A7 + A8 as one resolve over work lists, the composite inside the TAA kernel (and the IBL apron copies kept across frames) give the same frame, Bloom /
     TAA / SSAO / SSR outputs and SSR planes, bit for bit, as the separate passes."""
     import chain_util
@@ -370,18 +397,27 @@ def test_chain_fusion_is_bit_identical(mifx_lib):
     scene = synth.Scene()
     sa = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
     a, b = torch.zeros(h, w, 4, device=fused.device), torch.zeros(h, w, 4, device=fused.device)
-    for mode, srgb, channel, perceptual in ((4, 1, 0, 1), (7, 0, 0, 1), (0, 1, 1, 0), (10, 1, 0, 1)):
+    for case, frames in cases:
+        blocks = None
         for c in (fused, plain):
-            c.tone_mapping = B_tm(mode)
-            c.tonemap_flags = srgb
-            c.ssr_attribs.RoughnessChannel, c.ssr_attribs.IsRoughnessPerceptual = channel, perceptual
+            if isinstance(case, str):
+                import attrib_sets
+
+                blocks = attrib_sets.apply(c, case)
+            else:
+                mode, srgb, channel, perceptual = case
+                c.tone_mapping = B_tm(mode)
+                c.tonemap_flags = srgb
+                c.ssr_attribs.RoughnessChannel, c.ssr_attribs.IsRoughnessPerceptual = channel, perceptual
             c.reset_history()
-        for frame in range(7 if mode == 4 else 3):  # (the first case runs long enough for SSAO's history to pass the thresholds of A7 and A8)
+        for frame in range(frames):  # (seven frames: long enough for SSAO's history to pass the thresholds of A7 and A8)
             f = synth.make_frame(scene, frame, w, h, fused.device)
+            if blocks is not None:
+                attrib_sets.frame(f, blocks)
             fused.execute(fused.bind_frame(frame, f, ibl, sa, a))
             plain.execute(plain.bind_frame(frame, f, ibl, sa, b))
-            assert torch.equal(a, b), (mode, srgb, frame, int((a != b).sum()))
-            for fx in ("bloom", "taa", "ssao"):
+            assert torch.equal(a, b), (case, frame, int((a != b).sum()))
+            for fx in ("bloom", "taa", "ssao") + (("dof",) if blocks is not None and blocks["dof_attribs"] is not None else ()):
                 assert torch.equal(fused.effect_output(fx), plain.effect_output(fx)), (fx, frame)
             for name in ("mask", "roughness", "hist_radiance", "hist_variance"):
                 assert torch.equal(fused.effect("ssr").get_intermediate(name), plain.effect("ssr").get_intermediate(name)), name
@@ -476,7 +512,7 @@ def test_rocTX_markers_do_not_disturb_the_chain(mifx_lib):
 LANE_EDGES = "ssao_compute_ao_kernel<ssr_intersection_kernel@1,ssao_temporal_kernel<ssr_temporal_kernel@1,bloom_prefilter_kernel<ssr_spatial_kernel@0,taa_kernel<pbr_shade_ssr_mask_kernel@0"
 
 
-@pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, "4 + edges", "4 at 1920x1080", "5 at 1920x1080", "3 at 3840x2160", "4 at 3840x2160", "5 at 3840x2160"])
+@pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, "4 + edges", "4 at 1920x1080", "5 at 1920x1080", "3 at 3840x2160", "4 at 3840x2160", "5 at 3840x2160", "3 + set wide", "5 + set dof"])
 def test_chain_stream_overlap_is_bit_identical(mifx_lib, mode):
     """mifx_chain_set_overlap: prep + SSAO on the second stream (1), across frames (2: several frames are queued without a synchronisation in between, so that
     the next frame's prep + SSAO really run beside the previous frame's Bloom), the three lanes of mode 3 (shade + prep + Hi-Z + SSAO | SSR + composite + TAA | Bloom),
@@ -494,11 +530,19 @@ def test_chain_stream_overlap_is_bit_identical(mifx_lib, mode):
     over.set_overlap(int(str(mode)[0]))
     if mode == "4 + edges":
         over.set_lane_edges(LANE_EDGES)
+    blocks = None
+    if " + set " in str(mode):  # a set of tests/attrib_sets.py on both objects: half-resolution SSAO / SSR on the lanes of mode 3, depth of field on the Bloom lane of mode 5
+        import attrib_sets
+
+        for c in (plain, over):
+            blocks = attrib_sets.apply(c, str(mode).split(" + set ")[1])
     ibl = api.precompute_ibl(plain.postfx, synth.make_sky_cube(32, plain.device).clamp(max=200.0), lut_size=32, irradiance_size=8, prefiltered_size=32, lut_samples=32,
                              diffuse_samples=32, specular_samples=16)
     sa = chain_util.shade_attribs(len(ibl.pre) - 1)
     scene = synth.Scene()
     frames = [synth.make_frame(scene, i, w, h, plain.device) for i in range(8)]
+    if blocks is not None:
+        frames = [attrib_sets.frame(f, blocks) for f in frames]
     want = [torch.zeros(h, w, 4, device=plain.device) for _ in frames]
     got = [torch.zeros(h, w, 4, device=plain.device) for _ in frames]
     torch.cuda.synchronize()  # (mode 2: the inputs of every frame are complete before the first execute)

@@ -98,9 +98,10 @@ def test_dof_per_pass_and_output(mifx_lib, size, flags, rings):
     dof_per_pass_and_output(size, flags, rings)
 
 
-def dof_per_pass_and_output(size, flags, rings, frames=(7, 8, 9), edge=False):
+def dof_per_pass_and_output(size, flags, rings, frames=(7, 8, 9), edge=False, attribs=None):
     """The per-pass comparison at any frame size (tests/test_gpu_frame_edges.py runs it at the boundary sizes).  edge: the frame may be too small to hold a
-    visibly blurred texel; every comparison stays as it is."""
+    visibly blurred texel; every comparison stays as it is.  attribs: a DOFAttribs block to run with (tests/test_gpu_attribute_sweeps.py; `rings` is then its ring count
+    and density).  Returns the worst relative error of every pass."""
     from diligentfx_amd import api, binding as B, synth
 
     lib, pfx = checker()
@@ -109,9 +110,11 @@ def dof_per_pass_and_output(size, flags, rings, frames=(7, 8, 9), edge=False):
     ctx = api.PostFXContext(0, sobol, tile)
     dof = api.DepthOfField(ctx)
     scene = synth.Scene()
-    attribs = B.DOFAttribs.default()
-    attribs.MaxCircleOfConfusion, attribs.AlphaInterpolation = 0.02, 0.9
-    attribs.BokehKernelRingCount, attribs.BokehKernelRingDensity = rings
+    if attribs is None:
+        attribs = B.DOFAttribs.default()
+        attribs.MaxCircleOfConfusion, attribs.AlphaInterpolation = 0.02, 0.9
+        attribs.BokehKernelRingCount, attribs.BokehKernelRingDensity = rings
+    assert (attribs.BokehKernelRingCount, attribs.BokehKernelRingDensity) == tuple(rings)
     temporal = bool(flags & 1)
     e2e_chain = cpu_chain.CpuChain(lib, pfx)
     prev_temporal = np.zeros((h, w), np.float32)
@@ -174,11 +177,12 @@ def dof_per_pass_and_output(size, flags, rings, frames=(7, 8, 9), edge=False):
         pf = {"frame": frame, "cam": bytes(cam), "closest_motion": motion}
         want = e2e_chain.dof(pf, cnp, dnp, attribs, flags)
         # (measured on an MI355X: not one value beyond rtol, profiles/r03_parity_outliers_strict_vs_shipped.txt)
-        assert_close(got, want, max_outlier_frac=0.0, what=f"DOF end to end frame {frame}")
+        worst["end to end"] = max(worst.get("end to end", 0.0), assert_close(got, want, max_outlier_frac=0.0, what=f"DOF end to end frame {frame}")[0])
         assert np.isfinite(got).all() and (edge or np.abs(got[..., :3] - cnp[..., :3]).max() > 0.05)
     print("max rel err per pass:", {k: f"{v:.1e}" for k, v in worst.items()})
     dof.close()
     ctx.close()
+    return worst
 
 
 def test_dof_argument_checks(mifx_lib):

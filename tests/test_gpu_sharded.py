@@ -17,7 +17,10 @@ SHAPES = [(2, 640, 768, None, 0), (3, 640, 768, None, 0), (4, 512, 1536, None, 0
           (4, 640, 768, (0, 340, 372, 410, 768), 0),  # two bands of 32 / 38 rows: thinner than every history halo, ghost rows come from two ranks away
           (3, 640, 768, None, "dof"), (2, 600, 750, (0, 350, 750), "dof"),  # depth of field (temporal smoothing + Karis weights) between TAA and Bloom
           (3, 640, 768, (0, 330, 520, 768), "layers"),  # mifx_chain_set_material_layers: all five layers + two shadow-mapped lights in the shade and in the SSR hit fetch
-          (3, 640, 768, (0, 376, 392, 768), 0)]  # a band of 16 rows (the band setters take any non-empty band): its whole halo comes from its neighbours
+          (3, 640, 768, (0, 376, 392, 768), 0),  # a band of 16 rows (the band setters take any non-empty band): its whole halo comes from its neighbours
+          # the chain-wide attribute sets of tests/attrib_sets.py ("set NAME"): every attribute that sizes a row window below / above its default ("wide": on half resolution)
+          (3, 640, 768, (0, 330, 520, 768), "set narrow"), (2, 600, 750, (0, 350, 750), "set wide"), (3, 640, 768, (0, 330, 520, 768), "set dof"),
+          (3, 160, 192, (0, 70, 130, 192), "set narrow")]  # Bloom Radius 0.4 of 7 levels: a pyramid of two levels is not split (gather_level -1), both Bloom phases run it whole
 
 
 class LocalComm:
@@ -86,7 +89,16 @@ def history_mismatch(chain, ref_chain, info, b, e, H=H, W=W):
     return bad
 
 
-def run_sharded_frame(sharded, comm, bounds, skip=()):
+def bloom_is_unsplit(chain, W, H):
+    """Bloom::ComputeMipCount for the chain's Radius at this size gives no level beyond the one the ranks would gather (level 1): every rank builds the pyramid whole."""
+    import cpu_chain
+
+    return int(np.float32(chain.bloom_attribs.Radius) * np.float32(cpu_chain.compute_mip_levels_count(W // 2, H // 2))) <= 2
+
+
+def run_sharded_frame(sharded, comm, bounds, skip=(), unsplit_bloom=False, before_history_exchange=None):
+    """unsplit_bloom: the caller expects a Bloom pyramid too short to split (every rank builds it whole: gather_level -1, nothing to gather).
+    before_history_exchange: called with the infos when every phase has run and no ghost row of a history plane has been replaced yet."""
     from diligentfx_amd.sharded import HISTORY_PLANES
 
     for s, b in zip(sharded, bounds):
@@ -96,8 +108,8 @@ def run_sharded_frame(sharded, comm, bounds, skip=()):
     for s, b in zip(sharded, bounds):
         s.phase(b, 2)
     infos = [s.chain.shard_info(b) for s, b in zip(sharded, bounds)]
-    assert all(i.gather_level >= 0 for i in infos)
-    if "bloom" not in skip:
+    assert all((i.gather_level < 0) == unsplit_bloom for i in infos), [i.gather_level for i in infos]
+    if "bloom" not in skip and not unsplit_bloom:
         comm.gather_owned_rows("bloom_gather", infos)
     for s, b in zip(sharded, bounds):
         s.phase(b, 3)
@@ -106,6 +118,8 @@ def run_sharded_frame(sharded, comm, bounds, skip=()):
             comm.gather_luminance_rows(infos)
         for s, b in zip(sharded, bounds):
             s.phase(b, 4)
+    if before_history_exchange:
+        before_history_exchange(infos)
     if "history" not in skip:
         for name, field in HISTORY_PLANES:
             common = max(getattr(i, field) for i in infos)  # both sides of an exchange move the same number of rows
@@ -128,12 +142,18 @@ def test_sharded_chain_equals_unsharded(mifx_lib, world, W, H, cuts, half):
                              lut_samples=32, diffuse_samples=32, specular_samples=16)
     shade = chain_util.shade_attribs(len(ibl.pre) - 1)
     ranks = [api.Chain(0, sobol, tile) for _ in range(world)]
-    ae, dof, layers, half = half == "ae", half == "dof", half == "layers", 0 if half in ("ae", "dof", "layers") else half
+    attrib_set = half[4:] if str(half).startswith("set ") else None
+    ae, dof, layers, half = half == "ae", half == "dof", half == "layers", 0 if half in ("ae", "dof", "layers") or attrib_set else half
     if layers:
         shade = chain_util.shadowed_shade_attribs(len(ibl.pre) - 1)
         slices, infos_np = chain_util.make_shadow_inputs()
         shadow_maps = torch.from_numpy(np.stack(slices)).to(dev)
     for c in ranks + [ref_chain]:
+        if attrib_set:  # (feature flags and depth of field included)
+            import attrib_sets
+
+            blocks = attrib_sets.apply(c, attrib_set)
+            continue
         c.set_effect_feature_flags(ssao_feature_flags=half, ssr_feature_flags=half)  # 2 = FEATURE_FLAG_HALF_RESOLUTION of both effects
         if ae:
             c.set_auto_exposure(True, elapsed_time_s=0.25)
@@ -152,6 +172,8 @@ def test_sharded_chain_equals_unsharded(mifx_lib, world, W, H, cuts, half):
         g = synth.make_frame(scene, fi, W, H, dev)
         if dof:
             g["camera"].fFocusDistance, g["camera"].fFStop, g["camera"].fFocalLength = 12.0, 1.2, 135.0
+        if attrib_set:
+            attrib_sets.frame(g, blocks)
         if layers:  # new planes every frame, whole on every rank like the G-buffer
             from layers_util import IOR, ROTATION, make_layers
 
@@ -165,7 +187,7 @@ def test_sharded_chain_equals_unsharded(mifx_lib, world, W, H, cuts, half):
         assert float(m[..., 1].abs().max()) * 0.5 * H < MAX_MOTION_ROWS, "the synthetic motion exceeds the declared reprojection reach"
         ref_chain.execute(ref_chain.bind_frame(fi, g, ibl, shade, out_ref))
         bounds = [c.bind_frame(fi, g, ibl, shade, o) for c, o in zip(ranks, outs)]
-        infos = run_sharded_frame(sharded, comm, bounds)
+        infos = run_sharded_frame(sharded, comm, bounds, unsplit_bloom=bloom_is_unsplit(ref_chain, W, H))
         torch.cuda.synchronize()
         for r, s in enumerate(sharded):
             b, e = s.band
@@ -188,15 +210,132 @@ def test_sharded_chain_equals_unsharded(mifx_lib, world, W, H, cuts, half):
         c.close()
 
 
-@pytest.mark.parametrize("skip", ["bloom", "history", "luminance"])
+SWEEP = 32  # bands [H / 3 + k, 2 H / 3 + k), k = 0 .. 31: two whole periods of the 16-row alignment of SSAO's window on both edges
+
+
+def shard_info_controls(dev, attrib_set, W, H, make_ibl, on_frame=None, on_chain=None):
+    """Control of mifx_chain_get_shard_info at a set of tests/attrib_sets.py, one attribute at a time: the chain object with the whole set against a second one with the
+    same set and ONE attribute back at its default, so that nothing else (depth of field above all, which widens every window) stands in the way, over SWEEP interior
+    bands moved row by row -- SSAO's window is aligned to 16 rows, which takes up the 2 rows of the radius on most bands and not on all.
+      SSAO SpatialReconstructionRadius -> halo_ssao: never on the other side of the default's, and beyond it on at least one band;
+      depth of field                   -> halo_taa, halo_ssr, halo_ssao: larger on every band than without it;
+      Bloom Radius                     -> gather_level -1 where the pyramid is too short to split (bloom_is_unsplit), against 1 at the default; otherwise neither the
+                                          gathered level nor the rows a rank owns of it move -- they are functions of the band alone (mifx_bloom::make_plan) -- and that is held;
+      SSR SpatialReconstructionRadius  -> nothing: R6 / R7 read a fixed number of rows (mifx_ssr::accum_rows), halo_ssr is the same with the default radius.
+    (also run by tests/cpu_product/run.py `controls` on the CPU build of the host code)"""
+    import attrib_sets
+    import chain_util
+    from diligentfx_amd import api, binding as B, synth
+    from util import blue_noise_tables
+
+    sobol, tile = blue_noise_tables()
+    blocks = attrib_sets.blocks(attrib_set)
+    variants = {"set": lambda c: None,
+                "ssao radius": lambda c: setattr(c.ssao_attribs, "SpatialReconstructionRadius", B.SSAOAttribs.default().SpatialReconstructionRadius),
+                "ssr radius": lambda c: setattr(c.ssr_attribs, "SpatialReconstructionRadius", B.SSRAttribs.default().SpatialReconstructionRadius),
+                "bloom radius": lambda c: setattr(c.bloom_attribs, "Radius", B.BloomAttribs.default().Radius)}
+    if blocks["dof_attribs"] is not None:
+        variants["depth of field"] = lambda c: c.set_depth_of_field(None)
+    g = attrib_sets.frame(synth.make_frame(synth.Scene(), 19, W, H, dev), blocks)
+    if on_frame:
+        on_frame(g)
+    if on_chain:
+        on_chain(blocks)
+    out = torch.zeros(H, W, 4, device=dev)
+    info, ibl = {}, None
+    for name, reset in variants.items():
+        c = api.Chain(0, sobol, tile)
+        if ibl is None:
+            ibl, n_pre = make_ibl(c)
+            shade = chain_util.shade_attribs(n_pre - 1)
+        attrib_sets.apply(c, attrib_set)
+        reset(c)
+        c.set_row_band(H // 3, 2 * H // 3, MAX_MOTION_ROWS)
+        c.execute_phase(c.bind_frame(19, g, ibl, shade, out), 0)  # (mifx_chain_get_shard_info wants the frame's resources prepared)
+        rows = []
+        for k in range(SWEEP):
+            c.set_row_band(H // 3 + k, 2 * H // 3 + k, MAX_MOTION_ROWS)
+            rows.append(c.shard_info(c.bind_frame(19, g, ibl, shade, out)))
+        info[name] = {f: [getattr(i, f) for i in rows] for f, _ in rows[0]._fields_}
+        c.close()
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    full = info["set"]
+    plan = ("gather_level", "own_begin", "own_end")
+    unsplit = bloom_is_unsplit(type("Set", (), blocks), W, H)
+    print(f"set {attrib_set} {W}x{H}: gather_level {sorted(set(full['gather_level']))} | {sorted(set(info['bloom radius']['gather_level']))} at the default Bloom radius")
+    if unsplit:  # every rank builds Bloom whole, so every window in front of it is the whole frame: only Bloom's own radius can show, and it does
+        assert set(full["gather_level"]) == {-1} and set(info["bloom radius"]["gather_level"]) == {1}
+        assert all(full == info[name] for name in info if name != "bloom radius")
+        return
+    assert set(full["gather_level"]) == {1} and all(full[f] == info["bloom radius"][f] for f in plan)
+    # SSAO's radius
+    radius, default = blocks["ssao_attribs"].SpatialReconstructionRadius, B.SSAOAttribs.default().SpatialReconstructionRadius
+    sign = 1 if radius > default else -1
+    diff = [sign * (a - b) for a, b in zip(full["halo_ssao"], info["ssao radius"]["halo_ssao"])]
+    print(f"set {attrib_set} {W}x{H}: halo_ssao at radius {radius} minus at {default}, bands +0 .. +{SWEEP - 1}: {[sign * d for d in diff]}")
+    assert min(diff) >= 0 and max(diff) > 0, (attrib_set, full["halo_ssao"], info["ssao radius"]["halo_ssao"])
+    assert all(full[f] == info["ssao radius"][f] for f in full if f != "halo_ssao")
+    # depth of field
+    if "depth of field" in info:
+        for f in ("halo_taa", "halo_ssr", "halo_ssao"):
+            assert all(a > b for a, b in zip(full[f], info["depth of field"][f])), (attrib_set, f, full[f], info["depth of field"][f])
+    # SSR's radius
+    assert full == info["ssr radius"]
+
+
+@pytest.mark.parametrize("attrib_set", ["narrow", "wide", "dof"])
+def test_attribute_sets_move_every_effect_and_the_row_windows(mifx_lib, attrib_set):
+    """Control of the cases "set NAME" above: a case must not pass because its attributes were dead.  On the unsharded chain the output of every effect (and the frame)
+    differs from the default-attribute run of the same frames; SSR's resolve gathers taps (its reconstruction radius is scaled by the roughness: the roughness is
+    where the set reads it).  mifx_shard_info follows the attributes that size a row window, one at a time: shard_info_controls, at the size of the set's case and --
+    "narrow" -- at 160x192, where Bloom's pyramid is too short to split."""
+    import attrib_sets
+    import chain_util
+    from diligentfx_amd import api, synth
+    from util import blue_noise_tables
+
+    world, W, H, cuts = next((s[0], s[1], s[2], s[3]) for s in SHAPES if s[4] == "set " + attrib_set)  # (the first case of the set: the sizes of the issue)
+    sobol, tile = blue_noise_tables()
+    dev = torch.device("cuda", 0)
+    scene = synth.Scene()
+    moved, plain = api.Chain(0, sobol, tile), api.Chain(0, sobol, tile)
+    ibl = api.precompute_ibl(plain.postfx, synth.make_sky_cube(32, dev).clamp(max=200.0), lut_size=32, irradiance_size=8, prefiltered_size=32,
+                             lut_samples=32, diffuse_samples=32, specular_samples=16)
+    shade = chain_util.shade_attribs(len(ibl.pre) - 1)
+    blocks = attrib_sets.apply(moved, attrib_set)
+    outs = {c: torch.zeros(H, W, 4, device=dev) for c in (moved, plain)}
+    for fi in range(16, 19):
+        g = attrib_sets.frame(synth.make_frame(scene, fi, W, H, dev), blocks)  # (both chains on the same planes: only the attributes differ)
+        for c in (moved, plain):
+            c.execute(c.bind_frame(fi, g, ibl, shade, outs[c]))
+        torch.cuda.synchronize()
+        assert not torch.equal(outs[moved], outs[plain]), fi
+        for fx in ("ssao", "ssr", "taa", "bloom"):
+            a, b = moved.effect_output(fx), plain.effect_output(fx)
+            assert float((a != b).float().mean()) > 0.01, (fx, fi)
+    if blocks["dof_attribs"] is not None:
+        assert float((moved.effect_output("dof") != moved.effect_output("taa")).float().mean()) > 0.01
+    # the roughness where the set reads it: reflecting texels with a roughness of 0.05 and more, whose resolve gathers taps over the set's radius
+    rough, mask = moved.effect("ssr").get_intermediate("roughness"), moved.effect("ssr").get_intermediate("mask")
+    assert float(((rough > 0.05) & (mask > 0)).float().mean()) > 0.01
+    for c in (moved, plain):
+        c.close()
+    for w, h in [(W, H)] + ([(160, 192)] if attrib_set == "narrow" else []):
+        shard_info_controls(dev, attrib_set, w, h, _band_ibl(dev))
+
+
+@pytest.mark.parametrize("skip", ["bloom", "history", "luminance", "history at set wide"])
 def test_every_exchange_is_needed(mifx_lib, skip):
-    """Control: leaving out any one of the exchanges must change the result (otherwise the equality test above proves nothing)."""
+    """Control: leaving out any one of the exchanges must change the result (otherwise the equality test above proves nothing).  "at set NAME": with that set of
+    tests/attrib_sets.py on every chain object."""
     import chain_util
     from diligentfx_amd import api, synth
     from diligentfx_amd.sharded import ShardedChain
     from util import blue_noise_tables
 
     world = 2
+    skip, _, attrib_set = skip.partition(" at set ")
     sobol, tile = blue_noise_tables()
     dev = torch.device("cuda", 0)
     scene = synth.Scene()
@@ -205,6 +344,11 @@ def test_every_exchange_is_needed(mifx_lib, skip):
                              lut_samples=32, diffuse_samples=32, specular_samples=16)
     shade = chain_util.shade_attribs(len(ibl.pre) - 1)
     ranks = [api.Chain(0, sobol, tile) for _ in range(world)]
+    if attrib_set:
+        import attrib_sets
+
+        for c in ranks + [ref_chain]:
+            blocks = attrib_sets.apply(c, attrib_set)
     if skip == "luminance":
         for c in ranks + [ref_chain]:
             c.set_auto_exposure(True, elapsed_time_s=0.25)
@@ -215,6 +359,8 @@ def test_every_exchange_is_needed(mifx_lib, skip):
     differs = False
     for fi in range(16, 20):
         g = synth.make_frame(scene, fi, W, H, dev)
+        if attrib_set:
+            attrib_sets.frame(g, blocks)
         ref_chain.execute(ref_chain.bind_frame(fi, g, ibl, shade, out_ref))
         infos = run_sharded_frame(sharded, comm, [c.bind_frame(fi, g, ibl, shade, o) for c, o in zip(ranks, outs)], skip=(skip,))
         torch.cuda.synchronize()
@@ -227,8 +373,9 @@ def test_every_exchange_is_needed(mifx_lib, skip):
 
 
 
-def band_against_phases(dev, overlap, ae, make_ibl, W=W, H=H, cuts=(0, 250, 520, H), on_frame=None):
-    """(also run by tests/cpu_product/run.py `band` on the CPU build of the host code)"""
+def band_against_phases(dev, overlap, ae, make_ibl, W=W, H=H, cuts=(0, 250, 520, H), on_frame=None, attrib_set=None, on_chain=None):
+    """(also run by tests/cpu_product/run.py `band` on the CPU build of the host code)  attrib_set: a set of tests/attrib_sets.py on both chain objects; on_chain is then
+    called with the set's blocks."""
     import os
 
     import chain_util
@@ -241,9 +388,18 @@ def band_against_phases(dev, overlap, ae, make_ibl, W=W, H=H, cuts=(0, 250, 520,
     a, b = api.Chain(0, sobol, tile), api.Chain(0, sobol, tile)
     ibl, n_pre = make_ibl(a)
     shade = chain_util.shade_attribs(n_pre - 1)
+    blocks = None
     for c in (a, b):
         if ae:
             c.set_auto_exposure(True, elapsed_time_s=0.25)
+        if attrib_set:
+            import attrib_sets
+
+            blocks = attrib_sets.apply(c, attrib_set)
+    if blocks is not None:
+        if on_chain:
+            on_chain(blocks)
+        inner, on_frame = on_frame, lambda g: (attrib_sets.frame(g, blocks), inner(g) if inner else None)  # (the lens of depth of field, the roughness where the set reads it)
     # Two whole frames first, on both objects: without the exchanges the ghost rows and the other ranks' rows of the gathered Bloom level are never written, and a fresh
     # device allocation holds anything -- afterwards both objects hold the same values there (both slots of every history plane included).
     scratch = torch.zeros(H, W, 4, device=dev)
@@ -295,13 +451,14 @@ def band_against_phases(dev, overlap, ae, make_ibl, W=W, H=H, cuts=(0, 250, 520,
         c.close()
 
 
-@pytest.mark.parametrize("overlap,ae", [(0, False), (2, False), (2, True), (3, False), (3, True)])
-def test_execute_band_is_the_phases_without_the_exchanges(mifx_lib, overlap, ae):
+@pytest.mark.parametrize("overlap,ae,attrib_set", [(0, False, None), (2, False, None), (2, True, None), (3, False, None), (3, True, None), (3, True, "wide"), (2, False, "dof")],
+                         ids=["0-False", "2-False", "2-True", "3-False", "3-True", "3-True-wide", "2-False-dof"])
+def test_execute_band_is_the_phases_without_the_exchanges(mifx_lib, overlap, ae, attrib_set):
     """mifx_chain_execute_band (what tools/shard_cost.py and TiledChain.calibrate_cuts time): one rank's band through the phases -- and with overlap >= 2 the two lanes across
     frames -- of mifx_chain_execute_sharded, exchanges left out.  Against a second chain object on the same band driven phase by phase: the band's rows of every frame and all five
-    history planes (whole: both hold the same stale ghost rows) are equal bit for bit, frames queued back to back."""
+    history planes (whole: both hold the same stale ghost rows) are equal bit for bit, frames queued back to back.  "wide" / "dof": at those sets of tests/attrib_sets.py."""
     dev = torch.device("cuda", 0)
-    band_against_phases(dev, overlap, ae, _band_ibl(dev))
+    band_against_phases(dev, overlap, ae, _band_ibl(dev), attrib_set=attrib_set)
 
 
 @pytest.mark.parametrize("overlap,ae", [(0, False), (3, True)])

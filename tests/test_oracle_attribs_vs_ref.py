@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import cpu_chain
+from attrib_sets import BLOOM_SETS, DOF_SETS, SSAO_SETS, SSR_SETS, TAA_SETS, TONEMAP_SETS  # (the rows: tests/attrib_sets.py composes the chain-wide sets from them)
 from util import assert_close, blue_noise_tables
 
 W, H, FRAMES = 72, 48, (5, 6, 7)
@@ -40,13 +41,6 @@ def both(oracle, ref, run, **chain_kw):
         yield fi, res[0], res[1]
 
 
-SSAO_SETS = [  # (algorithm, radius, falloff, radius multiplier, mip offset, temporal, spatial radius, bitmask thickness)
-    ("gtao", 0.4, 0.3, 1.0, 2.0, 0.5, 2.0, 0.5),
-    ("gtao", 2.5, 0.9, 2.0, 4.5, 0.97, 6.0, 0.5),
-    ("hbao", 1.7, 0.615, 1.2, 3.3, 0.8, 4.0, 0.5),
-    ("vbao", 1.3, 0.615, 1.457, 2.5, 0.9, 3.0, 0.15),
-    ("vbao", 0.8, 0.4, 1.8, 3.3, 0.6, 5.0, 1.5),
-]
 
 
 @pytest.mark.parametrize("algo,radius,falloff,mult,mipoff,temporal,spatial,thick", SSAO_SETS)
@@ -63,12 +57,6 @@ def test_ssao_attribute_sweep(oracle, ref, algo, radius, falloff, mult, mipoff, 
         assert 0.0 <= x.min() and x.max() <= 1.0 and x.std() > 0.01
 
 
-SSR_SETS = [  # (thickness, roughness threshold, most detailed mip, perceptual, channel, traversals, GGX bias, spatial radius, temporal rad, temporal var, sigma)
-    (0.05, 0.35, 0, 1, 0, 64, 0.0, 2.0, 0.7, 0.5, 0.5),
-    (0.01, 0.5, 1, 1, 1, 128, 0.6, 6.0, 0.95, 0.9, 1.4),
-    (0.025, 0.15, 2, 0, 2, 24, 0.3, 4.0, 1.0, 0.9, 0.9),
-    (0.1, 1.0, 0, 1, 0, 8, 1.0, 1.0, 0.2, 0.2, 0.2),
-]
 
 
 @pytest.mark.parametrize("thick,thresh,mdm,perceptual,channel,trav,bias,radius,trad,tvar,sigma", SSR_SETS)
@@ -88,7 +76,7 @@ def test_ssr_attribute_sweep(oracle, ref, thick, thresh, mdm, perceptual, channe
     assert hits > 0.005  # the sweep does produce reflections
 
 
-@pytest.mark.parametrize("flags,stability,skip", [(0, 0.5, 0), (1, 0.9375, 0), (2, 0.8, 1), (3, 0.99, 0), (4, 0.9, 0), (6, 0.9375, 0), (7, 0.7, 1)])
+@pytest.mark.parametrize("flags,stability,skip", TAA_SETS)
 def test_taa_attribute_sweep(oracle, ref, flags, stability, skip):
     from diligentfx_amd.binding import TAAAttribs
 
@@ -98,7 +86,7 @@ def test_taa_attribute_sweep(oracle, ref, flags, stability, skip):
         assert_close(x, y, rtol=2e-4, atol=1e-6, max_outlier_frac=2e-3, what=f"TAA flags {flags} frame {fi}")
 
 
-@pytest.mark.parametrize("intensity,threshold,soft,radius,alpha", [(0.6, 0.2, 0.5, 0.4, 1.0), (0.05, 2.0, 0.0, 1.0, 0.4), (1.0, 0.0, 1.0, 0.55, 0.9)])
+@pytest.mark.parametrize("intensity,threshold,soft,radius,alpha", BLOOM_SETS)
 def test_bloom_attribute_sweep(oracle, ref, intensity, threshold, soft, radius, alpha):
     from diligentfx_amd.binding import BloomAttribs
 
@@ -154,7 +142,7 @@ def test_pbr_shade_and_composite_attribute_sweep(oracle, ref, ibl_scale, occl_st
     assert np.isfinite(outs[0][0]).all() and outs[0][0][..., :3].max() > 0.1
 
 
-@pytest.mark.parametrize("auto_exposure,middle_gray,white_point,lum_sat,ave_log_lum", [(0, 0.18, 3.0, 1.0, 0.3), (1, 0.4, 1.5, 0.6, 0.05), (1, 0.09, 8.0, 1.7, 4.0)])
+@pytest.mark.parametrize("auto_exposure,middle_gray,white_point,lum_sat,ave_log_lum", TONEMAP_SETS)
 def test_tonemap_attribute_sweep(oracle, ref, auto_exposure, middle_gray, white_point, lum_sat, ave_log_lum):
     """ToneMappingAttribs away from the defaults (ToneMappingStructures.fxh:24-52), every operator, with and without the sRGB conversion."""
     import struct
@@ -171,7 +159,7 @@ def test_tonemap_attribute_sweep(oracle, ref, auto_exposure, middle_gray, white_
             assert_close(a, b, rtol=2e-6, atol=1e-7, what=f"tone map mode {mode} srgb {srgb}")
 
 
-@pytest.mark.parametrize("max_coc,temporal,rings,density,alpha", [(0.005, 0.5, 3, 3, 1.0), (0.035, 0.99, 4, 5, 0.3), (0.015, 0.8, 2, 7, 0.65)])
+@pytest.mark.parametrize("max_coc,temporal,rings,density,alpha", DOF_SETS)
 def test_dof_attribute_sweep(oracle, ref, max_coc, temporal, rings, density, alpha):
     """DepthOfFieldAttribs away from the defaults (DepthOfFieldStructures.fxh:31-56): circle-of-confusion limit, temporal stability, Octaweb kernel shape
     (the large-kernel table is regenerated: DepthOfField.cpp:799-809), interpolation alpha; temporal smoothing + Karis inverse on."""
