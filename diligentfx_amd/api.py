@@ -447,22 +447,48 @@ class ShadowMapManager:
     (mifx_shadow_map_filter).  Cascade distribution and shadow-map rendering stay with the rasteriser: the attribs are taken as given."""
 
     def __init__(self, ctx: "PostFXContext", shadow_mode=B.SHADOW_MODE_PCF, is_32bit_filterable=True):
-        """ShadowMapManager::InitInfo::ShadowMode / Is32BitFilterableFmt.  Only the 32-bit filterable formats are built."""
+        """ShadowMapManager::InitInfo::ShadowMode / Is32BitFilterableFmt (ShadowMapManager.cpp:98-102).  is_32bit_filterable=False: the filterable array is
+        RG16_UNORM (VSM: int16 codes), RG16_FLOAT (EVSM2) or RGBA16_FLOAT (EVSM4), in both builds of the library."""
         if shadow_mode not in (B.SHADOW_MODE_PCF, B.SHADOW_MODE_VSM, B.SHADOW_MODE_EVSM2, B.SHADOW_MODE_EVSM4):
             raise ValueError(f"unknown shadow mode {shadow_mode}")
-        if not is_32bit_filterable:
-            raise NotImplementedError("the 16-bit filterable formats (RG16_UNORM / RG16F / RGBA16F) are not built")
         self.ctx = ctx
         self.shadow_mode = shadow_mode
+        self.is_32bit_filterable = bool(is_32bit_filterable)
         self.filterable = None
 
+    def filterable_dtype(self):
+        """The dtype of the filterable array's channels: float32, or float16 / int16 (the UNORM16 codes of VSM) for the 16-bit formats"""
+        if self.is_32bit_filterable:
+            return torch.float32
+        return torch.int16 if self.shadow_mode == B.SHADOW_MODE_VSM else torch.float16
+
+    def set_format_attribs(self, attribs: B.ShadowMapAttribs, filterable=None):
+        """ShadowAttribs.bIs32BitEVSM for a 16-bit filterable array: 0, as ShadowMapManager.cpp:157 sets it for a format that is not RG32_FLOAT / RGBA32_FLOAT (the
+        library refuses a 16-bit EVSM map with the flag set).  The format is that of `filterable`, the array actually handed over, or the manager's own when none is
+        given.  With an fp32 array the caller's value is left alone: the flag then selects the exponent clamp only, and 0 with an fp32 map is a combination the
+        library takes.  PCF has no filterable map: untouched."""
+        narrow = (filterable.dtype != torch.float32) if filterable is not None else not self.is_32bit_filterable
+        if narrow and self.shadow_mode != B.SHADOW_MODE_PCF:
+            attribs.bIs32BitEVSM = 0
+        return attribs
+
+    @staticmethod
+    def widen(filterable):
+        """A filterable array read back as float32 values: float16 widens, the int16 codes of RG16_UNORM become code / 65535 (correctly rounded)"""
+        if filterable.dtype == torch.int16:
+            codes = (filterable.to(torch.int32) & 0xFFFF).to(torch.float64)
+            return (codes / 65535.0).to(torch.float32)
+        return filterable.to(torch.float32)
+
     def convert_to_filterable(self, shadow_map, attribs: B.ShadowMapAttribs, out=None):
-        """ShadowMapManager::ConvertToFilterable.  shadow_map: float32 (slices, H, W).  Returns (and keeps) the filterable array, float32 (slices, H, W, 2) for VSM /
-        EVSM2 and (slices, H, W, 4) for EVSM4; PCF mode has none."""
+        """ShadowMapManager::ConvertToFilterable.  shadow_map: float32 (slices, H, W).  Returns (and keeps) the filterable array, (slices, H, W, 2) for VSM /
+        EVSM2 and (slices, H, W, 4) for EVSM4, of filterable_dtype() or the dtype of `out` (widen() reads a 16-bit one back as float32); PCF mode has none.  Into a
+        16-bit array attribs.bIs32BitEVSM is set to 0 (set_format_attribs); into an fp32 one the attribs are used as given."""
         if self.shadow_mode == B.SHADOW_MODE_PCF:
             return None
         if out is None:
-            out = torch.empty(tuple(shadow_map.shape) + (4 if self.shadow_mode == B.SHADOW_MODE_EVSM4 else 2,), dtype=torch.float32, device=shadow_map.device)
+            out = torch.empty(tuple(shadow_map.shape) + (4 if self.shadow_mode == B.SHADOW_MODE_EVSM4 else 2,), dtype=self.filterable_dtype(), device=shadow_map.device)
+        self.set_format_attribs(attribs, out)
         src, dst = B.shadow_map_array(shadow_map), B.filterable_shadow_map(out)
         self.ctx.sync_stream()
         B.check(self.ctx.lib.mifx_shadow_convert_to_filterable(self.ctx.handle, ctypes.byref(src), ctypes.byref(attribs), ctypes.c_uint32(self.shadow_mode), ctypes.byref(dst)))
@@ -480,6 +506,8 @@ class ShadowMapManager:
         sm = B.shadow_map_array(shadow_map) if shadow_map is not None else None
         if filterable_map is None and self.shadow_mode != B.SHADOW_MODE_PCF:
             filterable_map = self.filterable
+        if filterable_map is not None:
+            self.set_format_attribs(attribs, filterable_map)
         fm = B.filterable_shadow_map(filterable_map) if filterable_map is not None else None
         d, o = B.image(depth), B.image(light)
         c = B.image(casc) if casc is not None else None
@@ -565,6 +593,7 @@ class OITResources:
     def __init__(self, ctx: "PostFXContext", width, height, layer_count):
         self.ctx, self.lib = ctx, ctx.lib
         self.width, self.height, self.layer_count = width, height, layer_count
+        self.plane_dtype = B.storage_dtype()  # the 4-channel texel of the library build: float32, or float16 (RGBA16_FLOAT) in the native-storage build
         self.handle = ctypes.c_void_p()
         B.check(self.lib.mifx_oit_create(ctx.handle, ctypes.c_uint32(width), ctypes.c_uint32(height), ctypes.c_uint32(layer_count), ctypes.byref(self.handle)))
 
@@ -578,6 +607,15 @@ class OITResources:
             self.close()
         except Exception:
             pass
+
+    def new_targets(self):
+        """The four targets of OIT_TARGETS, zeroed, in the 4-channel texel of the library build"""
+        return {k: torch.zeros(self.height, self.width, 4, device=self.ctx.device, dtype=self.plane_dtype) for k in OIT_TARGETS}
+
+    def to_planes(self, planes):
+        """A slice or a set of targets with every 4-channel plane in the 4-channel texel of the library build (a float32 plane is rounded to binary16 in the
+        native-storage build); the one-channel planes stay float32"""
+        return {k: (v.to(self.plane_dtype).contiguous() if v is not None and v.dim() == 3 and v.shape[2] == 4 else v) for k, v in planes.items()}
 
     @staticmethod
     def _slices(slices):

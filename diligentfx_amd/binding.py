@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MIFX_LIB_PATH") or os.path.join(HERE, "libmifx_h4.so"
 MIFX_OK = 0
 FORMAT_F32, FORMAT_F32X2, FORMAT_F32X4, FORMAT_F16X4 = 1, 2, 4, 8
 FORMAT_U8, FORMAT_F16, FORMAT_F16X2, FORMAT_R11G11B10, FORMAT_U16 = 16, 32, 64, 128, 256  # the narrow planes of the native-storage build (include/mifx.h)
+FORMAT_U16X2 = 512  # RG16_UNORM: the 16-bit filterable shadow map of SHADOW_MODE_VSM, in both builds
 
 c_f = ctypes.c_float
 c_i = ctypes.c_int32
@@ -330,9 +331,15 @@ def shadow_map_array(t) -> "ShadowMapArray":
 
 
 def filterable_shadow_map(t) -> FilterableShadowMap:
-    """float32 CUDA tensor (slices, H, W, 2 | 4), rows and slices possibly pitched -> mifx_filterable_shadow_map"""
-    assert t.dim() == 4 and t.shape[3] in (2, 4) and t.stride(3) == 1 and t.stride(2) == t.shape[3], "a (slices, H, W, 2 | 4) float32 tensor with contiguous texels"
-    return FilterableShadowMap(t.data_ptr(), t.shape[2], t.shape[1], t.shape[0], FORMAT_F32X2 if t.shape[3] == 2 else FORMAT_F32X4, t.stride(1) * 4, t.stride(0) * 4)
+    """CUDA tensor (slices, H, W, 2 | 4), rows and slices possibly pitched -> mifx_filterable_shadow_map.  float32: F32X2 / F32X4; the 16-bit filterable formats:
+    float16 (…, 2) = F16X2 (RG16_FLOAT), float16 (…, 4) = F16X4 (RGBA16_FLOAT), int16 (…, 2) = U16X2 (the codes of RG16_UNORM)"""
+    assert t.dim() == 4 and t.shape[3] in (2, 4) and t.stride(3) == 1 and t.stride(2) == t.shape[3], "a (slices, H, W, 2 | 4) tensor with contiguous texels"
+    import torch
+
+    fmt = {(torch.float32, 2): FORMAT_F32X2, (torch.float32, 4): FORMAT_F32X4, (torch.float16, 2): FORMAT_F16X2, (torch.float16, 4): FORMAT_F16X4,
+           (torch.int16, 2): FORMAT_U16X2}.get((t.dtype, t.shape[3]))
+    assert fmt is not None, f"no filterable shadow-map format for {t.dtype} x {t.shape[3]}"
+    return FilterableShadowMap(t.data_ptr(), t.shape[2], t.shape[1], t.shape[0], fmt, t.stride(1) * t.element_size(), t.stride(0) * t.element_size())
 
 
 OIT_MAX_SLICES, OIT_MAX_LAYERS = 32, 16  # MIFX_OIT_MAX_SLICES, MIFX_OIT_MAX_LAYERS

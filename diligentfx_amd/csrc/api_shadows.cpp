@@ -23,17 +23,26 @@ static mifx_status to_shadow_arr(const mifx_shadow_map_array* m, const char* who
     return MIFX_OK;
 }
 
-static mifx_status to_filterable_arr(const mifx_filterable_shadow_map* m, uint32_t mode, const char* who, FilterableArrK& out)
+// The formats of ShadowMapManager.cpp:98-102 per mode: the 32-bit one, or the 16-bit one that Is32BitFilterableFmt == false selects.  `texel` is the texel size of
+// the format given.
+static mifx_status to_filterable_arr(const mifx_filterable_shadow_map* m, const mifx_shadow_map_attribs* attribs, uint32_t mode, const char* who, FilterableArrK& out)
 {
-    const uint32_t fmt = mode == MIFX_SHADOW_MODE_EVSM4 ? MIFX_FORMAT_F32X4 : MIFX_FORMAT_F32X2, texel = mode == MIFX_SHADOW_MODE_EVSM4 ? 16u : 8u;
+    const uint32_t fmt32 = mode == MIFX_SHADOW_MODE_EVSM4 ? MIFX_FORMAT_F32X4 : MIFX_FORMAT_F32X2;
+    const uint32_t fmt16 = mode == MIFX_SHADOW_MODE_EVSM4 ? MIFX_FORMAT_F16X4 : mode == MIFX_SHADOW_MODE_EVSM2 ? MIFX_FORMAT_F16X2 : MIFX_FORMAT_U16X2;
+    const int      ch    = mode == MIFX_SHADOW_MODE_EVSM4 ? 4 : 2;
     MIFX_REQUIRE(m->data != nullptr && m->width > 0 && m->height > 0 && m->slices > 0, "%s: filterable map: empty array", who);
-    MIFX_REQUIRE(m->format == fmt, "%s: filterable map: shadow mode %u needs %s texels, got format %u", who, mode, texel == 16u ? "MIFX_FORMAT_F32X4" : "MIFX_FORMAT_F32X2", m->format);
+    MIFX_REQUIRE(m->format == fmt32 || m->format == fmt16, "%s: filterable map: shadow mode %u needs %s texels (or the 16-bit %s), got format %u", who, mode,
+                 ch == 4 ? "MIFX_FORMAT_F32X4" : "MIFX_FORMAT_F32X2", ch == 4 ? "MIFX_FORMAT_F16X4" : mode == MIFX_SHADOW_MODE_EVSM2 ? "MIFX_FORMAT_F16X2" : "MIFX_FORMAT_U16X2", m->format);
+    const bool narrow = m->format == fmt16;
+    // exp(40 d) is not a binary16 value: a 16-bit EVSM map goes with the exponents clamped to 5.54 (GetEVSMExponents, Shadows.fxh:280-285; ShadowMapManager.cpp:157)
+    MIFX_REQUIRE(!(narrow && mode != MIFX_SHADOW_MODE_VSM && attribs->bIs32BitEVSM != 0), "%s: filterable map: a 16-bit EVSM format (%u) needs bIs32BitEVSM == 0", who, m->format);
+    const uint32_t texel = shadow_texel_bytes(narrow ? fmt16 : 0u, ch);
     MIFX_REQUIRE(m->width <= 16384u && m->height <= 16384u && m->slices <= 0x7FFFFFFFu, "%s: filterable map: %ux%u is larger than 16384", who, m->width, m->height);
     MIFX_REQUIRE(m->pitch_bytes >= m->width * texel && m->pitch_bytes <= 0x7FFFFFFFu && m->pitch_bytes % texel == 0 && reinterpret_cast<uintptr_t>(m->data) % texel == 0,
                  "%s: filterable map: bad pitch %u / alignment for width %u", who, m->pitch_bytes, m->width);
     MIFX_REQUIRE(m->slice_pitch_bytes >= uint64_t(m->pitch_bytes) * m->height && m->slice_pitch_bytes % texel == 0, "%s: filterable map: bad slice pitch %llu", who,
                  static_cast<unsigned long long>(m->slice_pitch_bytes));
-    out = FilterableArrK{static_cast<unsigned char*>(m->data), int(m->width), int(m->height), int(m->slices), int(m->pitch_bytes), m->slice_pitch_bytes};
+    out = FilterableArrK{static_cast<unsigned char*>(m->data), int(m->width), int(m->height), int(m->slices), int(m->pitch_bytes), m->slice_pitch_bytes, narrow ? fmt16 : 0u};
     return MIFX_OK;
 }
 
@@ -47,7 +56,7 @@ static mifx_status convert_check(const mifx_shadow_map_array* shadow_map, const 
     MIFX_REQUIRE(int64_t(shadow_map->slices) == int64_t(attribs->iNumCascades), "%s: the shadow map has %u slices, iNumCascades is %d (inconsistent number of cascades)", who,
                  shadow_map->slices, attribs->iNumCascades);
     MIFX_CHECK(to_shadow_arr(shadow_map, who, src));
-    MIFX_CHECK(to_filterable_arr(out, mode, who, dst));
+    MIFX_CHECK(to_filterable_arr(out, attribs, mode, who, dst));
     MIFX_REQUIRE(dst.w == src.w && dst.h == src.h && dst.slices == src.slices, "%s: the filterable map is %dx%dx%d, the shadow map %dx%dx%d", who, dst.w, dst.h, dst.slices, src.w, src.h,
                  src.slices);
     k = make_shadowconvk(*attribs, src.w, src.h);
@@ -96,7 +105,7 @@ static mifx_status filter_check(const mifx_image2d* depth, const mifx_camera_att
     else
     {
         MIFX_REQUIRE(filterable_map != nullptr, "%s: shadow mode %u reads the filterable map, which is NULL", who, mode);
-        MIFX_CHECK(to_filterable_arr(filterable_map, mode, who, filterable));
+        MIFX_CHECK(to_filterable_arr(filterable_map, attribs, mode, who, filterable));
         MIFX_REQUIRE(int64_t(filterable.slices) >= int64_t(attribs->iNumCascades), "%s: the filterable map has %d slices, iNumCascades is %d", who, filterable.slices,
                      attribs->iNumCascades);
     }

@@ -320,8 +320,9 @@ template <> struct GlobalAccess<v2>
 };
 // The 4-channel texel in memory.  fp32 build: float4 (16 bytes).  -DMIFX_STORAGE_H4 (libmifx_h4.so): RGBA16_FLOAT (8 bytes) -- a load widens, a store rounds
 // to nearest-even binary16 (v_cvt_f16_f32, overflow -> infinity: the conversion of a D3D / Vulkan RGBA16_FLOAT render-target write); registers and LDS stay fp32.
-#ifdef MIFX_STORAGE_H4
+typedef _Float16 mifx_h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 mifx_h4 __attribute__((ext_vector_type(4)));
+#ifdef MIFX_STORAGE_H4
 constexpr unsigned kV4Bytes = 8;
 MIFX_HD v4 quantize_v4(v4 v) { return v4{float(_Float16(v.x)), float(_Float16(v.y)), float(_Float16(v.z)), float(_Float16(v.w))}; } // what a store + load does to a value
 template <> struct GlobalAccess<v4>
@@ -343,6 +344,30 @@ template <> struct TexelBytes<v4> { static constexpr unsigned value = kV4Bytes; 
 template <class T> struct Stored { using value = T; }; // the value a load of a T-texel returns / a store takes (the narrow storage types below widen to float / v2 / v4)
 
 #include "mifx_ufloat.h" // float_to_ufloat / ufloat_to_float / quantize_ufloat: the unsigned small floats of R11G11B10_FLOAT
+
+// ------------------------------------------------------------------------------------------------ 16-bit converters of both builds
+// What a render-target write of a 16-bit format does to a value, and what a load gives back.  Outside the storage fence below: the filterable shadow maps choose
+// RG16_UNORM / RG16_FLOAT / RGBA16_FLOAT at run time in both builds (mifx_shadows.h), and the test suite compiles that header for the host.
+// R16_UNORM: c / 65535 correctly rounded as q = c * fl(1 / 65535) and one residual step (all 65536 codes: tests/test_formats.py)
+MIFX_D float unorm16_value(float c)
+{
+    const float r = 1.0f / 65535.0f, q = c * r;
+    return __builtin_fmaf(__builtin_fmaf(-q, 65535.0f, c), r, q);
+}
+MIFX_D float unorm16_code(float v) // NaN -> 0, clamp, x 65535, + 0.5, truncate
+{
+    v = v != v ? 0.0f : fminf(fmaxf(v, 0.0f), 1.0f);
+    float s = v * 65535.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(s)); // (rounded before the addition in every translation unit, as for st_unorm8)
+#else
+    asm volatile("" : "+m"(s)); // (the host compilation of the test suite: the same fence through memory)
+#endif
+    return float(unsigned(s + 0.5f));
+}
+MIFX_D float quantize_unorm16(float v) { return unorm16_value(unorm16_code(v)); }
+// binary16: round to nearest even, overflow -> infinity (v_cvt_f16_f32)
+MIFX_D float quantize_half(float v) { return float(_Float16(v)); }
 
 // ------------------------------------------------------------------------------------------------ per-plane storage types
 // The effects name the texel type of every intermediate plane that the reference keeps in a narrow format:
@@ -389,19 +414,6 @@ template <> struct GlobalAccess<st_unorm8>
         *(MIFX_GLOBAL unsigned char*)p = (unsigned char)(unsigned(s + 0.5f));
     }
 };
-// R16_UNORM, as st_unorm8: c / 65535 correctly rounded as q = c * fl(1 / 65535) and one residual step (all 65536 codes: tests/test_formats.py)
-MIFX_D float unorm16_value(float c)
-{
-    const float r = 1.0f / 65535.0f, q = c * r;
-    return __builtin_fmaf(__builtin_fmaf(-q, 65535.0f, c), r, q);
-}
-MIFX_D float unorm16_code(float v)
-{
-    v = v != v ? 0.0f : fminf(fmaxf(v, 0.0f), 1.0f);
-    float s = v * 65535.0f;
-    asm volatile("" : "+v"(s)); // (rounded before the addition in every translation unit, as for st_unorm8)
-    return float(unsigned(s + 0.5f));
-}
 template <> struct GlobalAccess<st_unorm16>
 {
     static MIFX_D float load(const unsigned char* p) { return unorm16_value(float(*(const MIFX_GLOBAL unsigned short*)p)); }
@@ -412,7 +424,6 @@ template <> struct GlobalAccess<st_half>
     static MIFX_D float load(const unsigned char* p) { return float(*(const MIFX_GLOBAL _Float16*)p); }
     static MIFX_D void  store(unsigned char* p, float v) { *(MIFX_GLOBAL _Float16*)p = _Float16(v); }
 };
-typedef _Float16 mifx_h2 __attribute__((ext_vector_type(2)));
 template <> struct GlobalAccess<st_half2>
 {
     static MIFX_D v2   load(const unsigned char* p) { const mifx_h2 t = *(const MIFX_GLOBAL mifx_h2*)p; return v2{float(t.x), float(t.y)}; }

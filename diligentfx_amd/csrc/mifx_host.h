@@ -79,6 +79,7 @@ inline uint32_t texel_size(uint32_t fmt)
         case MIFX_FORMAT_F16X2: return 4u;
         case MIFX_FORMAT_R11G11B10: return 4u;
         case MIFX_FORMAT_U16: return 2u;
+        case MIFX_FORMAT_U16X2: return 4u;
         default: return 0u;
     }
 }

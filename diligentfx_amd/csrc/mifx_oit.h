@@ -6,7 +6,9 @@
 // (tests/host_kernels/oit_host.cpp).
 //
 // Arithmetic.  Strict fp32 in the reference's operation order: no contraction, IEEE division (plain `/`).  A blend is dst = src * sf + dst * df, evaluated in that
-// order with the factors the blend state names, also where a factor is 0 or 1.
+// order with the factors the blend state names, also where a factor is 0 or 1.  The slice planes and the four targets are the build's 4-channel texel
+// (GlobalAccess<v4>: float4, or RGBA16_FLOAT in the native-storage build, where a store rounds to binary16 as the reference's targets do); depth, colour alpha,
+// the opaque depth and the tail are fp32 and the layers uint32 in both builds.
 //
 // The bodies take the pixel's K layer words through a pointer type: the words in HBM (the reference sequence: one launch per draw, as the reference's shaders) or
 // a register array of compile-time size (the fused kernels, whose loops over the layers unroll).  Both run the same functions in the same order, so their results
@@ -210,16 +212,25 @@ template <int K> MIFX_D void oit_store_layers(unsigned char* p, const uint32_t (
         for (int i = 0; i < K; ++i) *(MIFX_GLOBAL uint32_t*)(p + 4 * i) = L[i];
 }
 MIFX_D float oit_slice_depth(const OitSliceK& s, int x, int y) { return GlobalAccess<float>::load(s.depth + size_t(y) * s.pitchDepth + size_t(x) * 4u); }
-MIFX_D float oit_slice_opacity(const OitSliceK& s, int x, int y) { return GlobalAccess<float>::load(s.base + size_t(y) * s.pitchBase + size_t(x) * 16u + 12u); }
+// base_color.a alone: the float at +12 of the 16-byte texel; native-storage build: the half at +6 of the 8-byte texel
+MIFX_D float oit_slice_opacity(const OitSliceK& s, int x, int y)
+{
+    const unsigned char* p = s.base + size_t(y) * s.pitchBase + size_t(x) * kV4Bytes;
+#ifdef MIFX_STORAGE_H4
+    return float(*(const MIFX_GLOBAL _Float16*)(p + 6u));
+#else
+    return GlobalAccess<float>::load(p + 12u);
+#endif
+}
 MIFX_D float oit_opaque_at(const OitK& k, int x, int y) { return k.opaque ? GlobalAccess<float>::load(k.opaque + size_t(y) * k.opaquePitch + size_t(x) * 4u) : 0.0f; }
 MIFX_D bool  oit_fragment_at(const OitK& k, float depth, float opaque) { return oit_has_fragment(depth, k.opaque != nullptr, opaque, k.cam); }
 MIFX_D OitFragment oit_load_fragment(const OitSliceK& s, int x, int y)
 {
     OitFragment f;
-    f.base       = GlobalAccess<v4>::load(s.base + size_t(y) * s.pitchBase + size_t(x) * 16u);
-    f.material   = GlobalAccess<v4>::load(s.material + size_t(y) * s.pitchMaterial + size_t(x) * 16u);
-    f.radiance   = GlobalAccess<v4>::load(s.radiance + size_t(y) * s.pitchRadiance + size_t(x) * 16u);
-    f.ibl        = GlobalAccess<v4>::load(s.ibl + size_t(y) * s.pitchIbl + size_t(x) * 16u);
+    f.base       = GlobalAccess<v4>::load(s.base + size_t(y) * s.pitchBase + size_t(x) * kV4Bytes);
+    f.material   = GlobalAccess<v4>::load(s.material + size_t(y) * s.pitchMaterial + size_t(x) * kV4Bytes);
+    f.radiance   = GlobalAccess<v4>::load(s.radiance + size_t(y) * s.pitchRadiance + size_t(x) * kV4Bytes);
+    f.ibl        = GlobalAccess<v4>::load(s.ibl + size_t(y) * s.pitchIbl + size_t(x) * kV4Bytes);
     f.colorAlpha = s.alpha ? GlobalAccess<float>::load(s.alpha + size_t(y) * s.pitchAlpha + size_t(x) * 4u) : f.base.w;
     return f;
 }
@@ -295,9 +306,11 @@ template <int K> MIFX_D void oit_px_resolve(const OitK& k, const OitSlicesK& tab
     const float T      = oit_total_transmittance(L, K, tail);
     const float opaque = oit_opaque_at(k, x, y);
     bool touched = T != 1.0f;
+    // quantize_v4: what the sequence's store + load between two draws does to a target texel (native-storage build: binary16; fp32 build: the identity)
     if (touched)
     {
         oit_attenuate(c, T); oit_attenuate(b, T); oit_attenuate(m, T); oit_attenuate(i, T);
+        c = quantize_v4(c); b = quantize_v4(b); m = quantize_v4(m); i = quantize_v4(i);
     }
     for (int l = 0; l < tab.count; ++l)
     {
@@ -305,6 +318,7 @@ template <int K> MIFX_D void oit_px_resolve(const OitK& k, const OitSlicesK& tab
         const float      depth = oit_slice_depth(s, x, y);
         if (!oit_fragment_at(k, depth, opaque)) continue;
         oit_blend_slice(L, K, tail, k, s, depth, x, y, c, b, m, i);
+        c = quantize_v4(c); b = quantize_v4(b); m = quantize_v4(m); i = quantize_v4(i);
         touched = true;
     }
     if (!touched) return;

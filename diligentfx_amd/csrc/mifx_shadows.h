@@ -27,32 +27,77 @@ struct ShadowArrK
     int                  w, h, slices, pitch;
     unsigned long long   slicePitch;
 };
-// the filterable array (or the intermediate target of the two-launch conversion): CH = 2 or 4 true fp32 channels per texel
+// the filterable array (or the intermediate target of the two-launch conversion): CH = 2 or 4 channels per texel.  fmt == 0: true fp32 channels (F32X2 / F32X4 by
+// the channel count); otherwise one of the reference's 16-bit filterable formats (ShadowMapManager.cpp:98-102, Is32BitFilterableFmt == false): MIFX_FORMAT_U16X2
+// (RG16_UNORM, VSM), MIFX_FORMAT_F16X2 (RG16_FLOAT, EVSM2), MIFX_FORMAT_F16X4 (RGBA16_FLOAT, EVSM4) -- 2 bytes a channel.  A load widens to fp32, a store converts
+// the way a render-target write of the format does (mifx_device.h: unorm16_code, quantize_half); everything between stays fp32.  The branches on the
+// field are uniform over a launch; the kernels fix it at compile time (shadow_fixed_format below), the host compilation of the test suite takes them as they are.
 struct FilterableArrK
 {
     unsigned char*     data;
     int                w, h, slices, pitch;
     unsigned long long slicePitch;
+    unsigned           fmt;
 };
+MIFX_HD unsigned shadow_texel_bytes(unsigned fmt, int ch) { return (fmt ? 2u : 4u) * unsigned(ch); }
+// what a store to the array followed by a load does to a value
+MIFX_D float shadow_quantize(unsigned fmt, float v) { return fmt == 0u ? v : fmt == MIFX_FORMAT_U16X2 ? quantize_unorm16(v) : quantize_half(v); }
+typedef unsigned short mifx_us2 __attribute__((ext_vector_type(2)));
 template <int CH> MIFX_D void ld_moments(const FilterableArrK& a, int s, int x, int y, float (&m)[CH])
 {
-    const unsigned char* p = a.data + size_t(s) * a.slicePitch + size_t(y) * a.pitch + size_t(x) * (4u * CH);
-    if (CH == 2)
+    const unsigned char* p = a.data + size_t(s) * a.slicePitch + size_t(y) * a.pitch + size_t(x) * shadow_texel_bytes(a.fmt, CH);
+    if (a.fmt == 0u)
     {
-        const mifx_f2 t = *(const MIFX_GLOBAL mifx_f2*)p;
-        m[0] = t.x; m[1] = t.y;
+        if (CH == 2)
+        {
+            const mifx_f2 t = *(const MIFX_GLOBAL mifx_f2*)p;
+            m[0] = t.x; m[1] = t.y;
+        }
+        else
+        {
+            const mifx_f4 t = *(const MIFX_GLOBAL mifx_f4*)p;
+            m[0] = t.x; m[1] = t.y; m[CH - 2] = t.z; m[CH - 1] = t.w;
+        }
+    }
+    else if (CH == 2 && a.fmt == MIFX_FORMAT_U16X2)
+    {
+        const mifx_us2 t = *(const MIFX_GLOBAL mifx_us2*)p;
+        m[0] = unorm16_value(float(t.x)); m[1] = unorm16_value(float(t.y));
+    }
+    else if (CH == 2)
+    {
+        const mifx_h2 t = *(const MIFX_GLOBAL mifx_h2*)p;
+        m[0] = float(t.x); m[1] = float(t.y);
     }
     else
     {
-        const mifx_f4 t = *(const MIFX_GLOBAL mifx_f4*)p;
-        m[0] = t.x; m[1] = t.y; m[CH - 2] = t.z; m[CH - 1] = t.w;
+        const mifx_h4 t = *(const MIFX_GLOBAL mifx_h4*)p;
+        m[0] = float(t.x); m[1] = float(t.y); m[CH - 2] = float(t.z); m[CH - 1] = float(t.w);
     }
 }
 template <int CH> MIFX_D void st_moments(const FilterableArrK& a, int s, int x, int y, const float (&m)[CH])
 {
-    unsigned char* p = a.data + size_t(s) * a.slicePitch + size_t(y) * a.pitch + size_t(x) * (4u * CH);
-    if (CH == 2) *(MIFX_GLOBAL mifx_f2*)p = mifx_f2{m[0], m[1]};
-    else *(MIFX_GLOBAL mifx_f4*)p = mifx_f4{m[0], m[1], m[CH - 2], m[CH - 1]};
+    unsigned char* p = a.data + size_t(s) * a.slicePitch + size_t(y) * a.pitch + size_t(x) * shadow_texel_bytes(a.fmt, CH);
+    if (a.fmt == 0u)
+    {
+        if (CH == 2) *(MIFX_GLOBAL mifx_f2*)p = mifx_f2{m[0], m[1]};
+        else *(MIFX_GLOBAL mifx_f4*)p = mifx_f4{m[0], m[1], m[CH - 2], m[CH - 1]};
+    }
+    else if (CH == 2 && a.fmt == MIFX_FORMAT_U16X2)
+        *(MIFX_GLOBAL mifx_us2*)p = mifx_us2{(unsigned short)(unsigned(unorm16_code(m[0]))), (unsigned short)(unsigned(unorm16_code(m[1])))};
+    else if (CH == 2) *(MIFX_GLOBAL mifx_h2*)p = mifx_h2{_Float16(m[0]), _Float16(m[1])};
+    else *(MIFX_GLOBAL mifx_h4*)p = mifx_h4{_Float16(m[0]), _Float16(m[1]), _Float16(m[CH - 2]), _Float16(m[CH - 1])};
+}
+// `a` with its format the compile-time constant FMT: the kernels are instantiated per format (the launcher picks by FilterableArrK::fmt), so the branches of
+// ld_moments / st_moments fold away and the fp32 instantiation is the code it was before the 16-bit formats existed.  Left as run-time branches inside the tap
+// loops they cost the fp32 two-launch conversion up to 13 %, taken once per kernel around the loops still 3 - 7 % on the one-tap horizontal kernel (same-box A/Bs
+// against the parent commit).  a.fmt == FMT is expected: the entries accept a format other than fp32 only if it is the mode's 16-bit one
+// (api_shadows.cpp to_filterable_arr), and the launchers pick FMT from a.fmt and the mode, so FMT is the one source of truth inside a kernel.
+template <unsigned FMT> MIFX_D FilterableArrK shadow_fixed_format(const FilterableArrK& a)
+{
+    FilterableArrK k = a;
+    k.fmt = FMT;
+    return k;
 }
 // Load(int4(x, y, slice, 0)).r of the depth array: 0 outside the slice
 MIFX_D float ld_shadow_depth_zero(const ShadowArrK& a, int s, int x, int y)
@@ -213,8 +258,9 @@ template <int NB, bool EVSM> MIFX_D void shadow_tile_stage_a(int i, const Shadow
 #pragma unroll
     for (int n = 0; n < NB; ++n) A[(n * kShadowTileRows + r) * kShadowTileCols + c] = b[n];
 }
-// element i of B, i < kShadowTileRows * kShadowTileW
-template <int NB> MIFX_D void shadow_tile_stage_b(int i, const ShadowTile& t, int sliceH, const float* A, float* B)
+// element i of B, i < kShadowTileRows * kShadowTileW.  fmt: the target's FilterableArrK::fmt -- the reference's intermediate target has the filterable map's own
+// format (ShadowMapManager.cpp:120-123), so the horizontal result takes the values that format keeps before the vertical pass reads it (B itself stays fp32)
+template <int NB> MIFX_D void shadow_tile_stage_b(int i, const ShadowTile& t, int sliceH, const float* A, float* B, unsigned fmt = 0u)
 {
     constexpr int CH = 2 * NB;
     const int r = i / kShadowTileW, c = i - r * kShadowTileW, gy = t.y0 + r - kShadowFusedMaxRange;
@@ -233,7 +279,7 @@ template <int NB> MIFX_D void shadow_tile_stage_b(int i, const ShadowTile& t, in
             },
             t.rH, m);
 #pragma unroll
-    for (int n = 0; n < CH; ++n) B[(n * kShadowTileRows + r) * kShadowTileW + c] = m[n];
+    for (int n = 0; n < CH; ++n) B[(n * kShadowTileRows + r) * kShadowTileW + c] = shadow_quantize(fmt, m[n]);
 }
 // the texel (lx, ly) of the tile
 template <int NB> MIFX_D void shadow_tile_stage_c(int lx, int ly, const ShadowTile& t, const FilterableArrK& dst, const float* B)

@@ -1,6 +1,5 @@
 // mifx_shadows_host.h -- the launchers of the cascaded shadow maps (shadows.hip), called by api_shadows.cpp.
-// The native-storage build of the library compiles no shadow kernels (the filterable formats of that build, RG16 / RGBA16, are out of scope): there shadows.hip defines
-// the two launchers as refusals (MIFX_ERR_NOT_IMPLEMENTED), so the entries need no check of their own.
+// Both builds of the library compile the same kernels: the filterable array names its own format (FilterableArrK::fmt), every other plane is F32 / F32X2.
 #pragma once
 #include "mifx_host.h"
 #include "mifx_shadows.h"

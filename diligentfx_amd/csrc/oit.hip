@@ -12,6 +12,12 @@
 // at the device's copy rate for the bytes its shape moves (5.3 - 5.8 TB/s beside a copy at 5.3), so the fused pair's gain is the bytes it does not move.  Streaming
 // passes, but no non-temporal hints and no row walk: no A/B of either has been measured here.
 //
+// Native-storage build (-DMIFX_STORAGE_H4).  The same kernels: the slice planes and the four targets are the build's 4-channel texel, RGBA16_FLOAT (8 bytes: the
+// 16 / 128 above become 8 / 64; a slice's opacity is the half at +6), as the reference's targets are; depth, colour alpha and the opaque depth stay F32, the tail
+// F32X2, the layers uint32.  A blend is evaluated in fp32 and its store rounds to binary16, once per draw in the sequence; oit_resolve_kernel rounds the four texels
+// in registers at the same points (quantize_v4, the identity in the fp32 build), so it still equals the sequence bit for bit while it loads and stores each target
+// once (tests/h4_checks_shadows_oit.py).
+//
 // Why the entries are here and not in an api_oit.cpp: the launcher declarations of mifx_host.h / mifx_*_host.h are mirrored by a generated block of the CPU product
 // build's stand-in (tests/cpu_product/stub_device.cpp), which a change of this kind does not regenerate; the entries therefore call the kernels directly.  Moving
 // them out is a follow-up for whoever regenerates that block.
@@ -36,7 +42,6 @@ struct mifx_oit
 // they move (profiles/oit_bench.json, tools/oit_bench.py; mifx_oit_set_fusion(0) is the sequence).
 static bool g_oit_fusion = true;
 
-#ifndef MIFX_STORAGE_H4
 namespace mifx
 {
 __global__ __launch_bounds__(256) void oit_clear_kernel(OitK k)
@@ -76,7 +81,6 @@ template <int K> __global__ __launch_bounds__(256) void oit_resolve_kernel(OitK 
     oit_px_resolve<K>(k, tab, t, x, y);
 }
 } // namespace mifx
-#endif // MIFX_STORAGE_H4
 
 namespace
 {
@@ -142,7 +146,6 @@ mifx_status frame_check(uint32_t w, uint32_t h, const mifx_oit_slice* slices, ui
     return MIFX_OK;
 }
 
-#ifndef MIFX_STORAGE_H4
 OitK make_oitk(const mifx_oit* o, const OitFrameK& f)
 {
     OitK k{};
@@ -209,15 +212,6 @@ mifx_status run_resolve(mifx_oit* o, const OitFrameK& f)
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
 }
-#endif // MIFX_STORAGE_H4
-
-// The native-storage build compiles no OIT kernels (out of scope: its targets are RGBA16_FLOAT and its tail would be RGBA8_UNORM): every entry refuses once its
-// arguments have passed every check.
-mifx_status no_oit_kernels(const char* who)
-{
-    set_error("%s: this build of the library has no order-independent-transparency kernels (the native-storage build)", who);
-    return MIFX_ERR_NOT_IMPLEMENTED;
-}
 } // namespace
 
 extern "C" {
@@ -245,9 +239,6 @@ mifx_status mifx_oit_create(mifx_postfx* ctx, uint32_t width, uint32_t height, u
     const char* who = "mifx_oit_create";
     MIFX_REQUIRE(ctx != nullptr && out != nullptr, "%s: null argument", who);
     MIFX_CHECK(create_check(width, height, layer_count, who));
-#ifdef MIFX_STORAGE_H4
-    return no_oit_kernels(who);
-#else
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
     mifx_oit* o = new mifx_oit();
     o->ctx = ctx; o->w = width; o->h = height; o->K = layer_count;
@@ -265,7 +256,6 @@ mifx_status mifx_oit_create(mifx_postfx* ctx, uint32_t width, uint32_t height, u
     }
     *out = o;
     return MIFX_OK;
-#endif
 }
 
 void mifx_oit_destroy(mifx_oit* oit) { delete oit; }
@@ -285,14 +275,10 @@ mifx_status mifx_oit_get_tail(mifx_oit* oit, mifx_image2d* out)
     return MIFX_OK;
 }
 
-#ifdef MIFX_STORAGE_H4
-#define MIFX_OIT_RUN(...) return no_oit_kernels(who)
-#else
 #define MIFX_OIT_RUN(...)                          \
     MIFX_HIP_CHECK(hipSetDevice(oit->ctx->device)); \
     __VA_ARGS__                                    \
     return MIFX_OK
-#endif
 
 // ClearOITLayers.csh, and the tail's clear value of HnBeginOITPassTask.cpp:139-144
 mifx_status mifx_oit_clear_layers(mifx_oit* oit)

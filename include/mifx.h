@@ -57,7 +57,8 @@ enum
     MIFX_FORMAT_F16       = 32,
     MIFX_FORMAT_F16X2     = 64,
     MIFX_FORMAT_R11G11B10 = 128,
-    MIFX_FORMAT_U16       = 256 /* R16_UNORM: the dilated / blurred circle of confusion of depth of field (DepthOfField.cpp:227-229) */
+    MIFX_FORMAT_U16       = 256, /* R16_UNORM: the dilated / blurred circle of confusion of depth of field (DepthOfField.cpp:227-229) */
+    MIFX_FORMAT_U16X2     = 512  /* RG16_UNORM: the 16-bit filterable shadow map of SHADOW_MODE_VSM (ShadowMapManager.cpp:98-102); both builds, see mifx_filterable_shadow_map */
 };
 /* Which texels the images have -- inputs borrowed from the caller, effect-owned planes, outputs: a property of the library build, fixed when the
  * application picks the library (the same C ABI, two shared objects):
@@ -900,14 +901,22 @@ enum /* SHADOW_MODE_*, BasicStructures.fxh:19-22 */
     MIFX_SHADOW_MODE_EVSM2 = 3,
     MIFX_SHADOW_MODE_EVSM4 = 4
 };
-/* The filterable shadow-map array (ShadowMapManager::GetFilterableSRV): caller-owned, one mip, F32X2 texels for VSM / EVSM2 and TRUE fp32 F32X4 texels for EVSM4; slice k
- * at data + k * slice_pitch_bytes.  pitch_bytes is a multiple of the texel size, data and both pitches are aligned to the texel size.  The 16-bit formats of the
- * reference (RG16_UNORM / RG16F / RGBA16F) are not built. */
+/* The filterable shadow-map array (ShadowMapManager::GetFilterableSRV): caller-owned, one mip; slice k at data + k * slice_pitch_bytes.  The format is a run-time
+ * choice in BOTH builds of the library, as in the reference (ShadowMapManager.cpp:98-102, Is32BitFilterableFmt):
+ *        mode     32-bit filterable                       16-bit filterable
+ *        VSM      MIFX_FORMAT_F32X2 (8 bytes)             MIFX_FORMAT_U16X2 (RG16_UNORM, 4 bytes)
+ *        EVSM2    MIFX_FORMAT_F32X2 (8 bytes)             MIFX_FORMAT_F16X2 (RG16_FLOAT, 4 bytes)
+ *        EVSM4    MIFX_FORMAT_F32X4 (TRUE fp32, 16 bytes) MIFX_FORMAT_F16X4 (RGBA16_FLOAT, 8 bytes)
+ * pitch_bytes is a multiple of the texel size, data and both pitches are aligned to the texel size.  A 16-bit format: a store converts the way a render-target write
+ * does (UNORM16: NaN -> 0, clamp, x 65535, + 0.5, truncate; binary16: round to nearest even, overflow -> infinity), a load widens to fp32, all arithmetic stays fp32;
+ * the intermediate target of the conversion has the map's own format (ShadowMapManager.cpp:120-123), so the horizontal pass's result is rounded too.  A 16-bit EVSM
+ * format needs attribs->bIs32BitEVSM == 0 (exp(40 d) is not a binary16 value; GetEVSMExponents then clamps the exponents to 5.54): MIFX_ERR_INVALID_ARG otherwise.
+ * bIs32BitEVSM == 0 with an fp32 format is accepted. */
 typedef struct mifx_filterable_shadow_map
 {
     void*    data;
     uint32_t width, height, slices;
-    uint32_t format; /* MIFX_FORMAT_F32X2 or MIFX_FORMAT_F32X4 */
+    uint32_t format; /* MIFX_FORMAT_F32X2 / F32X4, or the mode's 16-bit format (table above) */
     uint32_t pitch_bytes;
     uint64_t slice_pitch_bytes;
 } mifx_filterable_shadow_map;
@@ -929,7 +938,7 @@ MIFX_API mifx_status mifx_shadow_map_default_attribs(mifx_shadow_map_attribs* ou
  * work per texel is proportional to the range.  With a range above 3 in any cascade, and by default (mifx_shadow_set_conversion_fusion), the two passes are two launches
  * through an intermediate array that the context owns (grown on demand on the context's device, used on its stream, freed with the context).
  * MIFX_ERR_INVALID_ARG: shadow_map->slices != attribs->iNumCascades, more than MIFX_MAX_CASCADES, a mode outside 2 .. 4, a wrong format / size / pitch, a radius that
- * is not finite or exceeds MIFX_SHADOW_MAX_FILTER_RADIUS.  MIFX_ERR_NOT_IMPLEMENTED in the native-storage build of the library.
+ * is not finite or exceeds MIFX_SHADOW_MAX_FILTER_RADIUS.  The same in both builds of the library (depth is F32; the filterable map names its own format).
  * Kernel-timing names (mifx_postfx_set_kernel_timing): "shadow_convert_fused_kernel", "shadow_convert_two_launch", "shadow_convert_horz_kernel" (iFixedFilterSize == 2).
  * mifx_shadow_convert_check: the argument checks alone -- no context, no device, nothing read but the descriptors and the attribs. */
 #define MIFX_SHADOW_MAX_FILTER_RADIUS 16384 /* the largest slice extent the entries take: a tap count is a loop count on the device */
@@ -957,7 +966,7 @@ MIFX_API int32_t mifx_shadow_set_conversion_fusion(int32_t enable);
  *     reaches iNumCascades or more.
  *   - SampleGrad on the filterable array (one mip, ShadowMapManager.cpp:63): a bilinear, clamped fetch of mip 0 at the UV in the slice rounded to nearest; the gradients
  *     and iMaxAnisotropy are not used.  SampleCmpLevelZero: "reference < texel" on the clamped 2x2 footprint, blended with the bilinear weights.
- * MIFX_ERR_NOT_IMPLEMENTED in the native-storage build of the library. */
+ * The same in both builds of the library: depth and light amount are F32, the cascade plane F32X2, the filterable map names its own format. */
 #define MIFX_SHADOW_MAX_VARYING_PCF_TEXELS 128
 MIFX_API mifx_status mifx_shadow_map_filter_check(const mifx_image2d* depth, const mifx_camera_attribs* camera, const mifx_shadow_map_attribs* attribs,
                                                   const mifx_shadow_filter_params* params, const mifx_shadow_map_array* shadow_map,
@@ -996,7 +1005,7 @@ typedef struct mifx_oit_slice
     const mifx_image2d* specular_ibl; /* F32X4: out_specular_ibl of the same call                                                            (colour entries) */
     const mifx_image2d* color_alpha;  /* F32 or NULL: OutColor.a; NULL = base_color.a; 1 - Transmission with ENABLE_TRANSMISSION (RenderPBR.psh:515-523)      */
 } mifx_oit_slice;
-typedef struct mifx_oit_targets /* F32X4, blended in place */
+typedef struct mifx_oit_targets /* F32X4 (native-storage build: F16X4), blended in place */
 {
     const mifx_image2d* color;
     const mifx_image2d* base_color;
@@ -1005,8 +1014,11 @@ typedef struct mifx_oit_targets /* F32X4, blended in place */
 } mifx_oit_targets;
 typedef struct mifx_oit mifx_oit;
 /* PBR_Renderer::CreateOITResources (PBR/src/PBR_Renderer.cpp, OITResources: Layers = width * height * layer_count uint32, Tail).  layer_count 1 .. MIFX_OIT_MAX_LAYERS,
- * width and height 1 .. 16384.  The layers and the tail are NOT cleared.  MIFX_ERR_NOT_IMPLEMENTED in the native-storage build of the library (every entry below,
- * after the same argument checks). */
+ * width and height 1 .. 16384.  The layers and the tail are NOT cleared.
+ * Native-storage build of the library: wherever a slice plane or a target is F32X4 below it is MIFX_FORMAT_F16X4 (the reference's RGBA16_FLOAT targets); depth,
+ * color_alpha and opaque_depth stay F32, the tail F32X2, the layers uint32.  A blend is evaluated in fp32 and its store rounds to binary16, once per draw in the
+ * sequence entries; mifx_oit_resolve rounds the four texels in registers where the sequence would have stored them (after the attenuation, where it applies, and
+ * after every blended slice), so it still equals the sequence bit for bit while loading and storing each target once. */
 MIFX_API mifx_status mifx_oit_create(mifx_postfx* ctx, uint32_t width, uint32_t height, uint32_t layer_count, mifx_oit** out);
 MIFX_API void        mifx_oit_destroy(mifx_oit* oit);
 /* The reference's sequence, one launch each (kernel-timing names "oit_clear_kernel", "oit_update_kernel", "oit_attenuate_kernel", "oit_blend_kernel").

@@ -7,9 +7,11 @@ mifx_oit_build_layers and mifx_oit_resolve by the reference's sequence of launch
     sequence   build  4 K + 8 + L (2 * 4 K + 2 * 8 + 20)        resolve  128 + 4 K + 8 + L (128 + 68 + 4 K + 8)
     fused      build  L * 20 + 4 K + 8                          resolve  128 + L * 68 + 4 K + 8
 
-beside the device's own copy rate measured in the same run.
+beside the device's own copy rate measured in the same run.  Under MIFX_STORAGE=h4 (the native-storage build) the 4-channel planes are RGBA16_FLOAT: with the
+texel size T = 8 instead of 16 the 20 / 68 / 128 above are 4 + T / 4 + 4 T / 8 T.
 
-    python tools/oit_bench.py --out profiles/oit_bench.json"""
+    python tools/oit_bench.py --out profiles/oit_bench.json
+    MIFX_STORAGE=h4 python tools/oit_bench.py --out profiles/oit_bench_h4.json"""
 import argparse
 import ctypes
 import json
@@ -25,10 +27,11 @@ W, H, K = 3840, 2160, 4
 SLICES = (2, 4, 8)
 
 
-def bytes_per_pixel(shape, what, n, k=K):
+def bytes_per_pixel(shape, what, n, k=K, t=16):
+    """t: the size of a 4-channel texel, 16 (fp32 build) or 8 (native-storage build)"""
     if shape == "sequence":
-        return 4 * k + 8 + n * (2 * 4 * k + 2 * 8 + 20) if what == "build" else 128 + 4 * k + 8 + n * (128 + 68 + 4 * k + 8)
-    return n * 20 + 4 * k + 8 if what == "build" else 128 + n * 68 + 4 * k + 8
+        return 4 * k + 8 + n * (2 * 4 * k + 2 * 8 + 4 + t) if what == "build" else 8 * t + 4 * k + 8 + n * (8 * t + 4 * t + 4 + 4 * k + 8)
+    return n * (4 + t) + 4 * k + 8 if what == "build" else 8 * t + n * (4 * t + 4) + 4 * k + 8
 
 
 def main():
@@ -93,7 +96,9 @@ def main():
     lib = ctx.lib
     default_fusion = lib.mifx_oit_set_fusion(1)
     lib.mifx_oit_set_fusion(default_fusion)
-    res = {"device": torch.cuda.get_device_name(0), "frame": [w, h], "layers": K, "fusion_default": default_fusion,
+    dtype4 = B.storage_dtype()  # the 4-channel texel of the library build
+    texel = 8 if dtype4 == torch.float16 else 16
+    res = {"device": torch.cuda.get_device_name(0), "frame": [w, h], "layers": K, "fusion_default": default_fusion, "storage_mode": int(lib.mifx_storage_mode()), "texel_bytes": texel,
            "method": f"median of {args.blocks} blocks of about {args.window} s each after {args.warm} s of warm-up; sequence and fused blocks alternate"}
     # the device's own copy rate on a buffer of one target's size (read + write)
     big = torch.empty(w * h * 4 * 4, dtype=torch.float32, device=ctx.device)
@@ -111,8 +116,9 @@ def main():
     for _ in range(max(SLICES)):
         base = rnd(h, w, 4)
         base[..., 3] = 0.05 + 0.9 * base[..., 3]
-        slices.append(dict(depth=0.05 + 0.9 * rnd(h, w), base_color=base, material=rnd(h, w, 4), radiance=rnd(h, w, 4), specular_ibl=rnd(h, w, 4)))
-    targets = {k: rnd(h, w, 4) for k in api.OIT_TARGETS}
+        slices.append(dict(depth=0.05 + 0.9 * rnd(h, w), base_color=base.to(dtype4), material=rnd(h, w, 4).to(dtype4), radiance=rnd(h, w, 4).to(dtype4),
+                           specular_ibl=rnd(h, w, 4).to(dtype4)))
+    targets = {k: rnd(h, w, 4).to(dtype4) for k in api.OIT_TARGETS}
     oit = api.OITResources(ctx, w, h, K)
     px = w * h
     t_struct, keep_t = oit._targets(targets)
@@ -126,7 +132,7 @@ def main():
             us_seq, us_fused = timed_us([(lambda: lib.mifx_oit_set_fusion(0), call), (lambda: lib.mifx_oit_set_fusion(1), call)])
             for shape, us in (("sequence", us_seq), ("fused", us_fused)):
                 key = f"{what}_l{n}_{shape}"
-                res[key + "_us"], res[key + "_bytes_per_pixel"], res[key + "_TBps"] = us, bytes_per_pixel(shape, what, n), px * bytes_per_pixel(shape, what, n) / us / 1e6
+                res[key + "_us"], res[key + "_bytes_per_pixel"], res[key + "_TBps"] = us, bytes_per_pixel(shape, what, n, t=texel), px * bytes_per_pixel(shape, what, n, t=texel) / us / 1e6
             res[f"{what}_l{n}_speedup"] = us_seq / us_fused
             lib.mifx_oit_set_fusion(default_fusion)
     oit.close()

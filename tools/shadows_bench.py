@@ -4,7 +4,9 @@ blocks of about 0.05 s, the blocks of an A/B pair alternating):
   * mifx_shadow_convert_to_filterable on a 2048 x 2048 x 4 array, VSM / EVSM2 / EVSM4 at iFixedFilterSize 2, 3 and 7 -- the fused kernel against the two launches
     through a scratch array in the same process (mifx_shadow_set_conversion_fusion), with the achieved bytes per second by the algorithmic bytes of the conversion
     (4 B read + 8 or 16 B written per texel) beside the device's own copy rate measured in the same run (BASELINE.md section 5 records 5.41 - 5.77 TB/s);
-  * mifx_shadow_map_filter at 3840 x 2160 for PCF 3x3, the varying PCF and EVSM4, without and with filtering across cascades.
+  * mifx_shadow_map_filter at 3840 x 2160 for PCF 3x3, the varying PCF, VSM and EVSM4, without and with filtering across cascades.
+--filterable-bits 16: the filterable array in the reference's 16-bit formats (RG16_UNORM / RG16_FLOAT / RGBA16_FLOAT, bIs32BitEVSM = 0: 4 B read + 4 or 8 B
+written per texel); 32 (the default): fp32.  Both work in both builds of the library (MIFX_STORAGE=h4 selects the native-storage one).
 
     python tools/shadows_bench.py --out profiles/shadows_bench.json"""
 import argparse
@@ -27,8 +29,10 @@ def main():
     ap.add_argument("--warm", type=float, default=0.3, help="seconds of warm-up before every measurement")
     ap.add_argument("--window", type=float, default=0.05, help="seconds per timed block")
     ap.add_argument("--blocks", type=int, default=7, help="timed blocks per variant (alternating)")
+    ap.add_argument("--filterable-bits", type=int, choices=(16, 32), default=32, help="the filterable array's format: fp32, or the reference's 16-bit formats")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    bits = args.filterable_bits
 
     import torch
 
@@ -82,7 +86,7 @@ def main():
     ctx = api.PostFXContext(0)
     ctx.sync_stream()
     lib = ctx.lib
-    res = {"device": torch.cuda.get_device_name(0), "map": [MAP, MAP, CASCADES], "frame": [W, H], "method": f"median of {args.blocks} blocks of about {args.window} s each after {args.warm} s of warm-up; fused and two-launch blocks alternate"}
+    res = {"device": torch.cuda.get_device_name(0), "map": [MAP, MAP, CASCADES], "frame": [W, H], "filterable_bits": bits, "storage_mode": int(lib.mifx_storage_mode()), "method": f"median of {args.blocks} blocks of about {args.window} s each after {args.warm} s of warm-up; fused and two-launch blocks alternate"}
     # the device's own copy rate on a buffer of the EVSM4 target's size (read + write)
     big = torch.empty(MAP * MAP * CASCADES * 4, dtype=torch.float32, device=ctx.device)
     dst = torch.empty_like(big)
@@ -98,11 +102,12 @@ def main():
     res["fusion_default"] = default_fusion
     for mode, name in ((S.MODE_VSM, "vsm"), (S.MODE_EVSM2, "evsm2"), (S.MODE_EVSM4, "evsm4")):
         ch = 4 if mode == S.MODE_EVSM4 else 2
-        out = torch.empty((CASCADES, MAP, MAP, ch), dtype=torch.float32, device=ctx.device)
+        dtype = torch.float32 if bits == 32 else (torch.int16 if mode == S.MODE_VSM else torch.float16)
+        out = torch.empty((CASCADES, MAP, MAP, ch), dtype=dtype, device=ctx.device)
         dstm = B.filterable_shadow_map(out)
-        nbytes = MAP * MAP * CASCADES * (4 + 4 * ch)
+        nbytes = MAP * MAP * CASCADES * (4 + (bits // 8) * ch)
         for fs in (2, 3, 7):
-            A = S.make_attribs(CASCADES, MAP, MAP, iFixedFilterSize=fs)
+            A = S.make_attribs(CASCADES, MAP, MAP, iFixedFilterSize=fs, bIs32BitEVSM=int(bits == 32))
             call = lambda: B.check(lib.mifx_shadow_convert_to_filterable(ctx.handle, ctypes.byref(src), ctypes.byref(A), ctypes.c_uint32(mode), ctypes.byref(dstm)))  # noqa: E731
             us_fused, us_two = timed_us([(lambda: lib.mifx_shadow_set_conversion_fusion(1), call), (lambda: lib.mifx_shadow_set_conversion_fusion(0), call)])
             for key, us in ((f"convert_{name}_f{fs}_fused", us_fused), (f"convert_{name}_f{fs}_two_launch", us_two)):
@@ -118,13 +123,14 @@ def main():
     light = torch.empty_like(frame)
     casc = torch.empty((H, W, 2), dtype=torch.float32, device=ctx.device)
     d, o, c = B.image(frame), B.image(light), B.image(casc)
-    fm4 = B.filterable_shadow_map(filterable[S.MODE_EVSM4])
-    for name, mode, over in (("pcf3", S.MODE_PCF, dict(iFixedFilterSize=3)), ("pcf_varying", S.MODE_PCF, dict(iFixedFilterSize=0, fFilterWorldSize=0.05)), ("evsm4", S.MODE_EVSM4, dict())):
-        A = S.make_attribs(CASCADES, MAP, MAP, **over)
+    fms = {m: B.filterable_shadow_map(t) for m, t in filterable.items()}
+    for name, mode, over in (("pcf3", S.MODE_PCF, dict(iFixedFilterSize=3)), ("pcf_varying", S.MODE_PCF, dict(iFixedFilterSize=0, fFilterWorldSize=0.05)), ("vsm", S.MODE_VSM, dict()),
+                             ("evsm4", S.MODE_EVSM4, dict())):
+        A = S.make_attribs(CASCADES, MAP, MAP, bIs32BitEVSM=int(bits == 32), **over)
         for across in (0, 1):
             p = B.ShadowFilterParams(mode, across, 0, 0)
             call = lambda: B.check(lib.mifx_shadow_map_filter(ctx.handle, ctypes.byref(d), ctypes.byref(cam_s), ctypes.byref(A), ctypes.byref(p),  # noqa: E731
-                                                                  ctypes.byref(src) if mode == S.MODE_PCF else None, ctypes.byref(fm4) if mode != S.MODE_PCF else None,
+                                                                  ctypes.byref(src) if mode == S.MODE_PCF else None, ctypes.byref(fms[mode]) if mode != S.MODE_PCF else None,
                                                                   ctypes.byref(o), ctypes.byref(c)))
             res[f"filter_{name}{'_across' if across else ''}_us"], = timed_us([(nothing, call)])
     ctx.close()
