@@ -383,6 +383,53 @@ def pbr_shade_layers(ctx: "PostFXContext", gbuffer: dict, layers: dict, flags: i
     return out_radiance, out_specular_ibl
 
 
+def pbr_shade_output(ctx: "PostFXContext", gbuffer: dict, layers, flags: int, camera: B.CameraAttribs, attribs: B.PBRShadeAttribs, ibl: IBLResources, output: dict = None,
+                     shadows=None, motion=None, mesh_normal=None, background=(0.0, 0.0, 0.0, 0.0), iridescence_ior=1.3, anisotropy_rotation=0.0, want_specular_ibl=True,
+                     out_color=None, out_specular_ibl=None):
+    """The shade with its output stage (mifx_pbr_shade_output): debug views, in-shader tone mapping, alpha modes, unlit, highlight, loading animation, sRGB.
+    layers / flags: as pbr_shade_layers(), or None / 0 for no layer.  output: dict with `renderer` (binding.PBRRendererShaderParameters) and any of debug_view,
+    tone_mapping_mode, loading_animation, alpha_mode, alpha_mask_cutoff, unlit, flags (the fields of mifx_pbr_shade_output_desc).  motion: F32X2 plane, mesh_normal: 4-channel
+    plane, or None.  shadows: as pbr_shade().  Returns (color, specular_ibl)."""
+    ref = gbuffer["depth"]
+    h, w = ref.shape
+    if out_color is None:
+        out_color = torch.empty(h, w, 4, device=ref.device, dtype=B.storage_dtype())
+    if out_specular_ibl is None and want_specular_ibl:
+        out_specular_ibl = torch.empty(h, w, 4, device=ref.device, dtype=B.storage_dtype())
+    imgs = {k: B.image(gbuffer[k]) for k in ("base_color", "normal", "material", "depth", "emissive", "occlusion") if gbuffer.get(k) is not None}
+    p = lambda k: ctypes.pointer(imgs[k]) if k in imgs else None  # noqa: E731
+    g = B.GBuffer(p("base_color"), p("normal"), p("material"), p("depth"), p("emissive"), p("occlusion"))
+    ly = None
+    if layers is not None and flags:
+        limgs = {k: B.image(layers[k]) for k in B.PBR_LAYER_PLANES if layers.get(k) is not None}
+        ly = B.PBRLayers(flags, iridescence_ior, anisotropy_rotation, 0, *[ctypes.pointer(limgs[k]) if k in limgs else None for k in B.PBR_LAYER_PLANES])
+    output = dict(output or {})
+    renderer = output.pop("renderer", None)
+    mi = B.image(motion) if motion is not None else None
+    ni = B.image(mesh_normal) if mesh_normal is not None else None
+    desc = B.PBRShadeOutputDesc(ctypes.pointer(renderer) if renderer is not None else None, output.pop("debug_view", 0), output.pop("tone_mapping_mode", 0),
+                                output.pop("loading_animation", 0), output.pop("alpha_mode", 0), output.pop("alpha_mask_cutoff", 0.5), int(output.pop("unlit", 0)),
+                                output.pop("flags", 0), 0, ctypes.pointer(mi) if mi is not None else None, ctypes.pointer(ni) if ni is not None else None)
+    assert not output, f"unknown fields of mifx_pbr_shade_output_desc: {sorted(output)}"
+    o0 = B.image(out_color)
+    o1 = B.image(out_specular_ibl) if out_specular_ibl is not None else None
+    bg = (ctypes.c_float * 4)(*background)
+    ctx.sync_stream()
+    sh = None
+    if shadows is not None:
+        sm, infos, pcf = shadows
+        assert sm.dtype == torch.float32 and sm.dim() == 3 and sm.is_contiguous()
+        arr = B.ShadowMapArray(sm.data_ptr(), sm.shape[2], sm.shape[1], sm.shape[0], sm.stride(1) * 4, sm.stride(0) * 4)
+        rows = (B.PBRShadowMapInfo * len(infos))()
+        for i, r in enumerate(infos):
+            rows[i] = r if isinstance(r, B.PBRShadowMapInfo) else B.PBRShadowMapInfo.from_buffer_copy(r.astype("float32").tobytes())
+        sh = B.PBRShadows(ctypes.pointer(arr), ctypes.cast(rows, ctypes.POINTER(B.PBRShadowMapInfo)), len(infos), pcf)
+    B.check(ctx.lib.mifx_pbr_shade_output(ctx.handle, ctypes.byref(g), ctypes.byref(ly) if ly is not None else None, ctypes.byref(camera), ctypes.byref(attribs),
+                                          ctypes.byref(ibl.struct), ctypes.byref(sh) if sh is not None else None, ctypes.byref(desc), bg, ctypes.byref(o0),
+                                          ctypes.byref(o1) if o1 is not None else None))
+    return out_color, out_specular_ibl
+
+
 HYDROGENT_GBUFFER_FORMATS = {"base_color": "RGBA8_UNORM", "normal": "RGBA16_FLOAT", "material": "RG8_UNORM", "depth": "R32_FLOAT", "emissive": "RGBA16_FLOAT",
                              "occlusion": "R8_UNORM"}  # HnBeginFrameTask.cpp:63-69 (emissive / occlusion are not Hydrogent targets: same classes of format)
 

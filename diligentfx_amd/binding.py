@@ -205,6 +205,25 @@ class PBRLayers(ctypes.Structure):  # mifx_pbr_layers
     _fields_ = [("flags", c_u), ("iridescence_ior", c_f), ("anisotropy_rotation", c_f), ("padding", c_u)] + [(n, PImage) for n in PBR_LAYER_PLANES]
 
 
+# PBR_Renderer::DebugViewType (PBR/interface/PBR_Renderer.hpp:401-439): PBR_DEBUG_VIEW_NONE = 0 ... PBR_DEBUG_VIEW_SCENE_DEPTH = 34
+PBR_DEBUG_VIEWS = ("NONE", "TEXCOORD0", "TEXCOORD1", "BASE_COLOR", "TRANSPARENCY", "OCCLUSION", "EMISSIVE", "METALLIC", "ROUGHNESS", "DIFFUSE_COLOR", "SPECULAR_COLOR",
+                   "REFLECTANCE90", "MESH_NORMAL", "SHADING_NORMAL", "MOTION_VECTORS", "NDOTV", "PUNCTUAL_LIGHTING", "DIFFUSE_IBL", "SPECULAR_IBL", "WHITE_BASE_COLOR", "CLEAR_COAT",
+                   "CLEAR_COAT_FACTOR", "CLEAR_COAT_ROUGHNESS", "CLEAR_COAT_NORMAL", "SHEEN", "SHEEN_COLOR", "SHEEN_ROUGHNESS", "ANISOTROPY_STRENGTH", "ANISOTROPY_DIRECTION",
+                   "IRIDESCENCE", "IRIDESCENCE_FACTOR", "IRIDESCENCE_THICKNESS", "TRANSMISSION", "THICKNESS", "SCENE_DEPTH")
+for _i, _n in enumerate(PBR_DEBUG_VIEWS):
+    globals()["PBR_DEBUG_VIEW_" + _n] = _i
+PBR_DEBUG_VIEW_COUNT = len(PBR_DEBUG_VIEWS)
+PBR_LOADING_ANIMATION_NONE, PBR_LOADING_ANIMATION_ALWAYS, PBR_LOADING_ANIMATION_TRANSITIONING = 0, 1, 2  # PBR_Renderer.hpp:441-447
+PBR_ALPHA_MODE_OPAQUE, PBR_ALPHA_MODE_MASK, PBR_ALPHA_MODE_BLEND = 0, 1, 2  # PBR_Structures.fxh:34-44
+PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB = 1
+TONE_MAPPING_MODES = ("NONE", "EXP", "REINHARD", "REINHARD_MOD", "UNCHARTED2", "FILMIC_ALU", "LOGARITHMIC", "ADAPTIVE_LOG", "AGX", "AGX_CUSTOM", "PBR_NEUTRAL", "COMMERCE")
+
+
+class PBRShadeOutputDesc(ctypes.Structure):  # mifx_pbr_shade_output_desc
+    _fields_ = [("renderer", ctypes.POINTER(PBRRendererShaderParameters)), ("debug_view", c_i), ("tone_mapping_mode", c_i), ("loading_animation", c_i), ("alpha_mode", c_i),
+                ("alpha_mask_cutoff", c_f), ("unlit", c_i), ("flags", c_u), ("padding", c_u), ("motion", PImage), ("mesh_normal", PImage)]
+
+
 class NativeImage(ctypes.Structure):  # mifx_native_image
     _fields_ = [("data", c_p), ("width", c_u), ("height", c_u), ("pitch_bytes", c_u), ("format", c_u)]
 
@@ -472,7 +491,7 @@ class CommStats(ctypes.Structure):  # mifx_comm_stats
                 ("timed_groups", ctypes.c_uint32), ("exchange_ms_total", ctypes.c_float), ("exchange_ms_max", ctypes.c_float)]
 
 
-SIZEOF_NAMES.update({"shard_info": ShardInfo, "comm_stats": CommStats, "oit_slice": OITSlice, "oit_targets": OITTargets})
+SIZEOF_NAMES.update({"pbr_shade_output_desc": PBRShadeOutputDesc, "shard_info": ShardInfo, "comm_stats": CommStats, "oit_slice": OITSlice, "oit_targets": OITTargets})
 
 
 class MifxError(RuntimeError):

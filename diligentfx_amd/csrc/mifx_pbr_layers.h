@@ -213,11 +213,38 @@ struct LayersK
 // SET: the layer set as a compile-time constant (the launcher instantiates each single layer and all five: the branches fold, and the permutation costs what it uses), or
 // kLayersRuntime: the set is read from LayersK::flags (any other combination; uniform branches, but the register budget of all five layers).  SHADOWS = ENABLE_SHADOWS
 // (the PCF filter alone costs ~55 registers: a template parameter as in the default shade).
+// TERMS: NoShadeTerms (every existing caller: nothing below exists for it), or ShadeTerms -- the shade's output stage (mifx_pbr_output.h) hands in what must act before the
+// lighting (the mask test, the white base colour) and takes back the intermediate terms its debug views show.
 constexpr unsigned kLayersRuntime = 0xffffffffu;
-template <bool APRON, unsigned SET, bool SHADOWS>
+struct NoShadeTerms { static constexpr bool kWanted = false; };
+struct ShadeTerms
+{
+    static constexpr bool kWanted = true;
+    // in
+    bool  maskTest;       // PBR_ALPHA_MODE_MASK: BaseColor.a < cutoff is discarded (RenderPBR.psh:460-465) -- here: a background pixel
+    float alphaMaskCutoff;
+    bool  whiteBaseColor; // DEBUG_VIEW_WHITE_BASE_COLOR (:467-471)
+    // out
+    bool  background;     // no fragment: outColor / outSpec hold the background, nothing else below is set
+    v4    baseColor;      // BaseColor as the lighting saw it
+    float depth, metallic, NdotV, occlusion;
+    v3    pos, N, emissive;
+    SurfaceReflectance srf;                    // BaseLayer.Srf (after the iridescence blend of :340-343)
+    v3    punctual, diffuseIBL, specularIBL;   // SrfLighting.Base
+    v3    clearcoatLighting, sheenLighting;    // GetClearcoatLighting / GetSheenLighting (PBR_Shading.fxh:826-845)
+    float clearcoatFactor, clearcoatRoughness;
+    v3    clearcoatNormal, sheenColor;
+    float sheenRoughness, anisotropyStrength;
+    v2    anisotropyDirection;
+    v3    iridescenceFresnel;
+    float iridescenceFactor, iridescenceThickness, transmission;
+};
+MIFX_D v4 shade_terms_base_color(v4 texel, const NoShadeTerms*) { return texel; }
+MIFX_D v4 shade_terms_base_color(v4 texel, const ShadeTerms* t) { return t->whiteBaseColor ? v4{1.0f, 1.0f, 1.0f, texel.w} : texel; }
+template <bool APRON, unsigned SET, bool SHADOWS, class TERMS = NoShadeTerms>
 MIFX_D void pbr_shade_layers_pixel(int x, int y, const Img& baseColor, const Img& normalTex, const Img& material, const Img& depthTex, const Img& emissive, const Img& occlusion,
                                    const LutK& lut, const v4* irradiance0, int irradianceSize, const v4* const* prefMips, int prefSize, int prefLevels, const CamK& cam,
-                                   const ShadeK& k, const LayersK& ly, int hasEmissive, int hasAo, const ShadowK& sh, v4& outColor, v4& outSpec)
+                                   const ShadeK& k, const LayersK& ly, int hasEmissive, int hasAo, const ShadowK& sh, v4& outColor, v4& outSpec, TERMS* terms = nullptr)
 {
     auto irradianceAt = [&](v3 d) { return APRON ? cube_sample_level_apron(irradiance0, irradianceSize, d) : cube_sample_level(irradiance0, irradianceSize, d); };
     auto prefilteredAt = [&](v3 d, float lod) { return APRON ? cube_sample_apron(prefMips, prefSize, prefLevels, d, lod) : cube_sample(prefMips, prefSize, prefLevels, d, lod); };
@@ -226,12 +253,23 @@ MIFX_D void pbr_shade_layers_pixel(int x, int y, const Img& baseColor, const Img
     {
         outColor = v4{k.background[0], k.background[1], k.background[2], k.background[3]};
         outSpec  = mk4(0.0f);
+        if constexpr (TERMS::kWanted) terms->background = true;
         return;
     }
     const unsigned set = SET == kLayersRuntime ? ly.flags : SET;
     const bool clearCoat = (set & MIFX_PBR_LAYER_CLEAR_COAT) != 0u, sheen = (set & MIFX_PBR_LAYER_SHEEN) != 0u, aniso = (set & MIFX_PBR_LAYER_ANISOTROPY) != 0u;
     const bool irid = (set & MIFX_PBR_LAYER_IRIDESCENCE) != 0u, transm = (set & MIFX_PBR_LAYER_TRANSMISSION) != 0u;
-    const v4 bc  = ld<v4>(baseColor, x, y);
+    const v4 bc  = shade_terms_base_color(ld<v4>(baseColor, x, y), terms);
+    if constexpr (TERMS::kWanted)
+    {
+        terms->background = terms->maskTest && bc.w < terms->alphaMaskCutoff;
+        if (terms->background)
+        {
+            outColor = v4{k.background[0], k.background[1], k.background[2], k.background[3]};
+            outSpec  = mk4(0.0f);
+            return;
+        }
+    }
     const v4 mat = ld<v4>(material, x, y);
     const v3 N   = xyz(ld<v4>(normalTex, x, y));
     const v3 pos  = inv_project_position(v3{(float(x) + 0.5f) * cam.ivw, (float(y) + 0.5f) * cam.ivh, depth}, cam.viewProjInv);
@@ -398,5 +436,28 @@ MIFX_D void pbr_shade_layers_pixel(int x, int y, const Img& baseColor, const Img
     }
     outColor = mk4(color, bc.w);
     outSpec  = mk4(specularIBL * iblScale * occl, 1.0f); // GetBaseLayerSpecularIBL (:801-805)
+    if constexpr (TERMS::kWanted)
+    {
+        terms->baseColor = bc;
+        terms->depth = depth; terms->NdotV = baseNdotV; terms->occlusion = occl;
+        terms->pos = pos; terms->N = N; terms->emissive = emis;
+        terms->srf = srf;
+        terms->punctual = basePunctualSum; terms->diffuseIBL = diffuseIBL; terms->specularIBL = specularIBL;
+        terms->clearcoatLighting = clearCoat ? ccPunctual * ccFactor + ccIBL * iblScale * occl * ccFactor : mk3(0.0f);
+        terms->sheenLighting     = sheen ? sheenPunctual + sheenIBL * iblScale * occl : mk3(0.0f);
+        terms->clearcoatFactor = ccFactor; terms->clearcoatRoughness = ccSrf.perceptualRoughness; terms->clearcoatNormal = ccN;
+        terms->sheenColor = sheenColor; terms->sheenRoughness = sheenRoughness;
+        terms->anisotropyStrength = an.strength;
+        // what only a view shows (Metallic of GetSurfaceReflectance, PBR_Shading.fxh:401,408; Anisotropy.Direction, RenderPBR.psh:264-266; Iridescence.Thickness, :246)
+        terms->metallic = k.workflow == MIFX_PBR_WORKFLOW_SPECULAR_GLOSSINESS ? unusedMetallic : saturate(mat.y * 1.0f);
+        terms->anisotropyDirection = v2{0.0f, 0.0f};
+        if (aniso)
+        {
+            const v4 packed = ld<v4>(ly.anisotropy, x, y);
+            terms->anisotropyDirection = v2{packed.x * ly.rotationCos - packed.y * ly.rotationSin, packed.x * ly.rotationSin + packed.y * ly.rotationCos};
+        }
+        terms->iridescenceFresnel = iridFresnel; terms->iridescenceFactor = iridFactor; terms->iridescenceThickness = irid ? ld<v4>(ly.iridescence, x, y).y : 0.0f;
+        terms->transmission = transmission;
+    }
 }
 } // namespace mifx

@@ -5,10 +5,12 @@
 //     world position rebuilt from depth with InvProjectPosition (PostFX_Common.fxh:99-105).  84 B/px: base colour, normal, material
 //     (3 x 16 B) + depth (4 B) in, radiance + specular IBL (2 x 16 B) out; LUT and cube maps are cache-resident (<= 9 MB).
 #include "mifx_host.h"
+#include "mifx_objects.h"
 #include <cmath>
 #include <cstdlib>
 #include "mifx_pbr.h"
 #include "mifx_pbr_layers.h"
+#include "mifx_pbr_output.h"
 #include "mifx_effects.h"
 #include "mifx_tonemap.h"
 #include "mifx_formats.h"
@@ -312,6 +314,27 @@ __global__ __launch_bounds__(256) void pbr_hit_fetch_layers_kernel(Img baseColor
     px_st(out, x, y, color);
 }
 
+#ifndef MIFX_STORAGE_H4
+// the shade with its output stage (mifx_pbr_output.h: the debug views, in-shader tone mapping, highlight, loading animation, alpha modes, sRGB): the layered body with the
+// set as a run-time mask -- a view shows any set -- and the tail behind it.  TM = TONE_MAPPING_MODE (0: ENABLE_TONE_MAPPING off), instantiated as tonemap.hip does.
+// Not the timed path; not in the native-storage build (mifx_pbr_shade_output returns MIFX_ERR_NOT_IMPLEMENTED there).
+template <int TM, bool SHADOWS>
+__global__ __launch_bounds__(256) void pbr_shade_output_kernel(Img baseColor, Img normalTex, Img material, Img depthTex, Img emissive, Img occlusion, LutK lut, CubeK irradiance,
+                                                               CubeK prefiltered, Img outColor, Img outSpecIBL, CamK cam, ShadeK k, LayersK ly, int hasEmissive, int hasAo, int writeSpec,
+                                                               ShadowK sh, OutputK o, Img motion, Img meshNormal)
+{
+    __shared__ const v4* prefMips[12];
+    stage_cube_mips(prefMips, prefiltered);
+    int x, y;
+    if (!pixel_xy(outColor, x, y)) return;
+    v4 color, spec;
+    pbr_shade_output_pixel<true, SHADOWS, TM>(x, y, baseColor, normalTex, material, depthTex, emissive, occlusion, lut, irradiance.mip[0], irradiance.size, prefMips, prefiltered.size,
+                                              prefiltered.mips, cam, k, ly, hasEmissive, hasAo, sh, o, motion, meshNormal, color, spec);
+    st<v4>(outColor, x, y, color);
+    if (writeSpec) st<v4>(outSpecIBL, x, y, spec);
+}
+#endif
+
 static mifx_status make_cubek(const mifx_cubemap* c, const char* what, CubeK& k)
 {
     MIFX_REQUIRE(c != nullptr && c->size > 0 && c->mip_count > 0 && c->mip_count <= 12, "%s: bad cube map", what);
@@ -466,10 +489,17 @@ static mifx_status make_lutk_r(const mifx_image2d* im, const char* what, LutK& k
     k.pitch_f = int(im->pitch_bytes / 4u);
     return MIFX_OK;
 }
-mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
-                                    const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec,
-                                    int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const LayeredHitFetch* hit)
+// the shade's output stage behind the layered body (mifx_pbr_shade_output, at the end of this file): `out_radiance` is then PSOut.Color
+struct ShadeOutputStage
 {
+    const mifx_pbr_shade_output_desc* desc; // validated by the entry
+};
+static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
+                                                const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance,
+                                                const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows,
+                                                const LayeredHitFetch* hit, const ShadeOutputStage* stage)
+{
+    MIFX_REQUIRE(stage == nullptr || hit == nullptr, "mifx_pbr_shade_output: the output stage is not combined with the hit fetch");
     const uint32_t known = MIFX_PBR_LAYER_CLEAR_COAT | MIFX_PBR_LAYER_SHEEN | MIFX_PBR_LAYER_ANISOTROPY | MIFX_PBR_LAYER_IRIDESCENCE | MIFX_PBR_LAYER_TRANSMISSION;
     MIFX_REQUIRE((layers.flags & ~known) == 0u, "layers: unknown flag bits 0x%x", layers.flags & ~known);
     Img bc, nrm, mat, depth, emis{}, occ{}, outR, outS{};
@@ -529,7 +559,35 @@ mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, cons
     MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k));
     const CamK cam = make_camk(camera, reversedDepth);
     const dim3 block(64, 4, 1);
-    if (hit != nullptr)
+    if (stage != nullptr)
+    {
+#ifndef MIFX_STORAGE_H4
+        Img motion{}, meshNormal{};
+        if (stage->desc->motion) MIFX_CHECK(to_img_wh(stage->desc->motion, MIFX_FORMAT_F32X2, W, H, "output.motion", motion));
+        if (stage->desc->mesh_normal) MIFX_CHECK(to_img_wh(stage->desc->mesh_normal, MIFX_FORMAT_F32X4, W, H, "output.mesh_normal", meshNormal));
+        const mifx_pbr_shade_output_desc& d = *stage->desc; // (validated by mifx_pbr_shade_output)
+        const mifx_pbr_renderer_shader_parameters& r = *d.renderer;
+        OutputK o{};
+        o.debugView = d.debug_view; o.loadingAnimation = d.loading_animation; o.alphaMode = d.alpha_mode; o.unlit = d.unlit != 0;
+        o.srgb = (d.flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0u;
+        o.hasMotion = d.motion != nullptr; o.hasMeshNormal = d.mesh_normal != nullptr;
+        o.alphaMaskCutoff = d.alpha_mask_cutoff;
+        o.tm = ToneMapK{r.MiddleGray, r.WhitePoint, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, r.AverageLogLum, 0};
+        for (int i = 0; i < 4; ++i) o.highlight[i] = r.HighlightColor[i];
+        o.time = r.Time; o.worldScale = r.LoadingAnimation.WorldScale; o.speed = r.LoadingAnimation.Speed;
+        o.factor = d.loading_animation == MIFX_PBR_LOADING_ANIMATION_TRANSITIONING ? r.LoadingAnimation.Factor : 1.0f; // RenderPBR.psh:617-622
+        for (int i = 0; i < 3; ++i) { o.color0[i] = r.LoadingAnimation.Color0[i]; o.color1[i] = r.LoadingAnimation.Color1[i]; }
+        o.sceneNearZ = camera.fSceneNearZ; o.sceneFarZ = camera.fSceneFarZ;
+#define MIFX_OUTPUT_INSTANCE(TM)                                                                                                                                                     \
+    hipLaunchKernelGGL((shadows ? pbr_shade_output_kernel<TM, true> : pbr_shade_output_kernel<TM, false>), grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, \
+                       outR, outS, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, out_spec ? 1 : 0, sh, o, motion, meshNormal)
+        MIFX_TONEMAP_DISPATCH(d.tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
+#undef MIFX_OUTPUT_INSTANCE
+#else
+        MIFX_REQUIRE(false, "mifx_pbr_shade_output: the output stage is not part of the native-storage build");
+#endif
+    }
+    else if (hit != nullptr)
     {
         const HitOut out{hit->rays, hit->coords, outR, hit->shadedBegin, hit->shadedEnd};
         hipLaunchKernelGGL(shadows ? pbr_hit_fetch_layers_kernel<true> : pbr_hit_fetch_layers_kernel<false>, grid2d(hit->rays, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr,
@@ -557,6 +615,13 @@ mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, cons
     }
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
+}
+
+mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
+                                    const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec,
+                                    int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const LayeredHitFetch* hit)
+{
+    return launch_pbr_shade_layers_impl(s, iblApron, g, layers, camera, a, ibl, background, out_radiance, out_spec, row_begin, row_end, reversedDepth, shadows, hit, nullptr);
 }
 
 mifx_status launch_pbr_hit_fetch(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
@@ -665,3 +730,45 @@ mifx_status launch_specgloss_material(hipStream_t s, Img baseColor, Img physical
 }
 
 } // namespace mifx
+
+// The C entry of the shade's output stage lives beside its kernel (as the OIT entries do in oit.hip): a build of the host objects alone neither has nor needs it.
+using namespace mifx;
+extern "C" {
+mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
+                                  const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
+                                  const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_specular_ibl)
+{
+    // (every argument check precedes the first device call)
+    MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && output != nullptr && out_color != nullptr,
+                 "mifx_pbr_shade_output: null argument");
+    MIFX_REQUIRE(output->renderer != nullptr, "mifx_pbr_shade_output: output->renderer is null (the PBRRendererShaderParameters block of the frame)");
+    MIFX_REQUIRE(output->debug_view >= 0 && output->debug_view < MIFX_PBR_DEBUG_VIEW_COUNT, "mifx_pbr_shade_output: debug view %d outside [0, %d)", output->debug_view,
+                 int(MIFX_PBR_DEBUG_VIEW_COUNT));
+    MIFX_REQUIRE(output->tone_mapping_mode >= 0 && output->tone_mapping_mode <= MIFX_TONE_MAPPING_MODE_COMMERCE, "mifx_pbr_shade_output: unknown tone mapping mode %d",
+                 output->tone_mapping_mode);
+    MIFX_REQUIRE(output->tone_mapping_mode != MIFX_TONE_MAPPING_MODE_AGX_CUSTOM,
+                 "mifx_pbr_shade_output: TONE_MAPPING_MODE_AGX_CUSTOM: the shader's ToneMappingAttribs carry no AgX look parameters (RenderPBR.psh:533-539)");
+    MIFX_REQUIRE(output->loading_animation >= MIFX_PBR_LOADING_ANIMATION_NONE && output->loading_animation <= MIFX_PBR_LOADING_ANIMATION_TRANSITIONING,
+                 "mifx_pbr_shade_output: unknown loading animation mode %d", output->loading_animation);
+    MIFX_REQUIRE(output->alpha_mode >= MIFX_PBR_ALPHA_MODE_OPAQUE && output->alpha_mode <= MIFX_PBR_ALPHA_MODE_BLEND, "mifx_pbr_shade_output: unknown alpha mode %d", output->alpha_mode);
+    MIFX_REQUIRE((output->flags & ~MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) == 0u, "mifx_pbr_shade_output: unknown flag bits 0x%x",
+                 output->flags & ~MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB);
+    const int view = output->debug_view;
+    MIFX_REQUIRE(!output->unlit || view == MIFX_PBR_DEBUG_VIEW_NONE || view == MIFX_PBR_DEBUG_VIEW_BASE_COLOR || view == MIFX_PBR_DEBUG_VIEW_TRANSPARENCY ||
+                     view == MIFX_PBR_DEBUG_VIEW_WHITE_BASE_COLOR,
+                 "mifx_pbr_shade_output: debug view %d shows a lighting term, which an unlit material (PBR_WORKFLOW_UNLIT) does not have", view);
+#ifdef MIFX_STORAGE_H4
+    (void)layers; (void)shadows; (void)background; (void)out_specular_ibl;
+    ::mifx::set_error("mifx_pbr_shade_output: the shade's output stage is not part of the native-storage build yet");
+    return MIFX_ERR_NOT_IMPLEMENTED;
+#else
+    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
+    const mifx_pbr_layers none{};
+    const Rows rows = ctx->needed_rows(int(out_color->height));
+    MifxKernelTimer timer(ctx, "pbr_shade_output_kernel");
+    const ShadeOutputStage stage{output};
+    return launch_pbr_shade_layers_impl(ctx->stream, ctx->ibl_apron, gbuffer, layers ? *layers : none, *camera, *attribs, ibl, background, out_color, out_specular_ibl, rows.b, rows.e,
+                                   (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, nullptr, &stage);
+#endif
+}
+} // extern "C"

@@ -657,6 +657,61 @@ typedef struct mifx_pbr_material_transmission_attribs /* PBRMaterialTransmission
 MIFX_API mifx_status mifx_pbr_layers_from_material_info(const void* material_info, uint64_t bytes, uint32_t layer_flags, int32_t enable_volume, uint32_t num_texture_attribs,
                                                         mifx_pbr_layers* layers, mifx_pbr_material_basic_attribs* out_basic);
 
+/* The shade's output stage: what `main` of Shaders/PBR/private/RenderPBR.psh does after ResolveLighting (:515-643) -- the debug views, the tone mapping inside the forward
+ * pass, the alpha modes, the unlit workflow, the selection highlight, the loading animation and the sRGB output -- on top of the layered shade, in one kernel.  The stages run
+ * in the shader's order: white base colour (:467-471) -> lighting (:473-528) -> tone map (:530-542) -> premultiply (:545-547) -> highlight lerp (:562) -> debug view
+ * (:574-613, GetDebugColor PBR_Shading.fxh:879-989) -> loading animation (:615-630) -> alpha (:633-637) -> sRGB (:639-643).  `out_color` is PSOut.Color, alpha included
+ * (BaseColor.a, or 1 - Transmission with the transmission layer, forced to 1 unless the mode is BLEND); `out_specular_ibl` is what mifx_pbr_shade_execute_layers writes.
+ * Background pixels get `background` and a zero `out_specular_ibl`.  With no rasteriser behind the entry a pixel that PBR_ALPHA_MODE_MASK discards (:460-465) is treated
+ * exactly as a background pixel.  What the G-buffer cannot carry falls through to black as in the shader's own permutation without it: TEXCOORD0 / TEXCOORD1 (no
+ * USE_TEXCOORD0 / 1), THICKNESS (no ENABLE_VOLUME), and a layer's views with that layer off in layers->flags.  Out of scope: the OIT transmittance of :548-558,632
+ * (mifx_oit_blend applies it), PRIMITIVE.CustomData, and the rewrites of the material / normal / IBL targets that the USD renderer's footer makes under clear coat and the
+ * loading animation (Hydrogent USD_Renderer.cpp:101-124).  In the native-storage build the entry returns MIFX_ERR_NOT_IMPLEMENTED. */
+enum /* PBR_Renderer::DebugViewType, PBR/interface/PBR_Renderer.hpp:401-439 (the values of the DEBUG_VIEW_* macros, PBR_Renderer.cpp:1439-1474) */
+{
+    MIFX_PBR_DEBUG_VIEW_NONE = 0, MIFX_PBR_DEBUG_VIEW_TEXCOORD0, MIFX_PBR_DEBUG_VIEW_TEXCOORD1, MIFX_PBR_DEBUG_VIEW_BASE_COLOR, MIFX_PBR_DEBUG_VIEW_TRANSPARENCY,
+    MIFX_PBR_DEBUG_VIEW_OCCLUSION, MIFX_PBR_DEBUG_VIEW_EMISSIVE, MIFX_PBR_DEBUG_VIEW_METALLIC, MIFX_PBR_DEBUG_VIEW_ROUGHNESS, MIFX_PBR_DEBUG_VIEW_DIFFUSE_COLOR,
+    MIFX_PBR_DEBUG_VIEW_SPECULAR_COLOR, MIFX_PBR_DEBUG_VIEW_REFLECTANCE90, MIFX_PBR_DEBUG_VIEW_MESH_NORMAL, MIFX_PBR_DEBUG_VIEW_SHADING_NORMAL,
+    MIFX_PBR_DEBUG_VIEW_MOTION_VECTORS, MIFX_PBR_DEBUG_VIEW_NDOTV, MIFX_PBR_DEBUG_VIEW_PUNCTUAL_LIGHTING, MIFX_PBR_DEBUG_VIEW_DIFFUSE_IBL, MIFX_PBR_DEBUG_VIEW_SPECULAR_IBL,
+    MIFX_PBR_DEBUG_VIEW_WHITE_BASE_COLOR, MIFX_PBR_DEBUG_VIEW_CLEAR_COAT, MIFX_PBR_DEBUG_VIEW_CLEAR_COAT_FACTOR, MIFX_PBR_DEBUG_VIEW_CLEAR_COAT_ROUGHNESS,
+    MIFX_PBR_DEBUG_VIEW_CLEAR_COAT_NORMAL, MIFX_PBR_DEBUG_VIEW_SHEEN, MIFX_PBR_DEBUG_VIEW_SHEEN_COLOR, MIFX_PBR_DEBUG_VIEW_SHEEN_ROUGHNESS,
+    MIFX_PBR_DEBUG_VIEW_ANISOTROPY_STRENGTH, MIFX_PBR_DEBUG_VIEW_ANISOTROPY_DIRECTION, MIFX_PBR_DEBUG_VIEW_IRIDESCENCE, MIFX_PBR_DEBUG_VIEW_IRIDESCENCE_FACTOR,
+    MIFX_PBR_DEBUG_VIEW_IRIDESCENCE_THICKNESS, MIFX_PBR_DEBUG_VIEW_TRANSMISSION, MIFX_PBR_DEBUG_VIEW_THICKNESS, MIFX_PBR_DEBUG_VIEW_SCENE_DEPTH,
+    MIFX_PBR_DEBUG_VIEW_COUNT /* NumDebugViews = 35 */
+};
+enum /* PBR_Renderer::LoadingAnimationMode, PBR_Renderer.hpp:441-447 */
+{
+    MIFX_PBR_LOADING_ANIMATION_NONE = 0, MIFX_PBR_LOADING_ANIMATION_ALWAYS = 1, MIFX_PBR_LOADING_ANIMATION_TRANSITIONING = 2
+};
+enum /* PBR_ALPHA_MODE_*, Shaders/PBR/public/PBR_Structures.fxh:34-44 */
+{
+    MIFX_PBR_ALPHA_MODE_OPAQUE = 0, MIFX_PBR_ALPHA_MODE_MASK = 1, MIFX_PBR_ALPHA_MODE_BLEND = 2
+};
+#define MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB 1u /* CONVERT_OUTPUT_TO_SRGB: FastLinearToSRGB of the colour, RenderPBR.psh:639-643 */
+typedef struct mifx_pbr_shade_output_desc
+{
+    const mifx_pbr_renderer_shader_parameters* renderer; /* g_Frame.Renderer: AverageLogLum, MiddleGray, WhitePoint (RenderPBR.psh:536-540), Time, LoadingAnimation (:364-368,620),
+                                                          * HighlightColor (:562) are read; DebugView is ignored -- the view is the pipeline key (PBR_Renderer.cpp:1439)          */
+    int32_t  debug_view;        /* DEBUG_VIEW: MIFX_PBR_DEBUG_VIEW_* (RenderPBR.psh:467-471,574-613, PBR_Shading.fxh:879-989); values outside [0, 35) are refused                 */
+    int32_t  tone_mapping_mode; /* 0 = ENABLE_TONE_MAPPING off; else TONE_MAPPING_MODE (MIFX_TONE_MAPPING_MODE_*), applied as :530-542: fLuminanceSaturation 1, no auto exposure.
+                                 * AGX_CUSTOM is refused: the shader leaves the AgX look parameters of its ToneMappingAttribs unset                                              */
+    int32_t  loading_animation; /* LOADING_ANIMATION: MIFX_PBR_LOADING_ANIMATION_* (:615-630; GetLoadingAnimationColor :361-386); ALWAYS uses factor 1                            */
+    int32_t  alpha_mode;        /* PBR_ALPHA_MODE / BasicAttribs.AlphaMode: MASK discards BaseColor.a < cutoff (:460-465), BLEND premultiplies (:545-547) and keeps alpha (:633) */
+    float    alpha_mask_cutoff; /* BasicAttribs.AlphaMaskCutoff (:461)                                                                                                            */
+    int32_t  unlit;             /* != 0: BasicAttribs.Workflow == PBR_WORKFLOW_UNLIT, OutColor = BaseColor (:525-528) and a zero out_specular_ibl (alpha 1): no lighting ran;
+                                 * only with the views NONE, BASE_COLOR, TRANSPARENCY and WHITE_BASE_COLOR (the others show lighting terms an unlit material does not have)     */
+    uint32_t flags;             /* MIFX_PBR_SHADE_OUTPUT_FLAG_*                                                                                                                   */
+    uint32_t padding;
+    const mifx_image2d* motion;      /* F32X2 or NULL: the MotionVec target, MotionVector of :564-571, shown by DEBUG_VIEW_MOTION_VECTORS (:594-597); NULL = the permutation
+                                      * without COMPUTE_MOTION_VECTORS, a zero vector                                                                                             */
+    const mifx_image2d* mesh_normal; /* F32X4 or NULL: VSOut.Normal (:426-431), shown by DEBUG_VIEW_MESH_NORMAL (:590-593); NULL = the permutation without USE_VERTEX_NORMALS,
+                                      * a zero vector: the view is (0.5, 0.5, 0.5)                                                                                                */
+} mifx_pbr_shade_output_desc;
+/* `layers` may be NULL (no layer), `shadows` may be NULL, `out_specular_ibl` may be NULL.  DEBUG_VIEW_SCENE_DEPTH reads camera->fSceneNearZ / fSceneFarZ (:602-608). */
+MIFX_API mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
+                                           const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
+                                           const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_specular_ibl);
+
 /* IBL precompute == PBR_Renderer::PrecomputeBRDF (PBR_Renderer.cpp:548-622) and PBR_Renderer::PrecomputeCubemaps (:729-972).
  * The environment map is a float4 cube with a full (box-filtered) mip chain, as the reference expects of its input SRV. */
 /* The shade samples the IBL cube maps through a working copy with a one-texel apron per face, made at every call because the maps are the caller's memory (they may
