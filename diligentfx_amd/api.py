@@ -430,6 +430,56 @@ def pbr_shade_output(ctx: "PostFXContext", gbuffer: dict, layers, flags: int, ca
     return out_color, out_specular_ibl
 
 
+PBR_TARGET_PLANES = ("normal", "base_color", "material", "ibl")
+
+
+def pbr_shade_targets(ctx: "PostFXContext", gbuffer: dict, layers, flags: int, camera: B.CameraAttribs, attribs: B.PBRShadeAttribs, ibl: IBLResources, output: dict = None,
+                      shadows=None, motion=None, mesh_normal=None, background=(0.0, 0.0, 0.0, 0.0), iridescence_ior=1.3, anisotropy_rotation=0.0, out_color=None, out_targets=None):
+    """The shade with its output stage and the USD footer's G-buffer targets (mifx_pbr_shade_targets).  Arguments as pbr_shade_output(); output=None is the entry's NULL desc
+    (view NONE, nothing on).  out_targets: dict of the four planes of PBR_TARGET_PLANES, or None.  Returns (color, normal, base_color, material, ibl)."""
+    ref = gbuffer["depth"]
+    h, w = ref.shape
+    if out_color is None:
+        out_color = torch.empty(h, w, 4, device=ref.device, dtype=B.storage_dtype())
+    if out_targets is None:
+        out_targets = {k: torch.empty(h, w, 4, device=ref.device, dtype=B.storage_dtype()) for k in PBR_TARGET_PLANES}
+    imgs = {k: B.image(gbuffer[k]) for k in ("base_color", "normal", "material", "depth", "emissive", "occlusion") if gbuffer.get(k) is not None}
+    p = lambda k: ctypes.pointer(imgs[k]) if k in imgs else None  # noqa: E731
+    g = B.GBuffer(p("base_color"), p("normal"), p("material"), p("depth"), p("emissive"), p("occlusion"))
+    ly = None
+    if layers is not None and flags:
+        limgs = {k: B.image(layers[k]) for k in B.PBR_LAYER_PLANES if layers.get(k) is not None}
+        ly = B.PBRLayers(flags, iridescence_ior, anisotropy_rotation, 0, *[ctypes.pointer(limgs[k]) if k in limgs else None for k in B.PBR_LAYER_PLANES])
+    desc = None
+    if output is not None:
+        output = dict(output)
+        renderer = output.pop("renderer", None)
+        mi = B.image(motion) if motion is not None else None
+        ni = B.image(mesh_normal) if mesh_normal is not None else None
+        desc = B.PBRShadeOutputDesc(ctypes.pointer(renderer) if renderer is not None else None, output.pop("debug_view", 0), output.pop("tone_mapping_mode", 0),
+                                    output.pop("loading_animation", 0), output.pop("alpha_mode", 0), output.pop("alpha_mask_cutoff", 0.5), int(output.pop("unlit", 0)),
+                                    output.pop("flags", 0), 0, ctypes.pointer(mi) if mi is not None else None, ctypes.pointer(ni) if ni is not None else None)
+        assert not output, f"unknown fields of mifx_pbr_shade_output_desc: {sorted(output)}"
+    o0 = B.image(out_color)
+    timgs = [B.image(out_targets[k]) for k in PBR_TARGET_PLANES]
+    tg = B.PBRTargets(*[ctypes.pointer(i) for i in timgs])
+    bg = (ctypes.c_float * 4)(*background)
+    ctx.sync_stream()
+    sh = None
+    if shadows is not None:
+        sm, infos, pcf = shadows
+        assert sm.dtype == torch.float32 and sm.dim() == 3 and sm.is_contiguous()
+        arr = B.ShadowMapArray(sm.data_ptr(), sm.shape[2], sm.shape[1], sm.shape[0], sm.stride(1) * 4, sm.stride(0) * 4)
+        rows = (B.PBRShadowMapInfo * len(infos))()
+        for i, r in enumerate(infos):
+            rows[i] = r if isinstance(r, B.PBRShadowMapInfo) else B.PBRShadowMapInfo.from_buffer_copy(r.astype("float32").tobytes())
+        sh = B.PBRShadows(ctypes.pointer(arr), ctypes.cast(rows, ctypes.POINTER(B.PBRShadowMapInfo)), len(infos), pcf)
+    B.check(ctx.lib.mifx_pbr_shade_targets(ctx.handle, ctypes.byref(g), ctypes.byref(ly) if ly is not None else None, ctypes.byref(camera), ctypes.byref(attribs),
+                                           ctypes.byref(ibl.struct), ctypes.byref(sh) if sh is not None else None, ctypes.byref(desc) if desc is not None else None, bg,
+                                           ctypes.byref(o0), ctypes.byref(tg)))
+    return (out_color,) + tuple(out_targets[k] for k in PBR_TARGET_PLANES)
+
+
 HYDROGENT_GBUFFER_FORMATS = {"base_color": "RGBA8_UNORM", "normal": "RGBA16_FLOAT", "material": "RG8_UNORM", "depth": "R32_FLOAT", "emissive": "RGBA16_FLOAT",
                              "occlusion": "R8_UNORM"}  # HnBeginFrameTask.cpp:63-69 (emissive / occlusion are not Hydrogent targets: same classes of format)
 
@@ -1125,7 +1175,11 @@ class Chain:
                 raise RuntimeError("Chain.effect_output('ssr'): no frame has been executed through this object yet (the deferred cleanup needs its depth / normal planes)")
             # the chain's composite evaluated the bilateral cleanup itself (MIFX_CHAIN_FUSE_SSR_CLEANUP_INTO_COMPOSITE): produce the plane from the frame just executed
             imgs = self._last_bound[2]
-            B.check(self.lib.mifx_ssr_run_deferred_cleanup(h, ctypes.byref(imgs["depth"]), ctypes.byref(imgs["normal"])))
+            normal = imgs["normal"]
+            if getattr(self, "_shade_targets", False):  # (the passes behind the shade read the chain's normal target, the cleanup included)
+                normal = B.Image2D()
+                B.check(self.lib.mifx_chain_get_shade_target(self.handle, b"normal", ctypes.byref(normal)))
+            B.check(self.lib.mifx_ssr_run_deferred_cleanup(h, ctypes.byref(imgs["depth"]), ctypes.byref(normal)))
         B.check(getattr(self.lib, f"mifx_{name}_get_output")(h, *extra, ctypes.byref(d)))
         return _view(d, self.device)
 
@@ -1190,6 +1244,29 @@ class Chain:
                 rows[i] = r if isinstance(r, B.PBRShadowMapInfo) else B.PBRShadowMapInfo.from_buffer_copy(r.astype("float32").tobytes())
             sh = B.PBRShadows(ctypes.pointer(arr), ctypes.cast(rows, ctypes.POINTER(B.PBRShadowMapInfo)), len(infos), pcf)
         B.check(self.lib.mifx_chain_set_material_layers(self.handle, ctypes.byref(ly) if ly is not None else None, ctypes.byref(sh) if sh is not None else None))
+
+    def set_shade_output(self, desc: "dict | None" = None, targets=True, motion=None, mesh_normal=None):
+        """The chain's shade with its output stage and, `targets`, the USD footer's G-buffer targets, which every later pass then reads (mifx_chain_set_shade_output).
+        desc: the fields of mifx_pbr_shade_output_desc as pbr_shade_output() takes them, or None; set_shade_output(None, False) turns it off."""
+        d = None
+        self._output_keep = (motion, mesh_normal)
+        if desc is not None:
+            desc = dict(desc)
+            renderer = desc.pop("renderer", None)
+            mi = B.image(motion) if motion is not None else None
+            ni = B.image(mesh_normal) if mesh_normal is not None else None
+            d = B.PBRShadeOutputDesc(ctypes.pointer(renderer) if renderer is not None else None, desc.pop("debug_view", 0), desc.pop("tone_mapping_mode", 0),
+                                     desc.pop("loading_animation", 0), desc.pop("alpha_mode", 0), desc.pop("alpha_mask_cutoff", 0.5), int(desc.pop("unlit", 0)), desc.pop("flags", 0), 0,
+                                     ctypes.pointer(mi) if mi is not None else None, ctypes.pointer(ni) if ni is not None else None)
+            assert not desc, f"unknown fields of mifx_pbr_shade_output_desc: {sorted(desc)}"
+        B.check(self.lib.mifx_chain_set_shade_output(self.handle, ctypes.byref(d) if d is not None else None, ctypes.c_int32(1 if targets else 0)))
+        self._shade_targets = bool(targets)
+
+    def shade_target(self, name):
+        """One of the chain's target planes ("normal", "base_color", "material", "ibl") as the last frame wrote it (mifx_chain_get_shade_target): a view."""
+        d = B.Image2D()
+        B.check(self.lib.mifx_chain_get_shade_target(self.handle, name.encode(), ctypes.byref(d)))
+        return _view(d, self.device)
 
     def set_selection(self, attribs: "B.SelectionAttribs | None", selection_depth=None):
         """Selection highlighting (mifx_chain_set_selection): the jump flood of `selection_depth` and the composite's selection tail on every frame from now on; None

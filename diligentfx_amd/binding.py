@@ -224,6 +224,10 @@ class PBRShadeOutputDesc(ctypes.Structure):  # mifx_pbr_shade_output_desc
                 ("alpha_mask_cutoff", c_f), ("unlit", c_i), ("flags", c_u), ("padding", c_u), ("motion", PImage), ("mesh_normal", PImage)]
 
 
+class PBRTargets(ctypes.Structure):  # mifx_pbr_targets: PSOut.Normal / BaseColor / Material / IBL of the USD footer (USD_Renderer.cpp:148-165)
+    _fields_ = [("normal", PImage), ("base_color", PImage), ("material", PImage), ("ibl", PImage)]
+
+
 class NativeImage(ctypes.Structure):  # mifx_native_image
     _fields_ = [("data", c_p), ("width", c_u), ("height", c_u), ("pitch_bytes", c_u), ("format", c_u)]
 
@@ -491,7 +495,7 @@ class CommStats(ctypes.Structure):  # mifx_comm_stats
                 ("timed_groups", ctypes.c_uint32), ("exchange_ms_total", ctypes.c_float), ("exchange_ms_max", ctypes.c_float)]
 
 
-SIZEOF_NAMES.update({"pbr_shade_output_desc": PBRShadeOutputDesc, "shard_info": ShardInfo, "comm_stats": CommStats, "oit_slice": OITSlice, "oit_targets": OITTargets})
+SIZEOF_NAMES.update({"pbr_shade_output_desc": PBRShadeOutputDesc, "pbr_targets": PBRTargets, "shard_info": ShardInfo, "comm_stats": CommStats, "oit_slice": OITSlice, "oit_targets": OITTargets})
 
 
 class MifxError(RuntimeError):

@@ -18,7 +18,7 @@ mifx_chain::~mifx_chain()
         if (e) (void)hipEventDestroy(e);
     if (halo_stream) (void)hipStreamSynchronize(halo_stream);
     if (ctx) ctx->pending_joins.clear();
-    for (hipEvent_t e : {evFork, evPrep, evSsao, evPrepConsumed, evBloomDone, evJoinS, evJoinX, evAfterP1, evAfterP2, evHaloSsao, evHaloRest, evXEnd[0], evXEnd[1], evHiz, evJoinH, evSsrDone})
+    for (hipEvent_t e : {evFork, evPrep, evSsao, evPrepConsumed, evBloomDone, evJoinS, evJoinX, evAfterP1, evAfterP2, evHaloSsao, evHaloRest, evXEnd[0], evXEnd[1], evHiz, evJoinH, evSsrDone, evShade})
         if (e) (void)hipEventDestroy(e);
     for (auto& kv : signals)
         for (hipEvent_t e : kv.second.ev)
@@ -123,6 +123,17 @@ static mifx_status chain_shade(mifx_chain* chain, const mifx_chain_frame* f, con
 {
     mifx_postfx* ctx = chain->ctx;
     mifx_ssr*    ssr = chain->ssr;
+    if (chain->has_shade_output) // mifx_chain_set_shade_output: the shade to the end of the pixel shader's `main` (no R2 by-product either); absent layers = the empty set
+    {
+        chain->shaded_rows  = ctx->needed_rows(int(radiance->height));
+        chain->shaded_frame = f->frame.Index;
+        const mifx_pbr_layers*            layers  = chain->has_layers ? &chain->layers : nullptr;
+        const mifx_pbr_shadows*           shadows = chain->has_shadows ? &chain->shadows : nullptr;
+        const mifx_pbr_shade_output_desc* desc    = chain->has_output_desc ? &chain->output_desc : nullptr;
+        if (!chain->write_targets) return mifx::g_shade_output_entries.output(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, spec);
+        const mifx_pbr_targets tg{&chain->target_desc[0], &chain->target_desc[1], &chain->target_desc[2], &chain->target_desc[3]}; // (`spec` is target_desc[3]: chain_frame_planes)
+        return mifx::g_shade_output_entries.targets(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, &tg);
+    }
     if (chain->has_layers || chain->has_shadows) // mifx_chain_set_material_layers: the layered kernel (no R2 by-product: SSR runs the pass itself)
     {
         const mifx_pbr_layers none{};
@@ -178,6 +189,30 @@ static mifx_status chain_selection_composite(mifx_chain* chain, const mifx_chain
     return selection_chain_composite(chain->selection, a, &chain->selection_depth, ca, f->gbuffer.depth, comp, r7);
 }
 
+// The Normal / BaseColor / Material planes the passes behind the shade read: the caller's G-buffer, or -- mifx_chain_set_shade_output with targets -- the planes the shade's
+// footer wrote this frame (USD_Renderer.cpp:148-160: in Hydrogent these ARE the G-buffer the post-process reads).  Depth and motion are always the caller's.
+struct ChainGBuffer
+{
+    const mifx_image2d *normal, *base_color, *material;
+};
+static ChainGBuffer chain_gbuffer(const mifx_chain* chain, const mifx_chain_frame* f)
+{
+    if (chain->has_shade_output && chain->write_targets) return {&chain->target_desc[0], &chain->target_desc[1], &chain->target_desc[2]};
+    return {f->gbuffer.normal, f->gbuffer.base_color, f->gbuffer.material};
+}
+// The chain's colour planes of this frame: radiance, the composite's specular IBL (the IBL target with targets on), the composite
+struct ChainPlanes
+{
+    mifx_image2d radiance, spec, comp;
+};
+static ChainPlanes chain_frame_planes(mifx_chain* chain)
+{
+    const bool targets = chain->has_shade_output && chain->write_targets;
+    if (targets)
+        for (int i = 0; i < 4; ++i) chain->target_desc[i] = chain->targets[i].desc();
+    return {chain->radiance.desc(), targets ? chain->target_desc[3] : chain->specular_ibl.desc(), chain->composite.desc()};
+}
+
 // The composite draw (HnPostProcess.psh:145-185).  With fuse_ssr_cleanup the kernel evaluates SSR's last pass (R7, the bilateral cleanup) for its own pixel from the
 // effect's accumulated radiance instead of reading the plane R7 would have written (mifx_ssr::run stopped after R6: mifx_ssr::Request::defer_cleanup).
 // With fuse_composite_taa on top of that (round 5) nothing is launched here: the TAA kernel of this frame evaluates the composite for the texels of its colour tile
@@ -196,7 +231,8 @@ static mifx_status chain_composite(mifx_chain* chain, const mifx_chain_frame* f,
     mifx_image2d ssr_out{};
     const bool fused = ssr->cleanup_pending; // (set by an execute that deferred the pass)
     if (!fused) MIFX_CHECK(mifx_ssr_get_output(ssr, &ssr_out));
-    mifx_composite_attribs ca{radiance, spec, fused ? radiance /* not read */ : &ssr_out, ssao_out, f->gbuffer.normal, f->gbuffer.base_color, f->gbuffer.material, f->ibl->brdf_lut,
+    const ChainGBuffer gb = chain_gbuffer(chain, f);
+    mifx_composite_attribs ca{radiance, spec, fused ? radiance /* not read */ : &ssr_out, ssao_out, gb.normal, gb.base_color, gb.material, f->ibl->brdf_lut,
                               f->curr_camera, f->ssr_scale, f->ssao_scale, nullptr, f->ave_log_lum};
     if (chain->has_selection) return chain_selection_composite(chain, f, ca, comp, fused ? &ssr->cleanup_in : nullptr); // (a pass of its own, also with fuse_composite_taa)
     if (!fused) return mifx_composite_execute(ctx, &ca, comp);
@@ -290,6 +326,8 @@ extern "C++" mifx_status mifx::chain_prepare_resources(mifx_chain* chain, const 
     MIFX_CHECK(chain->radiance.alloc(W, H, MIFX_FORMAT_F32X4));
     MIFX_CHECK(chain->specular_ibl.alloc(W, H, MIFX_FORMAT_F32X4));
     MIFX_CHECK(chain->composite.alloc(W, H, MIFX_FORMAT_F32X4));
+    if (chain->has_shade_output && chain->write_targets)
+        for (mifx::Plane& p : chain->targets) MIFX_CHECK(p.alloc(W, H, MIFX_FORMAT_F32X4)); // (once per size; freed with the chain)
     return MIFX_OK;
 }
 
@@ -300,11 +338,13 @@ struct FrameAttribs
     mifx_ssr_render_attribs    sr;
     mifx_ssao_render_attribs   sa;
 };
-static FrameAttribs chain_frame_attribs(mifx_postfx* ctx, const mifx_chain_frame* f, const mifx_image2d* radiance)
+static FrameAttribs chain_frame_attribs(const mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* radiance)
 {
+    mifx_postfx* ctx = chain->ctx;
+    const ChainGBuffer gb = chain_gbuffer(chain, f);
     return {{f->gbuffer.depth, f->prev_depth, f->motion, f->curr_camera, f->prev_camera},
-            {ctx, radiance, f->gbuffer.depth, f->gbuffer.normal, f->gbuffer.material, f->motion, f->ssr},
-            {ctx, f->gbuffer.depth, f->gbuffer.normal, f->ssao}};
+            {ctx, radiance, f->gbuffer.depth, gb.normal, gb.material, f->motion, f->ssr},
+            {ctx, f->gbuffer.depth, gb.normal, f->ssao}};
 }
 
 // Creates the chain's extra streams and events on first use.
@@ -314,7 +354,7 @@ extern "C++" mifx_status mifx::chain_make_lanes(mifx_chain* chain, int lanes)
     {
         // (a stream priority for the second stream was measured: lowest 1.713-1.723 ms, highest 1.728-1.736 ms, default 1.701-1.703 ms per 4K frame in mode 2)
         MIFX_HIP_CHECK(hipStreamCreateWithFlags(&chain->side, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&chain->evFork, &chain->evPrep, &chain->evSsao, &chain->evPrepConsumed, &chain->evJoinS}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (hipEvent_t* e : {&chain->evFork, &chain->evPrep, &chain->evSsao, &chain->evPrepConsumed, &chain->evJoinS, &chain->evShade}) MIFX_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     if (lanes >= 3 && !chain->lane_x)
     {
@@ -372,6 +412,8 @@ static void chain_swap_shadow(mifx_chain* chain)
     mifx_chain::Shadow& sh = chain->shadow;
     chain->radiance.swap(sh.radiance);
     chain->specular_ibl.swap(sh.specular_ibl);
+    if (chain->has_shade_output && chain->write_targets)
+        for (int i = 0; i < 4; ++i) chain->targets[i].swap(sh.targets[i]);
     ctx->reproj_depth.swap(sh.reproj_depth);
     ctx->closest_motion.swap(sh.closest_motion);
     ctx->noise_xy.swap(sh.noise_xy);
@@ -390,6 +432,8 @@ static mifx_status chain_prepare_shadow(mifx_chain* chain)
     mifx_chain::Shadow& sh = chain->shadow;
     MIFX_CHECK(sh.radiance.alloc_like(chain->radiance));
     MIFX_CHECK(sh.specular_ibl.alloc_like(chain->specular_ibl));
+    if (chain->has_shade_output && chain->write_targets)
+        for (int i = 0; i < 4; ++i) MIFX_CHECK(sh.targets[i].alloc_like(chain->targets[i]));
     MIFX_CHECK(sh.reproj_depth.alloc_like(ctx->reproj_depth));
     MIFX_CHECK(sh.closest_motion.alloc_like(ctx->closest_motion));
     MIFX_CHECK(sh.noise_xy.alloc_like(ctx->noise_xy));
@@ -446,14 +490,14 @@ static mifx_status chain_execute_lanes(mifx_chain* chain, const mifx_chain_frame
         MIFX_CHECK(chain_prepare_shadow(chain));
         chain_swap_shadow(chain); // this frame's set = the one the frame before the previous frame used
     }
-    const mifx_image2d radiance = chain->radiance.desc(), spec = chain->specular_ibl.desc(), comp = chain->composite.desc();
+    const auto [radiance, spec, comp] = chain_frame_planes(chain);
     LaneJoin join{chain, M, {S, chain->evJoinS}, {X, chain->evJoinX}}; // (the regular path joins through evSsao -> evPrepConsumed)
     const uint64_t k = chain->seq;
     // lane S continues behind the last reader of what it overwrites: the end of lane X of the previous frame -- or, two frames in flight, of the frame before that one
     const bool deep = pipelined && k >= 2 && f->frame.Index == chain->last_index + 1u;
     MIFX_CHECK(chain_fork_lanes(chain, {{S, deep ? chain->evXEnd[k & 1u] : chain->evPrepConsumed}, {X, nullptr}})); // (evXEnd[k & 1] still holds frame k - 2's record)
     if (pipelined && !chain->edges.empty()) ctx->kernel_hook = [chain](const char* name, bool begin) { chain_kernel_hook(chain, name, begin); };
-    const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
+    const auto [pa, sr, sa] = chain_frame_attribs(chain, f, &radiance);
     // lane S: shade, prep
     ctx->stream = S;
     MIFX_CHECK(chain_shade(chain, f, &radiance, &spec));
@@ -510,7 +554,7 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
     mifx_postfx* ctx = chain->ctx;
     MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
     if (chain->overlap >= 3 && !chain->profiling) return chain_execute_lanes(chain, f, out_ldr, out_native, chain->overlap);
-    const mifx_image2d radiance = chain->radiance.desc(), spec = chain->specular_ibl.desc(), comp = chain->composite.desc();
+    const auto [radiance, spec, comp] = chain_frame_planes(chain);
     int stage = 0;
     auto mark = [&]() -> mifx_status {
         if (chain->profiling) MIFX_HIP_CHECK(hipEventRecord(chain->ev[stage], ctx->stream));
@@ -519,7 +563,7 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
     };
     MIFX_CHECK(mark());
 
-    const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
+    const auto [pa, sr, sa] = chain_frame_attribs(chain, f, &radiance);
     const bool        two  = chain->overlap && !chain->profiling;
     const hipStream_t main = ctx->stream;
     if (two) MIFX_CHECK(chain_make_lanes(chain, 2));
@@ -538,13 +582,21 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
         //  (tools/exp_two_chains.py).  tools/overlap_stats.py shows what runs beside what: profiles/r03_overlap_stats.txt.)
         // (only while nothing else was queued on the context stream in between -- a reset's or a re-allocating prepare's history fills, an import: chain_lanes_continue)
         MIFX_CHECK(chain_fork_lanes(chain, {{chain->side, chain->evPrepConsumed}}, chain->overlap >= 2));
+        // (with the shade's targets on, SSAO reads the normal target: the shade is then queued first and SSAO waits for it; prep still runs beside it)
+        const bool ssao_reads_shade = chain->has_shade_output && chain->write_targets;
+        if (ssao_reads_shade)
+        {
+            MIFX_CHECK(chain_shade(chain, f, &radiance, &spec));
+            MIFX_HIP_CHECK(hipEventRecord(chain->evShade, main));
+        }
         ctx->stream = chain->side;
         MIFX_CHECK(mifx_postfx_execute(ctx, &pa));
         MIFX_HIP_CHECK(hipEventRecord(chain->evPrep, chain->side));
+        if (ssao_reads_shade) MIFX_HIP_CHECK(hipStreamWaitEvent(chain->side, chain->evShade, 0));
         MIFX_CHECK(mifx_ssao_execute(chain->ssao, &sa));
         MIFX_HIP_CHECK(hipEventRecord(chain->evSsao, chain->side));
         ctx->stream = main;
-        MIFX_CHECK(chain_shade(chain, f, &radiance, &spec)); // (measured: the shade on the side stream as well, in front of prep, changes nothing: 1.747 vs 1.751 ms)
+        if (!ssao_reads_shade) MIFX_CHECK(chain_shade(chain, f, &radiance, &spec)); // (measured: the shade on the side stream as well, in front of prep, changes nothing: 1.747 vs 1.751 ms)
         MIFX_HIP_CHECK(hipStreamWaitEvent(main, chain->evPrep, 0));
         MIFX_CHECK(chain->ssr->run(&sr, mifx_ssr::Request{chain->fuse_ssr_cleanup}));
         MIFX_HIP_CHECK(hipStreamWaitEvent(main, chain->evSsao, 0));
@@ -651,6 +703,8 @@ ShardRows shard_rows(const mifx_chain* chain, const mifx_chain_frame* f, Rows ba
 extern "C" mifx_status mifx_chain_set_row_band(mifx_chain* chain, int32_t row_begin, int32_t row_end, int32_t max_motion_rows)
 {
     MIFX_REQUIRE(chain != nullptr && row_begin >= 0 && row_end >= row_begin && max_motion_rows >= 0, "mifx_chain_set_row_band: bad argument");
+    MIFX_REQUIRE(row_end == row_begin || !chain->has_shade_output,
+                 "mifx_chain_set_row_band: a row band (or sharding) is not combined with mifx_chain_set_shade_output: the sharded hit fetch has no output stage or footer");
     chain->band       = Rows{row_begin, row_end}; // {0, 0} switches sharding off
     chain->max_motion = max_motion_rows;
     chain->ctx->band  = chain->band;
@@ -675,6 +729,7 @@ extern "C++" mifx_status mifx::chain_execute_phase(mifx_chain* chain, const mifx
 {
     MIFX_REQUIRE(chain != nullptr && f != nullptr && out_ldr != nullptr && phase >= 0 && phase <= 4, "mifx_chain_execute_phase: bad argument");
     MIFX_REQUIRE(!chain->band.empty(), "mifx_chain_execute_phase: no row band set (mifx_chain_set_row_band)");
+    MIFX_REQUIRE(!chain->has_shade_output, "mifx_chain_execute_phase: a row band is not combined with mifx_chain_set_shade_output (the sharded hit fetch has no output stage or footer)");
     MIFX_CHECK(chain_check_frame(f, "mifx_chain_execute_phase"));
     mifx_postfx* ctx = chain->ctx;
     if (phase == 0) MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
@@ -692,7 +747,7 @@ extern "C++" mifx_status mifx::chain_execute_phase(mifx_chain* chain, const mifx
     }
     mifx_image2d ssao_out, taa_out, bloom_out;
     mifx_bloom_render_attribs ba{ctx, nullptr, f->bloom};
-    const auto [pa, sr, sa] = chain_frame_attribs(ctx, f, &radiance);
+    const auto [pa, sr, sa] = chain_frame_attribs(chain, f, &radiance);
     // A history-halo exchange of the previous sharded frame that is still travelling (mifx_chain_execute_sharded, async_halos) is joined where this frame first reads the
     // plane -- also for a caller that mixes mifx_chain_execute_sharded frames with phases of its own.
     if (phase == 1 && chain->halo_ssao_pending)
@@ -928,6 +983,70 @@ mifx_status mifx_chain_set_material_layers(mifx_chain* chain, const mifx_pbr_lay
         chain->has_shadows = true;
     }
     return MIFX_OK;
+}
+
+mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_output_desc* output, int32_t write_targets)
+{
+    // (no device call: every refusal is an argument check)
+    MIFX_REQUIRE(chain != nullptr, "mifx_chain_set_shade_output: null chain");
+    if (output != nullptr)
+    {
+        MIFX_CHECK(mifx::check_shade_output_desc("mifx_chain_set_shade_output", output));
+        MIFX_REQUIRE(output->tone_mapping_mode == 0,
+                     "mifx_chain_set_shade_output: tone_mapping_mode %d: the chain tone-maps at its own end (HnPostProcessTask runs the renderer without ENABLE_TONE_MAPPING)",
+                     output->tone_mapping_mode);
+        MIFX_REQUIRE((output->flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) == 0u,
+                     "mifx_chain_set_shade_output: CONVERT_OUTPUT_TO_SRGB: the chain converts at its own end (the copy-frame pass)");
+    }
+    const bool on = output != nullptr || write_targets != 0;
+    MIFX_REQUIRE(!on || chain->band.empty(),
+                 "mifx_chain_set_shade_output: not combined with a row band or sharding (mifx_chain_set_row_band / _set_sharding): the sharded hit fetch has no output stage or footer");
+#ifdef MIFX_STORAGE_H4
+    if (on)
+    {
+        ::mifx::set_error("mifx_chain_set_shade_output: the shade's output stage and its footer are not part of the native-storage build yet");
+        return MIFX_ERR_NOT_IMPLEMENTED;
+    }
+#endif
+    if (on && mifx::g_shade_output_entries.targets == nullptr)
+    {
+        ::mifx::set_error("mifx_chain_set_shade_output: this build has no shade kernels (host objects alone)");
+        return MIFX_ERR_NOT_IMPLEMENTED;
+    }
+    chain->has_shade_output = on;
+    chain->has_output_desc  = output != nullptr;
+    chain->write_targets    = write_targets != 0;
+    if (output != nullptr)
+    {
+        chain->output_desc          = *output;
+        chain->output_renderer      = *output->renderer;
+        chain->output_desc.renderer = &chain->output_renderer;
+        const mifx_image2d** slot[2] = {&chain->output_desc.motion, &chain->output_desc.mesh_normal};
+        for (int i = 0; i < 2; ++i)
+            if (*slot[i] != nullptr)
+            {
+                chain->output_images[i] = **slot[i];
+                *slot[i] = &chain->output_images[i];
+            }
+    }
+    chain->prep_consumed = false; // (which planes the lanes trade and read changes: the next frame forks from the context stream once)
+    return MIFX_OK;
+}
+
+mifx_status mifx_chain_get_shade_target(mifx_chain* chain, const char* name, mifx_image2d* out)
+{
+    MIFX_REQUIRE(chain != nullptr && name != nullptr && out != nullptr, "mifx_chain_get_shade_target: null argument");
+    static const char* const names[4] = {"normal", "base_color", "material", "ibl"};
+    for (int i = 0; i < 4; ++i)
+        if (std::string(name) == names[i])
+        {
+            MIFX_REQUIRE(chain->has_shade_output && chain->write_targets && chain->targets[i].data != nullptr,
+                         "mifx_chain_get_shade_target: no '%s' target (mifx_chain_set_shade_output with write_targets, and a frame executed)", name);
+            *out = chain->targets[i].desc();
+            return MIFX_OK;
+        }
+    set_error("mifx_chain_get_shade_target: unknown target '%s' (normal, base_color, material, ibl)", name);
+    return MIFX_ERR_INVALID_ARG;
 }
 
 mifx_status mifx_chain_set_effect_feature_flags(mifx_chain* chain, uint32_t ssao_feature_flags, uint32_t ssr_feature_flags)

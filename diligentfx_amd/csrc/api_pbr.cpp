@@ -251,3 +251,24 @@ mifx_status mifx_image_export(mifx_postfx* ctx, const mifx_image2d* src, const m
 }
 
 } // extern "C"
+
+// what both entries and mifx_chain_set_shade_output refuse of a desc (every check precedes the first device call)
+mifx_status mifx::check_shade_output_desc(const char* who, const mifx_pbr_shade_output_desc* output)
+{
+    MIFX_REQUIRE(output->renderer != nullptr, "%s: output->renderer is null (the PBRRendererShaderParameters block of the frame)", who);
+    MIFX_REQUIRE(output->debug_view >= 0 && output->debug_view < MIFX_PBR_DEBUG_VIEW_COUNT, "%s: debug view %d outside [0, %d)", who, output->debug_view, int(MIFX_PBR_DEBUG_VIEW_COUNT));
+    MIFX_REQUIRE(output->tone_mapping_mode >= 0 && output->tone_mapping_mode <= MIFX_TONE_MAPPING_MODE_COMMERCE, "%s: unknown tone mapping mode %d", who, output->tone_mapping_mode);
+    MIFX_REQUIRE(output->tone_mapping_mode != MIFX_TONE_MAPPING_MODE_AGX_CUSTOM,
+                 "%s: TONE_MAPPING_MODE_AGX_CUSTOM: the shader's ToneMappingAttribs carry no AgX look parameters (RenderPBR.psh:533-539)", who);
+    MIFX_REQUIRE(output->loading_animation >= MIFX_PBR_LOADING_ANIMATION_NONE && output->loading_animation <= MIFX_PBR_LOADING_ANIMATION_TRANSITIONING,
+                 "%s: unknown loading animation mode %d", who, output->loading_animation);
+    MIFX_REQUIRE(output->alpha_mode >= MIFX_PBR_ALPHA_MODE_OPAQUE && output->alpha_mode <= MIFX_PBR_ALPHA_MODE_BLEND, "%s: unknown alpha mode %d", who, output->alpha_mode);
+    MIFX_REQUIRE((output->flags & ~MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) == 0u, "%s: unknown flag bits 0x%x", who,
+                 output->flags & ~MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB);
+    const int view = output->debug_view;
+    MIFX_REQUIRE(!output->unlit || view == MIFX_PBR_DEBUG_VIEW_NONE || view == MIFX_PBR_DEBUG_VIEW_BASE_COLOR || view == MIFX_PBR_DEBUG_VIEW_TRANSPARENCY ||
+                     view == MIFX_PBR_DEBUG_VIEW_WHITE_BASE_COLOR,
+                 "%s: debug view %d shows a lighting term, which an unlit material (PBR_WORKFLOW_UNLIT) does not have", who, view);
+    return MIFX_OK;
+}
+mifx::ShadeOutputEntries mifx::g_shade_output_entries{};

@@ -235,6 +235,7 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("pbr_renderer_shader_parameters", mifx_pbr_renderer_shader_parameters);
     MIFX_SZ("pbr_material_basic_attribs", mifx_pbr_material_basic_attribs);
     MIFX_SZ("pbr_shade_output_desc", mifx_pbr_shade_output_desc);
+    MIFX_SZ("pbr_targets", mifx_pbr_targets);
     MIFX_SZ("frame_desc", mifx_frame_desc);
     MIFX_SZ("chain_frame", mifx_chain_frame);
     MIFX_SZ("composite_attribs", mifx_composite_attribs);

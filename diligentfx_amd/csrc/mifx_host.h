@@ -290,6 +290,16 @@ struct SsrMaskOut
 mifx_status launch_pbr_shade(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                              const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth,
                              const mifx_pbr_shadows* shadows = nullptr, const SsrMaskOut* ssrMask = nullptr);
+// what mifx_pbr_shade_output, mifx_pbr_shade_targets and mifx_chain_set_shade_output refuse of a desc, `who` in front of the message (pbr.hip; no device call)
+mifx_status check_shade_output_desc(const char* who, const mifx_pbr_shade_output_desc* output);
+// mifx_pbr_shade_output and mifx_pbr_shade_targets live beside their kernels in pbr.hip, which a build of the host objects alone does not have: the chain calls them through
+// this table, filled by pbr.hip when the library is loaded (null in such a build: mifx_chain_set_shade_output then answers MIFX_ERR_NOT_IMPLEMENTED)
+struct ShadeOutputEntries
+{
+    decltype(&mifx_pbr_shade_output)  output;
+    decltype(&mifx_pbr_shade_targets) targets;
+};
+extern ShadeOutputEntries g_shade_output_entries;
 // the sharded SSR's hit fetch with the layered body: `out_radiance` of launch_pbr_shade_layers is then the plane phase 0 shaded rows [shadedBegin, shadedEnd) of
 struct LayeredHitFetch
 {

@@ -413,6 +413,16 @@ struct mifx_chain
     mifx_pbr_shadows         shadows{};
     mifx_shadow_map_array    shadow_array{};
     mifx_pbr_shadow_map_info shadow_infos[MIFX_PBR_MAX_SHADOW_MAPS]{};
+    // mifx_chain_set_shade_output: the shade is mifx_pbr_shade_output / mifx_pbr_shade_targets (deep copies of the desc and its renderer block; the motion / mesh-normal
+    // planes are borrowed).  With write_targets the chain owns the footer's four planes, and every pass behind the shade reads them in place of gbuffer.normal / .base_color /
+    // .material and of the specular-IBL plane (target_desc: this frame's descriptors, set at the start of every frame -- the planes trade places with `shadow` in modes 4, 5).
+    bool                                has_shade_output = false, has_output_desc = false, write_targets = false;
+    mifx_pbr_shade_output_desc          output_desc{};
+    mifx_pbr_renderer_shader_parameters output_renderer{};
+    mifx_image2d                        output_images[2]{};
+    mifx::Plane                         targets[4]; // normal, base colour, material, IBL
+    mifx_image2d                        target_desc[4]{};
+    hipEvent_t                          evShade = nullptr; // overlap 1, 2 with targets: SSAO on the side stream reads the normal target the shade writes
     // mifx_chain_set_selection: the jump flood + the selection composite in place of the composite (api_selection.cpp); the attribs and the
     // image descriptor are copies, the selection depth plane is borrowed
     bool                   has_selection = false;
@@ -446,6 +456,7 @@ struct mifx_chain
     struct Shadow
     {
         mifx::Plane radiance, specular_ibl;                                    // the chain's
+        mifx::Plane targets[4];                                                // ... and with mifx_chain_set_shade_output's targets on, those
         mifx::Plane reproj_depth, closest_motion, noise_xy, noise_zw, prev_depth16; // mifx_postfx's
         mifx::Plane roughness, mask, hiz[mifx_ssr::kMips];                     // mifx_ssr's (hiz: views into hiz_slab)
         mifx::DeviceScratch hiz_slab;

@@ -216,10 +216,10 @@ struct LayersK
 // TERMS: NoShadeTerms (every existing caller: nothing below exists for it), or ShadeTerms -- the shade's output stage (mifx_pbr_output.h) hands in what must act before the
 // lighting (the mask test, the white base colour) and takes back the intermediate terms its debug views show.
 constexpr unsigned kLayersRuntime = 0xffffffffu;
-struct NoShadeTerms { static constexpr bool kWanted = false; };
+struct NoShadeTerms { static constexpr bool kWanted = false, kFooter = false; };
 struct ShadeTerms
 {
-    static constexpr bool kWanted = true;
+    static constexpr bool kWanted = true, kFooter = false;
     // in
     bool  maskTest;       // PBR_ALPHA_MODE_MASK: BaseColor.a < cutoff is discarded (RenderPBR.psh:460-465) -- here: a background pixel
     float alphaMaskCutoff;
@@ -238,6 +238,12 @@ struct ShadeTerms
     v2    anisotropyDirection;
     v3    iridescenceFresnel;
     float iridescenceFactor, iridescenceThickness, transmission;
+};
+// ... and what the USD footer's targets need on top (mifx_pbr_output.h: shade_targets_footer).  A type of its own: the instances with ShadeTerms keep their code.
+struct ShadeFooterTerms : ShadeTerms
+{
+    static constexpr bool kFooter = true;
+    v3 clearcoatIBL; // GetClearcoatIBL (PBR_Shading.fxh:834-838), zero without the layer
 };
 MIFX_D v4 shade_terms_base_color(v4 texel, const NoShadeTerms*) { return texel; }
 MIFX_D v4 shade_terms_base_color(v4 texel, const ShadeTerms* t) { return t->whiteBaseColor ? v4{1.0f, 1.0f, 1.0f, texel.w} : texel; }
@@ -459,5 +465,6 @@ MIFX_D void pbr_shade_layers_pixel(int x, int y, const Img& baseColor, const Img
         terms->iridescenceFresnel = iridFresnel; terms->iridescenceFactor = iridFactor; terms->iridescenceThickness = irid ? ld<v4>(ly.iridescence, x, y).y : 0.0f;
         terms->transmission = transmission;
     }
+    if constexpr (TERMS::kFooter) terms->clearcoatIBL = clearCoat ? ccIBL * iblScale * occl * ccFactor : mk3(0.0f);
 }
 } // namespace mifx

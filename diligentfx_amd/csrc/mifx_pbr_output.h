@@ -142,4 +142,73 @@ MIFX_D void pbr_shade_output_pixel(int x, int y, const Img& baseColor, const Img
     const v3 meshNormal = o.hasMeshNormal ? xyz(ld<v4>(meshNormalTex, x, y)) : mk3(0.0f);
     outColor = shade_output_tail<TM>(t, lit, ly.flags, o, motion, meshNormal, cam);
 }
+
+// ---- the G-buffer targets of the USD renderer's footer (Hydrogent: the text USD_Renderer::GetUsdPbrPSMainSource builds behind `main`, PBR/src/USD_Renderer.cpp:85-168):
+// what PSOut.Normal / BaseColor / Material / IBL receive, which the later passes of the frame (SSR, SSAO, the composite of HnPostProcess.psh:145-185) read.
+struct ShadeTargets
+{
+    v4 normal, baseColor, material, ibl;
+};
+// The footer for a pixel that has a fragment.  t: the terms of the pixel; baseSpecularIBL: GetBaseLayerSpecularIBL (PBR_Shading.fxh:801-805), what the layered body returns as
+// its specular-IBL output; animationFactor: g_Frame.Renderer.LoadingAnimation.Factor as it stands -- the footer does NOT force 1 for LOADING_ANIMATION_ALWAYS, unlike the colour
+// (RenderPBR.psh:617).  An unlit material ran no lighting: SrfLighting keeps its default and both IBL getters return zero.
+MIFX_D ShadeTargets shade_targets_footer(const ShadeFooterTerms& t, v3 baseSpecularIBL, unsigned set, const OutputK& o, float animationFactor)
+{
+    v3 normal = t.N;                                          // USD_Renderer.cpp:97  Shading.BaseLayer.Normal
+    v2 materialData{t.srf.perceptualRoughness, t.metallic};   // :98
+    v3 ibl  = o.unlit ? mk3(0.0f) : baseSpecularIBL;          // :99
+    v3 base = xyz(t.baseColor);                               // BaseColor after RenderPBR.psh:467-471; the BLEND premultiply of :547 touches OutColor only
+    if ((set & MIFX_PBR_LAYER_CLEAR_COAT) != 0u)              // :101-117
+    {
+        const float f = t.clearcoatFactor;
+        normal       = normalize(lerp3(normal, t.clearcoatNormal, f));                                              // :108
+        materialData = v2{lerpf(materialData.x, t.clearcoatRoughness, f), lerpf(materialData.y, 0.0f, f)};          // :109
+        base         = lerp3(base, mk3(1.0f), f);                                                                   // :110
+        ibl          = lerp3(ibl, o.unlit ? mk3(0.0f) : t.clearcoatIBL, f);                                         // :115 (GetClearcoatIBL, PBR_Shading.fxh:834-838)
+    }
+    if (o.loadingAnimation != MIFX_PBR_LOADING_ANIMATION_NONE)                                                      // :118-120
+        materialData = v2{lerpf(materialData.x, 1.0f, animationFactor), lerpf(materialData.y, 0.0f, animationFactor)};
+    const float transmittance = 1.0f; // (:122-124; NUM_OIT_LAYERS 0 -- the OIT transmittance is mifx_oit_blend's)
+    materialData = v2{materialData.x * transmittance, materialData.y * transmittance};
+    ibl          = ibl * transmittance;
+    base         = base * transmittance;
+    const float a = t.baseColor.w;
+    ShadeTargets r;
+    r.normal    = mk4(normal, 1.0f);                                        // :148 (not blended: the normal of the top layer)
+    r.baseColor = mk4(base * a, a);                                         // :155
+    r.material  = v4{materialData.x * a, materialData.y * a, 0.0f, a};      // :160
+    r.ibl       = mk4(ibl * a, a);                                          // :165
+    return r;
+}
+// One pixel of the shade with its output stage and the footer: the body of pbr_shade_targets_kernel (pbr.hip) and of tests/host_kernels/shade_targets_host.cpp.  A pixel without
+// a fragment (background, or discarded by PBR_ALPHA_MODE_MASK) keeps what the caller's G-buffer holds -- there is no rasteriser: "not covered" is "what the plane had" -- and
+// gets a zero IBL target, as out_specular_ibl does.
+template <bool APRON, bool SHADOWS, int TM>
+MIFX_D void pbr_shade_targets_pixel(int x, int y, const Img& baseColor, const Img& normalTex, const Img& material, const Img& depthTex, const Img& emissive, const Img& occlusion,
+                                    const LutK& lut, const v4* irradiance0, int irradianceSize, const v4* const* prefMips, int prefSize, int prefLevels, const CamK& cam,
+                                    const ShadeK& k, const LayersK& ly, int hasEmissive, int hasAo, const ShadowK& sh, const OutputK& o, float animationFactor, const Img& motionTex,
+                                    const Img& meshNormalTex, v4& outColor, ShadeTargets& targets)
+{
+    // (pbr_shade_output_pixel with the footer's terms: the same statements, so that PSOut.Color is that entry's, bit for bit)
+    ShadeFooterTerms t;
+    t.maskTest        = o.alphaMode == MIFX_PBR_ALPHA_MODE_MASK;
+    t.alphaMaskCutoff = o.alphaMaskCutoff;
+    t.whiteBaseColor  = o.debugView == MIFX_PBR_DEBUG_VIEW_WHITE_BASE_COLOR;
+    v4 lit, spec;
+    pbr_shade_layers_pixel<APRON, kLayersRuntime, SHADOWS, ShadeFooterTerms>(x, y, baseColor, normalTex, material, depthTex, emissive, occlusion, lut, irradiance0, irradianceSize,
+                                                                             prefMips, prefSize, prefLevels, cam, k, ly, hasEmissive, hasAo, sh, lit, spec, &t);
+    if (t.background)
+    {
+        outColor          = lit;
+        targets.normal    = ld<v4>(normalTex, x, y);
+        targets.baseColor = ld<v4>(baseColor, x, y);
+        targets.material  = ld<v4>(material, x, y);
+        targets.ibl       = mk4(0.0f);
+        return;
+    }
+    const v2 motion     = o.hasMotion ? ld<v2>(motionTex, x, y) : v2{0.0f, 0.0f};
+    const v3 meshNormal = o.hasMeshNormal ? xyz(ld<v4>(meshNormalTex, x, y)) : mk3(0.0f);
+    outColor = shade_output_tail<TM>(t, lit, ly.flags, o, motion, meshNormal, cam);
+    targets  = shade_targets_footer(t, xyz(spec), ly.flags, o, animationFactor);
+}
 } // namespace mifx

@@ -333,6 +333,33 @@ __global__ __launch_bounds__(256) void pbr_shade_output_kernel(Img baseColor, Im
     st<v4>(outColor, x, y, color);
     if (writeSpec) st<v4>(outSpecIBL, x, y, spec);
 }
+// the same shade with the footer of the USD renderer behind it (mifx_pbr_output.h: shade_targets_footer): PSOut.Color and the Normal / BaseColor / Material / IBL targets,
+// five 16-byte stores per pixel.  A kernel of its own -- pbr_shade_output_kernel keeps its arguments and its instructions.  The colour is stored before the footer runs, so
+// its registers are free for the four targets; plain stores: the passes behind the shade read these planes next.
+struct TargetsK
+{
+    Img   normal, baseColor, material, ibl;
+    float animationFactor; // g_Frame.Renderer.LoadingAnimation.Factor, unforced (USD_Renderer.cpp:119)
+};
+template <int TM, bool SHADOWS>
+__global__ __launch_bounds__(256) void pbr_shade_targets_kernel(Img baseColor, Img normalTex, Img material, Img depthTex, Img emissive, Img occlusion, LutK lut, CubeK irradiance,
+                                                                CubeK prefiltered, Img outColor, CamK cam, ShadeK k, LayersK ly, int hasEmissive, int hasAo, ShadowK sh, OutputK o,
+                                                                Img motion, Img meshNormal, TargetsK tg)
+{
+    __shared__ const v4* prefMips[12];
+    stage_cube_mips(prefMips, prefiltered);
+    int x, y;
+    if (!pixel_xy(outColor, x, y)) return;
+    v4 color;
+    ShadeTargets t;
+    pbr_shade_targets_pixel<true, SHADOWS, TM>(x, y, baseColor, normalTex, material, depthTex, emissive, occlusion, lut, irradiance.mip[0], irradiance.size, prefMips, prefiltered.size,
+                                               prefiltered.mips, cam, k, ly, hasEmissive, hasAo, sh, o, tg.animationFactor, motion, meshNormal, color, t);
+    st<v4>(outColor, x, y, color);
+    st<v4>(tg.normal, x, y, t.normal);
+    st<v4>(tg.baseColor, x, y, t.baseColor);
+    st<v4>(tg.material, x, y, t.material);
+    st<v4>(tg.ibl, x, y, t.ibl);
+}
 #endif
 
 static mifx_status make_cubek(const mifx_cubemap* c, const char* what, CubeK& k)
@@ -493,6 +520,7 @@ static mifx_status make_lutk_r(const mifx_image2d* im, const char* what, LutK& k
 struct ShadeOutputStage
 {
     const mifx_pbr_shade_output_desc* desc; // validated by the entry
+    const mifx_pbr_targets* targets = nullptr; // mifx_pbr_shade_targets: the footer's four planes as well (validated by the entry; `out_spec` is then null)
 };
 static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
                                                 const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance,
@@ -581,7 +609,24 @@ static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& ib
 #define MIFX_OUTPUT_INSTANCE(TM)                                                                                                                                                     \
     hipLaunchKernelGGL((shadows ? pbr_shade_output_kernel<TM, true> : pbr_shade_output_kernel<TM, false>), grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, \
                        outR, outS, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, out_spec ? 1 : 0, sh, o, motion, meshNormal)
-        MIFX_TONEMAP_DISPATCH(d.tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
+#define MIFX_TARGETS_INSTANCE(TM)                                                                                                                                                      \
+    hipLaunchKernelGGL((shadows ? pbr_shade_targets_kernel<TM, true> : pbr_shade_targets_kernel<TM, false>), grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, \
+                       outR, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, sh, o, motion, meshNormal, tg)
+        if (stage->targets != nullptr)
+        {
+            TargetsK tg{};
+            MIFX_CHECK(to_img_wh(stage->targets->normal, MIFX_FORMAT_F32X4, W, H, "targets.normal", tg.normal));
+            MIFX_CHECK(to_img_wh(stage->targets->base_color, MIFX_FORMAT_F32X4, W, H, "targets.base_color", tg.baseColor));
+            MIFX_CHECK(to_img_wh(stage->targets->material, MIFX_FORMAT_F32X4, W, H, "targets.material", tg.material));
+            MIFX_CHECK(to_img_wh(stage->targets->ibl, MIFX_FORMAT_F32X4, W, H, "targets.ibl", tg.ibl));
+            tg.animationFactor = r.LoadingAnimation.Factor;
+            MIFX_TONEMAP_DISPATCH(d.tone_mapping_mode, MIFX_TARGETS_INSTANCE)
+        }
+        else
+        {
+            MIFX_TONEMAP_DISPATCH(d.tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
+        }
+#undef MIFX_TARGETS_INSTANCE
 #undef MIFX_OUTPUT_INSTANCE
 #else
         MIFX_REQUIRE(false, "mifx_pbr_shade_output: the output stage is not part of the native-storage build");
@@ -741,22 +786,7 @@ mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer,
     // (every argument check precedes the first device call)
     MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && output != nullptr && out_color != nullptr,
                  "mifx_pbr_shade_output: null argument");
-    MIFX_REQUIRE(output->renderer != nullptr, "mifx_pbr_shade_output: output->renderer is null (the PBRRendererShaderParameters block of the frame)");
-    MIFX_REQUIRE(output->debug_view >= 0 && output->debug_view < MIFX_PBR_DEBUG_VIEW_COUNT, "mifx_pbr_shade_output: debug view %d outside [0, %d)", output->debug_view,
-                 int(MIFX_PBR_DEBUG_VIEW_COUNT));
-    MIFX_REQUIRE(output->tone_mapping_mode >= 0 && output->tone_mapping_mode <= MIFX_TONE_MAPPING_MODE_COMMERCE, "mifx_pbr_shade_output: unknown tone mapping mode %d",
-                 output->tone_mapping_mode);
-    MIFX_REQUIRE(output->tone_mapping_mode != MIFX_TONE_MAPPING_MODE_AGX_CUSTOM,
-                 "mifx_pbr_shade_output: TONE_MAPPING_MODE_AGX_CUSTOM: the shader's ToneMappingAttribs carry no AgX look parameters (RenderPBR.psh:533-539)");
-    MIFX_REQUIRE(output->loading_animation >= MIFX_PBR_LOADING_ANIMATION_NONE && output->loading_animation <= MIFX_PBR_LOADING_ANIMATION_TRANSITIONING,
-                 "mifx_pbr_shade_output: unknown loading animation mode %d", output->loading_animation);
-    MIFX_REQUIRE(output->alpha_mode >= MIFX_PBR_ALPHA_MODE_OPAQUE && output->alpha_mode <= MIFX_PBR_ALPHA_MODE_BLEND, "mifx_pbr_shade_output: unknown alpha mode %d", output->alpha_mode);
-    MIFX_REQUIRE((output->flags & ~MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) == 0u, "mifx_pbr_shade_output: unknown flag bits 0x%x",
-                 output->flags & ~MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB);
-    const int view = output->debug_view;
-    MIFX_REQUIRE(!output->unlit || view == MIFX_PBR_DEBUG_VIEW_NONE || view == MIFX_PBR_DEBUG_VIEW_BASE_COLOR || view == MIFX_PBR_DEBUG_VIEW_TRANSPARENCY ||
-                     view == MIFX_PBR_DEBUG_VIEW_WHITE_BASE_COLOR,
-                 "mifx_pbr_shade_output: debug view %d shows a lighting term, which an unlit material (PBR_WORKFLOW_UNLIT) does not have", view);
+    MIFX_CHECK(check_shade_output_desc("mifx_pbr_shade_output", output));
 #ifdef MIFX_STORAGE_H4
     (void)layers; (void)shadows; (void)background; (void)out_specular_ibl;
     ::mifx::set_error("mifx_pbr_shade_output: the shade's output stage is not part of the native-storage build yet");
@@ -771,4 +801,49 @@ mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer,
                                    (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, nullptr, &stage);
 #endif
 }
+
+mifx_status mifx_pbr_shade_targets(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
+                                   const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
+                                   const float background[4], const mifx_image2d* out_color, const mifx_pbr_targets* targets)
+{
+    // (every argument check precedes the first device call)
+    MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && out_color != nullptr && targets != nullptr,
+                 "mifx_pbr_shade_targets: null argument");
+    // output == NULL: view NONE, nothing on -- the footer behind the layered shade
+    static const mifx_pbr_renderer_shader_parameters noRenderer{};
+    mifx_pbr_shade_output_desc identity{};
+    identity.renderer = &noRenderer;
+    if (output == nullptr) output = &identity;
+    MIFX_CHECK(check_shade_output_desc("mifx_pbr_shade_targets", output));
+    const mifx_image2d* const planes[4] = {targets->normal, targets->base_color, targets->material, targets->ibl};
+    static const char* const names[4] = {"normal", "base_color", "material", "ibl"};
+    const mifx_image2d* const sources[4] = {gbuffer->normal, gbuffer->base_color, gbuffer->material, out_color};
+    for (int i = 0; i < 4; ++i)
+    {
+        const mifx_image2d* p = planes[i];
+        MIFX_REQUIRE(p != nullptr && p->data != nullptr, "mifx_pbr_shade_targets: targets->%s is null (all four target planes are required)", names[i]);
+        MIFX_REQUIRE(p->format == MIFX_FORMAT_F32X4 && p->width == out_color->width && p->height == out_color->height && p->pitch_bytes >= p->width * 16u,
+                     "mifx_pbr_shade_targets: targets->%s is %ux%u (format %u, pitch %u): an F32X4 plane of the size of out_color, %ux%u, is required", names[i], p->width, p->height,
+                     p->format, p->pitch_bytes, out_color->width, out_color->height);
+        for (int j = 0; j < 4; ++j)
+            MIFX_REQUIRE(sources[j] == nullptr || p->data != sources[j]->data, "mifx_pbr_shade_targets: targets->%s aliases %s: a target is written while the planes it is computed from are read",
+                         names[i], j < 3 ? "a G-buffer plane" : "out_color");
+        for (int j = 0; j < i; ++j) MIFX_REQUIRE(p->data != planes[j]->data, "mifx_pbr_shade_targets: targets->%s aliases targets->%s", names[i], names[j]);
+    }
+#ifdef MIFX_STORAGE_H4
+    (void)layers; (void)shadows; (void)background;
+    ::mifx::set_error("mifx_pbr_shade_targets: the shade's output stage and its footer are not part of the native-storage build yet");
+    return MIFX_ERR_NOT_IMPLEMENTED;
+#else
+    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
+    const mifx_pbr_layers none{};
+    const Rows rows = ctx->needed_rows(int(out_color->height));
+    MifxKernelTimer timer(ctx, "pbr_shade_targets_kernel");
+    const ShadeOutputStage stage{output, targets};
+    return launch_pbr_shade_layers_impl(ctx->stream, ctx->ibl_apron, gbuffer, layers ? *layers : none, *camera, *attribs, ibl, background, out_color, nullptr, rows.b, rows.e,
+                                   (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, nullptr, &stage);
+#endif
+}
 } // extern "C"
+// (the chain reaches the two entries through this table: a build of the host objects alone has api_chain.cpp but not this file)
+static const bool shade_output_entries_registered = (mifx::g_shade_output_entries = mifx::ShadeOutputEntries{&mifx_pbr_shade_output, &mifx_pbr_shade_targets}, true);

@@ -665,8 +665,8 @@ MIFX_API mifx_status mifx_pbr_layers_from_material_info(const void* material_inf
  * Background pixels get `background` and a zero `out_specular_ibl`.  With no rasteriser behind the entry a pixel that PBR_ALPHA_MODE_MASK discards (:460-465) is treated
  * exactly as a background pixel.  What the G-buffer cannot carry falls through to black as in the shader's own permutation without it: TEXCOORD0 / TEXCOORD1 (no
  * USE_TEXCOORD0 / 1), THICKNESS (no ENABLE_VOLUME), and a layer's views with that layer off in layers->flags.  Out of scope: the OIT transmittance of :548-558,632
- * (mifx_oit_blend applies it), PRIMITIVE.CustomData, and the rewrites of the material / normal / IBL targets that the USD renderer's footer makes under clear coat and the
- * loading animation (Hydrogent USD_Renderer.cpp:101-124).  In the native-storage build the entry returns MIFX_ERR_NOT_IMPLEMENTED. */
+ * (mifx_oit_blend applies it) and PRIMITIVE.CustomData.  The rewrites of the material / normal / IBL targets that the USD renderer's footer makes under clear coat and the
+ * loading animation are mifx_pbr_shade_targets, below.  In the native-storage build the entry returns MIFX_ERR_NOT_IMPLEMENTED. */
 enum /* PBR_Renderer::DebugViewType, PBR/interface/PBR_Renderer.hpp:401-439 (the values of the DEBUG_VIEW_* macros, PBR_Renderer.cpp:1439-1474) */
 {
     MIFX_PBR_DEBUG_VIEW_NONE = 0, MIFX_PBR_DEBUG_VIEW_TEXCOORD0, MIFX_PBR_DEBUG_VIEW_TEXCOORD1, MIFX_PBR_DEBUG_VIEW_BASE_COLOR, MIFX_PBR_DEBUG_VIEW_TRANSPARENCY,
@@ -711,6 +711,37 @@ typedef struct mifx_pbr_shade_output_desc
 MIFX_API mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
                                            const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
                                            const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_specular_ibl);
+
+/* The shade to the last line of the pixel shader: mifx_pbr_shade_output and, behind it, the footer that Hydrogent appends to `main` (the text
+ * USD_Renderer::GetUsdPbrPSMainSource builds, PBR/src/USD_Renderer.cpp:85-168), which writes the G-buffer targets that SSR, SSAO and the composite of HnPostProcess.psh:145-185
+ * read.  For a pixel with a fragment, in the footer's order:
+ *   Normal       = Shading.BaseLayer.Normal                                              (:97)
+ *   MaterialData = (BaseLayer.Srf.PerceptualRoughness, BaseLayer.Metallic)               (:98)
+ *   IBL          = GetBaseLayerSpecularIBL (PBR_Shading.fxh:801-805)                     (:99)   zero for an unlit material: no lighting ran
+ *   clear coat on in layers->flags (:101-117):
+ *     Normal = normalize(lerp(Normal, Clearcoat.Normal, Factor)) (:108), MaterialData = lerp(MaterialData, (Clearcoat.Srf.PerceptualRoughness, 0), Factor) (:109),
+ *     BaseColor.rgb = lerp(BaseColor.rgb, 1, Factor) (:110), IBL = lerp(IBL, GetClearcoatIBL (PBR_Shading.fxh:834-838), Factor) (:115)
+ *   loading_animation != NONE: MaterialData = lerp(MaterialData, (1, 0), renderer->LoadingAnimation.Factor) (:118-120) -- the renderer's Factor in both modes: ALWAYS does not
+ *     force 1 here, unlike the colour at RenderPBR.psh:617
+ *   Transmittance = 1 (:122-124; the OIT transmittance stays in mifx_oit_blend)
+ *   PSOut.Normal = (Normal, 1) (:148), PSOut.BaseColor = (BaseColor.rgb * BaseColor.a, BaseColor.a) (:155), PSOut.Material = (MaterialData * BaseColor.a, 0, BaseColor.a) (:160),
+ *   PSOut.IBL = (IBL * BaseColor.a, BaseColor.a) (:165)
+ * BaseColor is the variable after DEBUG_VIEW_WHITE_BASE_COLOR (RenderPBR.psh:467-471), not premultiplied by the BLEND path of :547 (that touches OutColor only).  No other view
+ * changes a target.  A background pixel and a pixel PBR_ALPHA_MODE_MASK discards have no fragment: Normal, BaseColor and Material receive the caller's G-buffer texel unchanged
+ * (there is no rasteriser here: "not covered by geometry" is "what the plane had") and IBL receives zero, as out_specular_ibl does.  `out_color` is what mifx_pbr_shade_output
+ * writes for the same arguments, bit for bit.  Not in the entry: MeshID (:96,138-141), MotionVec (:143-147), UNSHADED (:91-94, RenderUnshaded.psh) and the OIT transmittance
+ * (RenderPBR.psh:548-558,632).  In the native-storage build the entry returns MIFX_ERR_NOT_IMPLEMENTED. */
+typedef struct mifx_pbr_targets /* all F32X4 of out_color's size, all required; none may alias a G-buffer plane it is computed from, out_color or another target (32 bytes) */
+{
+    const mifx_image2d* normal;     /* PSOut.Normal    (USD_Renderer.cpp:148) */
+    const mifx_image2d* base_color; /* PSOut.BaseColor (:155)                 */
+    const mifx_image2d* material;   /* PSOut.Material  (:160)                 */
+    const mifx_image2d* ibl;        /* PSOut.IBL       (:165)                 */
+} mifx_pbr_targets;
+/* `output` may be NULL: view NONE and nothing on (the footer behind the layered shade).  Refusals: those of mifx_pbr_shade_output, and null, mis-sized or aliasing targets. */
+MIFX_API mifx_status mifx_pbr_shade_targets(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
+                                            const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
+                                            const float background[4], const mifx_image2d* out_color, const mifx_pbr_targets* targets);
 
 /* IBL precompute == PBR_Renderer::PrecomputeBRDF (PBR_Renderer.cpp:548-622) and PBR_Renderer::PrecomputeCubemaps (:729-972).
  * The environment map is a float4 cube with a full (box-filtered) mip chain, as the reference expects of its input SRV. */
@@ -1168,6 +1199,19 @@ MIFX_API mifx_status mifx_chain_set_depth_of_field(mifx_chain* chain, const mifx
  * shade kernel writes its two planes as a by-product, this one does not).  With a row band the sharded SSR's hit fetch shades its pixels with the same layers and shadow maps
  * (every rank holds the planes whole, as it holds the G-buffer). */
 MIFX_API mifx_status mifx_chain_set_material_layers(mifx_chain* chain, const mifx_pbr_layers* layers, const mifx_pbr_shadows* shadows);
+/* The chain's shade to the end of the pixel shader (off by default): the frames executed from now on shade with mifx_pbr_shade_output(output) or, write_targets != 0, with
+ * mifx_pbr_shade_targets(output) -- `output` may then be NULL (view NONE, nothing on).  (NULL, 0) turns it off: the chain launches exactly what it launches without the call.
+ * Combines with mifx_chain_set_material_layers in either order; absent layers are the empty set.  The desc and its renderer block are copied, the motion / mesh-normal planes
+ * borrowed.  With write_targets the chain owns the footer's four planes (allocated once per frame size, freed with the chain), and every pass behind the shade reads them in
+ * place of gbuffer.normal / .base_color / .material -- SSR's passes (R2, which then runs as a pass of its own, included), SSAO, the composite and the selection composite --
+ * and the composite's specular IBL is the IBL target, as in Hydrogent, where these targets ARE the G-buffer of the post-process (USD_Renderer.cpp:148-165,
+ * HnPostProcess.psh:145-185).  Depth, motion and everything the shade itself reads stay the caller's.  Every fusion bit and every overlap mode works on the new planes.
+ * Refused (MIFX_ERR_INVALID_ARG): what mifx_pbr_shade_output refuses of a desc; tone_mapping_mode != 0 and CONVERT_OUTPUT_TO_SRGB (the chain tone-maps and converts at its own
+ * end: HnPostProcessTask runs the renderer without them); a row band or sharding together with this call, in whichever order (the sharded hit fetch has no footer).
+ * Switching it on or off resets no history: reset as after a change of the layers.  In the native-storage build turning it on returns MIFX_ERR_NOT_IMPLEMENTED. */
+MIFX_API mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_output_desc* output /* may be NULL */, int32_t write_targets);
+/* One of the chain's four target planes ("normal", "base_color", "material", "ibl") as the frame executed last wrote it: a view, valid until the next execute or prepare. */
+MIFX_API mifx_status mifx_chain_get_shade_target(mifx_chain* chain, const char* name, mifx_image2d* out);
 /* Selection highlighting in the chain (off by default): every frame executed from now on runs the jump flood of mifx_selection_execute on `selection_depth` and the
  * composite with the selection tail (mifx_composite_execute_selection).  The attribs are copied, the image descriptor too; the device plane is borrowed for every frame
  * until the next call (like the G-buffer: whole on every rank of a row band, so a band needs no exchange for it).  TAA follows, so with a tone mapping mode other than NONE
