@@ -412,8 +412,7 @@ def load():
         _lib.mifx_abi_version.restype = c_u
         _lib.mifx_storage_mode.restype = c_u
         assert bool(_lib.mifx_storage_mode()) == STORAGE_H4 or os.environ.get("MIFX_LIB_PATH"), "the loaded library is not the storage build MIFX_STORAGE asks for"
-        if hasattr(_lib, "mifx_oit_create"):  # (an alternative build of the host objects alone, MIFX_LIB_PATH, has no OIT entries: they live beside their kernels)
-            _declare_oit(_lib)
+        _declare_oit(_lib)
     return _lib
 
 

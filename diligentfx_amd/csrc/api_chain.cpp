@@ -130,9 +130,9 @@ static mifx_status chain_shade(mifx_chain* chain, const mifx_chain_frame* f, con
         const mifx_pbr_layers*            layers  = chain->has_layers ? &chain->layers : nullptr;
         const mifx_pbr_shadows*           shadows = chain->has_shadows ? &chain->shadows : nullptr;
         const mifx_pbr_shade_output_desc* desc    = chain->has_output_desc ? &chain->output_desc : nullptr;
-        if (!chain->write_targets) return mifx::g_shade_output_entries.output(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, spec);
+        if (!chain->write_targets) return mifx_pbr_shade_output(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, spec);
         const mifx_pbr_targets tg{&chain->target_desc[0], &chain->target_desc[1], &chain->target_desc[2], &chain->target_desc[3]}; // (`spec` is target_desc[3]: chain_frame_planes)
-        return mifx::g_shade_output_entries.targets(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, &tg);
+        return mifx_pbr_shade_targets(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, &tg);
     }
     if (chain->has_layers || chain->has_shadows) // mifx_chain_set_material_layers: the layered kernel (no R2 by-product: SSR runs the pass itself)
     {
@@ -1008,11 +1008,6 @@ mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_
         return MIFX_ERR_NOT_IMPLEMENTED;
     }
 #endif
-    if (on && mifx::g_shade_output_entries.targets == nullptr)
-    {
-        ::mifx::set_error("mifx_chain_set_shade_output: this build has no shade kernels (host objects alone)");
-        return MIFX_ERR_NOT_IMPLEMENTED;
-    }
     chain->has_shade_output = on;
     chain->has_output_desc  = output != nullptr;
     chain->write_targets    = write_targets != 0;

@@ -250,6 +250,68 @@ mifx_status mifx_image_export(mifx_postfx* ctx, const mifx_image2d* src, const m
     return launch_image_export(ctx->stream, src, dst);
 }
 
+mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
+                                  const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
+                                  const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_specular_ibl)
+{
+    // (every argument check precedes the first device call)
+    MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && output != nullptr && out_color != nullptr,
+                 "mifx_pbr_shade_output: null argument");
+    MIFX_CHECK(check_shade_output_desc("mifx_pbr_shade_output", output));
+#ifdef MIFX_STORAGE_H4
+    (void)layers; (void)shadows; (void)background; (void)out_specular_ibl;
+    ::mifx::set_error("mifx_pbr_shade_output: the shade's output stage is not part of the native-storage build yet");
+    return MIFX_ERR_NOT_IMPLEMENTED;
+#else
+    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
+    const Rows rows = ctx->needed_rows(int(out_color->height));
+    MifxKernelTimer timer(ctx, "pbr_shade_output_kernel");
+    return launch_pbr_shade_output(ctx->stream, ctx->ibl_apron, gbuffer, layers, *camera, *attribs, ibl, background, out_color, out_specular_ibl, rows.b, rows.e,
+                                   (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, *output, nullptr);
+#endif
+}
+
+mifx_status mifx_pbr_shade_targets(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
+                                   const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
+                                   const float background[4], const mifx_image2d* out_color, const mifx_pbr_targets* targets)
+{
+    // (every argument check precedes the first device call)
+    MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && out_color != nullptr && targets != nullptr,
+                 "mifx_pbr_shade_targets: null argument");
+    // output == NULL: view NONE, nothing on -- the footer behind the layered shade
+    static const mifx_pbr_renderer_shader_parameters noRenderer{};
+    mifx_pbr_shade_output_desc identity{};
+    identity.renderer = &noRenderer;
+    if (output == nullptr) output = &identity;
+    MIFX_CHECK(check_shade_output_desc("mifx_pbr_shade_targets", output));
+    const mifx_image2d* const planes[4] = {targets->normal, targets->base_color, targets->material, targets->ibl};
+    static const char* const names[4] = {"normal", "base_color", "material", "ibl"};
+    const mifx_image2d* const sources[4] = {gbuffer->normal, gbuffer->base_color, gbuffer->material, out_color};
+    for (int i = 0; i < 4; ++i)
+    {
+        const mifx_image2d* p = planes[i];
+        MIFX_REQUIRE(p != nullptr && p->data != nullptr, "mifx_pbr_shade_targets: targets->%s is null (all four target planes are required)", names[i]);
+        MIFX_REQUIRE(p->format == MIFX_FORMAT_F32X4 && p->width == out_color->width && p->height == out_color->height && p->pitch_bytes >= p->width * 16u,
+                     "mifx_pbr_shade_targets: targets->%s is %ux%u (format %u, pitch %u): an F32X4 plane of the size of out_color, %ux%u, is required", names[i], p->width, p->height,
+                     p->format, p->pitch_bytes, out_color->width, out_color->height);
+        for (int j = 0; j < 4; ++j)
+            MIFX_REQUIRE(sources[j] == nullptr || p->data != sources[j]->data, "mifx_pbr_shade_targets: targets->%s aliases %s: a target is written while the planes it is computed from are read",
+                         names[i], j < 3 ? "a G-buffer plane" : "out_color");
+        for (int j = 0; j < i; ++j) MIFX_REQUIRE(p->data != planes[j]->data, "mifx_pbr_shade_targets: targets->%s aliases targets->%s", names[i], names[j]);
+    }
+#ifdef MIFX_STORAGE_H4
+    (void)layers; (void)shadows; (void)background;
+    ::mifx::set_error("mifx_pbr_shade_targets: the shade's output stage and its footer are not part of the native-storage build yet");
+    return MIFX_ERR_NOT_IMPLEMENTED;
+#else
+    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
+    const Rows rows = ctx->needed_rows(int(out_color->height));
+    MifxKernelTimer timer(ctx, "pbr_shade_targets_kernel");
+    return launch_pbr_shade_output(ctx->stream, ctx->ibl_apron, gbuffer, layers, *camera, *attribs, ibl, background, out_color, nullptr, rows.b, rows.e,
+                                   (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, *output, targets);
+#endif
+}
+
 } // extern "C"
 
 // what both entries and mifx_chain_set_shade_output refuse of a desc (every check precedes the first device call)
@@ -271,4 +333,3 @@ mifx_status mifx::check_shade_output_desc(const char* who, const mifx_pbr_shade_
                  "%s: debug view %d shows a lighting term, which an unlit material (PBR_WORKFLOW_UNLIT) does not have", who, view);
     return MIFX_OK;
 }
-mifx::ShadeOutputEntries mifx::g_shade_output_entries{};

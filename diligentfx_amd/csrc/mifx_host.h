@@ -290,16 +290,8 @@ struct SsrMaskOut
 mifx_status launch_pbr_shade(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                              const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth,
                              const mifx_pbr_shadows* shadows = nullptr, const SsrMaskOut* ssrMask = nullptr);
-// what mifx_pbr_shade_output, mifx_pbr_shade_targets and mifx_chain_set_shade_output refuse of a desc, `who` in front of the message (pbr.hip; no device call)
+// what mifx_pbr_shade_output, mifx_pbr_shade_targets and mifx_chain_set_shade_output refuse of a desc, `who` in front of the message (api_pbr.cpp; no device call)
 mifx_status check_shade_output_desc(const char* who, const mifx_pbr_shade_output_desc* output);
-// mifx_pbr_shade_output and mifx_pbr_shade_targets live beside their kernels in pbr.hip, which a build of the host objects alone does not have: the chain calls them through
-// this table, filled by pbr.hip when the library is loaded (null in such a build: mifx_chain_set_shade_output then answers MIFX_ERR_NOT_IMPLEMENTED)
-struct ShadeOutputEntries
-{
-    decltype(&mifx_pbr_shade_output)  output;
-    decltype(&mifx_pbr_shade_targets) targets;
-};
-extern ShadeOutputEntries g_shade_output_entries;
 // the sharded SSR's hit fetch with the layered body: `out_radiance` of launch_pbr_shade_layers is then the plane phase 0 shaded rows [shadedBegin, shadedEnd) of
 struct LayeredHitFetch
 {
@@ -309,6 +301,11 @@ struct LayeredHitFetch
 mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
                                     const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec,
                                     int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows = nullptr, const LayeredHitFetch* hit = nullptr);
+// the layered shade (layers == nullptr: the empty set) with its output stage behind it (`output`, `targets`: validated by the entries, api_pbr.cpp): pbr_shade_output_kernel,
+// or -- targets != nullptr, the footer's four planes, `out_spec` then null -- pbr_shade_targets_kernel.  Not in the native-storage build: the entries refuse before they get here.
+mifx_status launch_pbr_shade_output(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers* layers, const mifx_camera_attribs& camera,
+                                    const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_spec, int row_begin,
+                                    int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc& output, const mifx_pbr_targets* targets);
 // Row-band sharding: the colour of every ray hit that ssr_intersection_kernel recorded in `hitCoords` (packed x | y << 16; 0xffffffff = outside the frame) goes into
 // xyz of `rays` (w = the confidence the march wrote): loaded from `radiance` when the hit row lies in [shadedBegin, shadedEnd) -- the rows this rank shaded -- and
 // otherwise computed on the spot by the shade kernel's own body for that one pixel (the G-buffer and the IBL maps are whole on every rank): no radiance exchange.

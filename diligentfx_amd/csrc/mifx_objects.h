@@ -388,6 +388,15 @@ struct mifx_selection // == HnProcessSelectionTask
     mifx::Plane  tmp[2]; // the leading steps' ping-pong planes (max_distance > 4)
 };
 
+struct mifx_oit // == PBR_Renderer::CreateOITResources (api_oit.cpp)
+{
+    mifx_postfx* ctx = nullptr;
+    uint32_t     w = 0, h = 0, K = 0;
+    void*        layers = nullptr; // w * h * K words
+    mifx::Plane  tail;             // F32X2
+    ~mifx_oit() { if (layers) (void)hipFree(layers); }
+};
+
 struct mifx_chain
 {
     mifx_postfx* ctx   = nullptr;

@@ -449,6 +449,32 @@ static mifx_status make_shadowk(const mifx_pbr_shadows& shadows, ShadowK& sh)
     return MIFX_OK;
 }
 
+// the G-buffer planes of a W x H shade, and its specular-IBL target where there is one (the launchers of the fp32 planes share the checks and their order)
+static mifx_status bind_gbuffer(const mifx_gbuffer* g, const mifx_image2d* out_spec, uint32_t W, uint32_t H, Img& bc, Img& nrm, Img& mat, Img& depth, Img& emis, Img& occ, Img& outS)
+{
+    MIFX_CHECK(to_img_wh(g->base_color, MIFX_FORMAT_F32X4, W, H, "gbuffer.base_color", bc));
+    MIFX_CHECK(to_img_wh(g->normal, MIFX_FORMAT_F32X4, W, H, "gbuffer.normal", nrm));
+    MIFX_CHECK(to_img_wh(g->material, MIFX_FORMAT_F32X4, W, H, "gbuffer.material", mat));
+    MIFX_CHECK(to_img_wh(g->depth, MIFX_FORMAT_F32, W, H, "gbuffer.depth", depth));
+    if (g->emissive) MIFX_CHECK(to_img_wh(g->emissive, MIFX_FORMAT_F32X4, W, H, "gbuffer.emissive", emis));
+    if (g->occlusion) MIFX_CHECK(to_img_wh(g->occlusion, MIFX_FORMAT_F32, W, H, "gbuffer.occlusion", occ));
+    if (out_spec) MIFX_CHECK(to_img_wh(out_spec, MIFX_FORMAT_F32X4, W, H, "out_specular_ibl", outS));
+    return MIFX_OK;
+}
+// the lights of a shade; `entry` = what the message names as the way to hand shadow maps in
+static mifx_status check_lights(const mifx_pbr_shade_attribs& a, const mifx_pbr_shadows* shadows, const char* entry)
+{
+    MIFX_REQUIRE(a.LightCount >= 0 && a.LightCount <= MIFX_PBR_MAX_LIGHTS, "LightCount %d out of range", a.LightCount);
+    for (int i = 0; i < a.LightCount; ++i)
+    {
+        MIFX_REQUIRE(a.Lights[i].Type >= 1 && a.Lights[i].Type <= 3, "light %d: unknown type %d", i, a.Lights[i].Type);
+        if (a.Lights[i].ShadowMapIndex >= 0)
+            MIFX_REQUIRE(shadows != nullptr && uint32_t(a.Lights[i].ShadowMapIndex) < shadows->shadow_map_count, "light %d: ShadowMapIndex %d needs %s and an entry in shadow_maps", i,
+                         a.Lights[i].ShadowMapIndex, entry);
+    }
+    return MIFX_OK;
+}
+
 mifx_status launch_pbr_shade(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                              const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth,
                              const mifx_pbr_shadows* shadows, const SsrMaskOut* ssrMask)
@@ -458,22 +484,8 @@ mifx_status launch_pbr_shade(hipStream_t s, IblApronCache& iblApron, const mifx_
     Img bc, nrm, mat, depth, emis{}, occ{}, outR, outS{};
     MIFX_CHECK(to_img(out_radiance, MIFX_FORMAT_F32X4, "out_radiance", outR));
     outR = rows_of(outR, row_begin, row_end);
-    const uint32_t W = out_radiance->width, H = out_radiance->height;
-    MIFX_CHECK(to_img_wh(g->base_color, MIFX_FORMAT_F32X4, W, H, "gbuffer.base_color", bc));
-    MIFX_CHECK(to_img_wh(g->normal, MIFX_FORMAT_F32X4, W, H, "gbuffer.normal", nrm));
-    MIFX_CHECK(to_img_wh(g->material, MIFX_FORMAT_F32X4, W, H, "gbuffer.material", mat));
-    MIFX_CHECK(to_img_wh(g->depth, MIFX_FORMAT_F32, W, H, "gbuffer.depth", depth));
-    if (g->emissive) MIFX_CHECK(to_img_wh(g->emissive, MIFX_FORMAT_F32X4, W, H, "gbuffer.emissive", emis));
-    if (g->occlusion) MIFX_CHECK(to_img_wh(g->occlusion, MIFX_FORMAT_F32, W, H, "gbuffer.occlusion", occ));
-    if (out_spec) MIFX_CHECK(to_img_wh(out_spec, MIFX_FORMAT_F32X4, W, H, "out_specular_ibl", outS));
-    MIFX_REQUIRE(a.LightCount >= 0 && a.LightCount <= MIFX_PBR_MAX_LIGHTS, "LightCount %d out of range", a.LightCount);
-    for (int i = 0; i < a.LightCount; ++i)
-    {
-        MIFX_REQUIRE(a.Lights[i].Type >= 1 && a.Lights[i].Type <= 3, "light %d: unknown type %d", i, a.Lights[i].Type);
-        if (a.Lights[i].ShadowMapIndex >= 0)
-            MIFX_REQUIRE(shadows != nullptr && uint32_t(a.Lights[i].ShadowMapIndex) < shadows->shadow_map_count,
-                         "light %d: ShadowMapIndex %d needs mifx_pbr_shade_execute_with_shadows and an entry in shadow_maps", i, a.Lights[i].ShadowMapIndex);
-    }
+    MIFX_CHECK(bind_gbuffer(g, out_spec, out_radiance->width, out_radiance->height, bc, nrm, mat, depth, emis, occ, outS));
+    MIFX_CHECK(check_lights(a, shadows, "mifx_pbr_shade_execute_with_shadows"));
     ShadowK sh{};
     if (shadows != nullptr) MIFX_CHECK(make_shadowk(*shadows, sh));
     LutK lut;
@@ -516,18 +528,13 @@ static mifx_status make_lutk_r(const mifx_image2d* im, const char* what, LutK& k
     k.pitch_f = int(im->pitch_bytes / 4u);
     return MIFX_OK;
 }
-// the shade's output stage behind the layered body (mifx_pbr_shade_output, at the end of this file): `out_radiance` is then PSOut.Color
-struct ShadeOutputStage
-{
-    const mifx_pbr_shade_output_desc* desc; // validated by the entry
-    const mifx_pbr_targets* targets = nullptr; // mifx_pbr_shade_targets: the footer's four planes as well (validated by the entry; `out_spec` is then null)
-};
+// output != nullptr: the shade's output stage behind the layered body (launch_pbr_shade_output; `out_radiance` is then PSOut.Color), with the footer's four planes where
+// `targets` is given (`out_spec` is then null); both validated by the entries (api_pbr.cpp)
 static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
                                                 const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance,
                                                 const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows,
-                                                const LayeredHitFetch* hit, const ShadeOutputStage* stage)
+                                                const LayeredHitFetch* hit, const mifx_pbr_shade_output_desc* output, const mifx_pbr_targets* targets)
 {
-    MIFX_REQUIRE(stage == nullptr || hit == nullptr, "mifx_pbr_shade_output: the output stage is not combined with the hit fetch");
     const uint32_t known = MIFX_PBR_LAYER_CLEAR_COAT | MIFX_PBR_LAYER_SHEEN | MIFX_PBR_LAYER_ANISOTROPY | MIFX_PBR_LAYER_IRIDESCENCE | MIFX_PBR_LAYER_TRANSMISSION;
     MIFX_REQUIRE((layers.flags & ~known) == 0u, "layers: unknown flag bits 0x%x", layers.flags & ~known);
     Img bc, nrm, mat, depth, emis{}, occ{}, outR, outS{};
@@ -535,21 +542,8 @@ static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& ib
     if (hit == nullptr) outR = rows_of(outR, row_begin, row_end);
     const uint32_t W = out_radiance->width, H = out_radiance->height;
     if (hit != nullptr) MIFX_REQUIRE(W <= 65536u && H <= 65536u, "launch_pbr_shade_layers: frame %ux%u exceeds the 16-bit hit coordinates", W, H);
-    MIFX_CHECK(to_img_wh(g->base_color, MIFX_FORMAT_F32X4, W, H, "gbuffer.base_color", bc));
-    MIFX_CHECK(to_img_wh(g->normal, MIFX_FORMAT_F32X4, W, H, "gbuffer.normal", nrm));
-    MIFX_CHECK(to_img_wh(g->material, MIFX_FORMAT_F32X4, W, H, "gbuffer.material", mat));
-    MIFX_CHECK(to_img_wh(g->depth, MIFX_FORMAT_F32, W, H, "gbuffer.depth", depth));
-    if (g->emissive) MIFX_CHECK(to_img_wh(g->emissive, MIFX_FORMAT_F32X4, W, H, "gbuffer.emissive", emis));
-    if (g->occlusion) MIFX_CHECK(to_img_wh(g->occlusion, MIFX_FORMAT_F32, W, H, "gbuffer.occlusion", occ));
-    if (out_spec) MIFX_CHECK(to_img_wh(out_spec, MIFX_FORMAT_F32X4, W, H, "out_specular_ibl", outS));
-    MIFX_REQUIRE(a.LightCount >= 0 && a.LightCount <= MIFX_PBR_MAX_LIGHTS, "LightCount %d out of range", a.LightCount);
-    for (int i = 0; i < a.LightCount; ++i)
-    {
-        MIFX_REQUIRE(a.Lights[i].Type >= 1 && a.Lights[i].Type <= 3, "light %d: unknown type %d", i, a.Lights[i].Type);
-        if (a.Lights[i].ShadowMapIndex >= 0)
-            MIFX_REQUIRE(shadows != nullptr && uint32_t(a.Lights[i].ShadowMapIndex) < shadows->shadow_map_count, "light %d: ShadowMapIndex %d needs `shadows` and an entry in shadow_maps", i,
-                         a.Lights[i].ShadowMapIndex);
-    }
+    MIFX_CHECK(bind_gbuffer(g, out_spec, W, H, bc, nrm, mat, depth, emis, occ, outS));
+    MIFX_CHECK(check_lights(a, shadows, "`shadows`"));
     ShadowK sh{};
     if (shadows != nullptr) MIFX_CHECK(make_shadowk(*shadows, sh));
     LayersK ly{};
@@ -587,23 +581,22 @@ static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& ib
     MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k));
     const CamK cam = make_camk(camera, reversedDepth);
     const dim3 block(64, 4, 1);
-    if (stage != nullptr)
+    if (output != nullptr)
     {
 #ifndef MIFX_STORAGE_H4
         Img motion{}, meshNormal{};
-        if (stage->desc->motion) MIFX_CHECK(to_img_wh(stage->desc->motion, MIFX_FORMAT_F32X2, W, H, "output.motion", motion));
-        if (stage->desc->mesh_normal) MIFX_CHECK(to_img_wh(stage->desc->mesh_normal, MIFX_FORMAT_F32X4, W, H, "output.mesh_normal", meshNormal));
-        const mifx_pbr_shade_output_desc& d = *stage->desc; // (validated by mifx_pbr_shade_output)
-        const mifx_pbr_renderer_shader_parameters& r = *d.renderer;
+        if (output->motion) MIFX_CHECK(to_img_wh(output->motion, MIFX_FORMAT_F32X2, W, H, "output.motion", motion));
+        if (output->mesh_normal) MIFX_CHECK(to_img_wh(output->mesh_normal, MIFX_FORMAT_F32X4, W, H, "output.mesh_normal", meshNormal));
+        const mifx_pbr_renderer_shader_parameters& r = *output->renderer;
         OutputK o{};
-        o.debugView = d.debug_view; o.loadingAnimation = d.loading_animation; o.alphaMode = d.alpha_mode; o.unlit = d.unlit != 0;
-        o.srgb = (d.flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0u;
-        o.hasMotion = d.motion != nullptr; o.hasMeshNormal = d.mesh_normal != nullptr;
-        o.alphaMaskCutoff = d.alpha_mask_cutoff;
+        o.debugView = output->debug_view; o.loadingAnimation = output->loading_animation; o.alphaMode = output->alpha_mode; o.unlit = output->unlit != 0;
+        o.srgb = (output->flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0u;
+        o.hasMotion = output->motion != nullptr; o.hasMeshNormal = output->mesh_normal != nullptr;
+        o.alphaMaskCutoff = output->alpha_mask_cutoff;
         o.tm = ToneMapK{r.MiddleGray, r.WhitePoint, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, r.AverageLogLum, 0};
         for (int i = 0; i < 4; ++i) o.highlight[i] = r.HighlightColor[i];
         o.time = r.Time; o.worldScale = r.LoadingAnimation.WorldScale; o.speed = r.LoadingAnimation.Speed;
-        o.factor = d.loading_animation == MIFX_PBR_LOADING_ANIMATION_TRANSITIONING ? r.LoadingAnimation.Factor : 1.0f; // RenderPBR.psh:617-622
+        o.factor = output->loading_animation == MIFX_PBR_LOADING_ANIMATION_TRANSITIONING ? r.LoadingAnimation.Factor : 1.0f; // RenderPBR.psh:617-622
         for (int i = 0; i < 3; ++i) { o.color0[i] = r.LoadingAnimation.Color0[i]; o.color1[i] = r.LoadingAnimation.Color1[i]; }
         o.sceneNearZ = camera.fSceneNearZ; o.sceneFarZ = camera.fSceneFarZ;
 #define MIFX_OUTPUT_INSTANCE(TM)                                                                                                                                                     \
@@ -612,19 +605,19 @@ static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& ib
 #define MIFX_TARGETS_INSTANCE(TM)                                                                                                                                                      \
     hipLaunchKernelGGL((shadows ? pbr_shade_targets_kernel<TM, true> : pbr_shade_targets_kernel<TM, false>), grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, \
                        outR, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, sh, o, motion, meshNormal, tg)
-        if (stage->targets != nullptr)
+        if (targets != nullptr)
         {
             TargetsK tg{};
-            MIFX_CHECK(to_img_wh(stage->targets->normal, MIFX_FORMAT_F32X4, W, H, "targets.normal", tg.normal));
-            MIFX_CHECK(to_img_wh(stage->targets->base_color, MIFX_FORMAT_F32X4, W, H, "targets.base_color", tg.baseColor));
-            MIFX_CHECK(to_img_wh(stage->targets->material, MIFX_FORMAT_F32X4, W, H, "targets.material", tg.material));
-            MIFX_CHECK(to_img_wh(stage->targets->ibl, MIFX_FORMAT_F32X4, W, H, "targets.ibl", tg.ibl));
+            MIFX_CHECK(to_img_wh(targets->normal, MIFX_FORMAT_F32X4, W, H, "targets.normal", tg.normal));
+            MIFX_CHECK(to_img_wh(targets->base_color, MIFX_FORMAT_F32X4, W, H, "targets.base_color", tg.baseColor));
+            MIFX_CHECK(to_img_wh(targets->material, MIFX_FORMAT_F32X4, W, H, "targets.material", tg.material));
+            MIFX_CHECK(to_img_wh(targets->ibl, MIFX_FORMAT_F32X4, W, H, "targets.ibl", tg.ibl));
             tg.animationFactor = r.LoadingAnimation.Factor;
-            MIFX_TONEMAP_DISPATCH(d.tone_mapping_mode, MIFX_TARGETS_INSTANCE)
+            MIFX_TONEMAP_DISPATCH(output->tone_mapping_mode, MIFX_TARGETS_INSTANCE)
         }
         else
         {
-            MIFX_TONEMAP_DISPATCH(d.tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
+            MIFX_TONEMAP_DISPATCH(output->tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
         }
 #undef MIFX_TARGETS_INSTANCE
 #undef MIFX_OUTPUT_INSTANCE
@@ -666,22 +659,25 @@ mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, cons
                                     const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec,
                                     int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const LayeredHitFetch* hit)
 {
-    return launch_pbr_shade_layers_impl(s, iblApron, g, layers, camera, a, ibl, background, out_radiance, out_spec, row_begin, row_end, reversedDepth, shadows, hit, nullptr);
+    return launch_pbr_shade_layers_impl(s, iblApron, g, layers, camera, a, ibl, background, out_radiance, out_spec, row_begin, row_end, reversedDepth, shadows, hit, nullptr, nullptr);
+}
+
+mifx_status launch_pbr_shade_output(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers* layers, const mifx_camera_attribs& camera,
+                                    const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_spec, int row_begin,
+                                    int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc& output, const mifx_pbr_targets* targets)
+{
+    const mifx_pbr_layers none{};
+    return launch_pbr_shade_layers_impl(s, iblApron, g, layers ? *layers : none, camera, a, ibl, background, out_color, out_spec, row_begin, row_end, reversedDepth, shadows, nullptr, &output, targets);
 }
 
 mifx_status launch_pbr_hit_fetch(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                                  const float background[4], Img rays, Img hitCoords, const mifx_image2d* radiance, int shadedBegin, int shadedEnd, bool reversedDepth)
 {
-    Img bc, nrm, mat, depth, emis{}, occ{}, rad;
+    Img bc, nrm, mat, depth, emis{}, occ{}, rad, noSpec{};
     MIFX_CHECK(to_img(radiance, MIFX_FORMAT_F32X4, "radiance", rad));
     const uint32_t W = radiance->width, H = radiance->height;
     MIFX_REQUIRE(W <= 65536u && H <= 65536u, "launch_pbr_hit_fetch: frame %ux%u exceeds the 16-bit hit coordinates", W, H);
-    MIFX_CHECK(to_img_wh(g->base_color, MIFX_FORMAT_F32X4, W, H, "gbuffer.base_color", bc));
-    MIFX_CHECK(to_img_wh(g->normal, MIFX_FORMAT_F32X4, W, H, "gbuffer.normal", nrm));
-    MIFX_CHECK(to_img_wh(g->material, MIFX_FORMAT_F32X4, W, H, "gbuffer.material", mat));
-    MIFX_CHECK(to_img_wh(g->depth, MIFX_FORMAT_F32, W, H, "gbuffer.depth", depth));
-    if (g->emissive) MIFX_CHECK(to_img_wh(g->emissive, MIFX_FORMAT_F32X4, W, H, "gbuffer.emissive", emis));
-    if (g->occlusion) MIFX_CHECK(to_img_wh(g->occlusion, MIFX_FORMAT_F32, W, H, "gbuffer.occlusion", occ));
+    MIFX_CHECK(bind_gbuffer(g, nullptr, W, H, bc, nrm, mat, depth, emis, occ, noSpec));
     LutK lut;
     CubeK irr, pre;
     ShadeK k{};
@@ -775,75 +771,3 @@ mifx_status launch_specgloss_material(hipStream_t s, Img baseColor, Img physical
 }
 
 } // namespace mifx
-
-// The C entry of the shade's output stage lives beside its kernel (as the OIT entries do in oit.hip): a build of the host objects alone neither has nor needs it.
-using namespace mifx;
-extern "C" {
-mifx_status mifx_pbr_shade_output(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
-                                  const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
-                                  const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_specular_ibl)
-{
-    // (every argument check precedes the first device call)
-    MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && output != nullptr && out_color != nullptr,
-                 "mifx_pbr_shade_output: null argument");
-    MIFX_CHECK(check_shade_output_desc("mifx_pbr_shade_output", output));
-#ifdef MIFX_STORAGE_H4
-    (void)layers; (void)shadows; (void)background; (void)out_specular_ibl;
-    ::mifx::set_error("mifx_pbr_shade_output: the shade's output stage is not part of the native-storage build yet");
-    return MIFX_ERR_NOT_IMPLEMENTED;
-#else
-    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
-    const mifx_pbr_layers none{};
-    const Rows rows = ctx->needed_rows(int(out_color->height));
-    MifxKernelTimer timer(ctx, "pbr_shade_output_kernel");
-    const ShadeOutputStage stage{output};
-    return launch_pbr_shade_layers_impl(ctx->stream, ctx->ibl_apron, gbuffer, layers ? *layers : none, *camera, *attribs, ibl, background, out_color, out_specular_ibl, rows.b, rows.e,
-                                   (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, nullptr, &stage);
-#endif
-}
-
-mifx_status mifx_pbr_shade_targets(mifx_postfx* ctx, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers, const mifx_camera_attribs* camera,
-                                   const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
-                                   const float background[4], const mifx_image2d* out_color, const mifx_pbr_targets* targets)
-{
-    // (every argument check precedes the first device call)
-    MIFX_REQUIRE(ctx != nullptr && gbuffer != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && out_color != nullptr && targets != nullptr,
-                 "mifx_pbr_shade_targets: null argument");
-    // output == NULL: view NONE, nothing on -- the footer behind the layered shade
-    static const mifx_pbr_renderer_shader_parameters noRenderer{};
-    mifx_pbr_shade_output_desc identity{};
-    identity.renderer = &noRenderer;
-    if (output == nullptr) output = &identity;
-    MIFX_CHECK(check_shade_output_desc("mifx_pbr_shade_targets", output));
-    const mifx_image2d* const planes[4] = {targets->normal, targets->base_color, targets->material, targets->ibl};
-    static const char* const names[4] = {"normal", "base_color", "material", "ibl"};
-    const mifx_image2d* const sources[4] = {gbuffer->normal, gbuffer->base_color, gbuffer->material, out_color};
-    for (int i = 0; i < 4; ++i)
-    {
-        const mifx_image2d* p = planes[i];
-        MIFX_REQUIRE(p != nullptr && p->data != nullptr, "mifx_pbr_shade_targets: targets->%s is null (all four target planes are required)", names[i]);
-        MIFX_REQUIRE(p->format == MIFX_FORMAT_F32X4 && p->width == out_color->width && p->height == out_color->height && p->pitch_bytes >= p->width * 16u,
-                     "mifx_pbr_shade_targets: targets->%s is %ux%u (format %u, pitch %u): an F32X4 plane of the size of out_color, %ux%u, is required", names[i], p->width, p->height,
-                     p->format, p->pitch_bytes, out_color->width, out_color->height);
-        for (int j = 0; j < 4; ++j)
-            MIFX_REQUIRE(sources[j] == nullptr || p->data != sources[j]->data, "mifx_pbr_shade_targets: targets->%s aliases %s: a target is written while the planes it is computed from are read",
-                         names[i], j < 3 ? "a G-buffer plane" : "out_color");
-        for (int j = 0; j < i; ++j) MIFX_REQUIRE(p->data != planes[j]->data, "mifx_pbr_shade_targets: targets->%s aliases targets->%s", names[i], names[j]);
-    }
-#ifdef MIFX_STORAGE_H4
-    (void)layers; (void)shadows; (void)background;
-    ::mifx::set_error("mifx_pbr_shade_targets: the shade's output stage and its footer are not part of the native-storage build yet");
-    return MIFX_ERR_NOT_IMPLEMENTED;
-#else
-    MIFX_HIP_CHECK(hipSetDevice(ctx->device));
-    const mifx_pbr_layers none{};
-    const Rows rows = ctx->needed_rows(int(out_color->height));
-    MifxKernelTimer timer(ctx, "pbr_shade_targets_kernel");
-    const ShadeOutputStage stage{output, targets};
-    return launch_pbr_shade_layers_impl(ctx->stream, ctx->ibl_apron, gbuffer, layers ? *layers : none, *camera, *attribs, ibl, background, out_color, nullptr, rows.b, rows.e,
-                                   (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, shadows, nullptr, &stage);
-#endif
-}
-} // extern "C"
-// (the chain reaches the two entries through this table: a build of the host objects alone has api_chain.cpp but not this file)
-static const bool shade_output_entries_registered = (mifx::g_shade_output_entries = mifx::ShadeOutputEntries{&mifx_pbr_shade_output, &mifx_pbr_shade_targets}, true);

@@ -749,6 +749,36 @@ def main():
         for seed in range(int(sys.argv[2]), int(sys.argv[3])):
             chain_random(lib, seed, exact)
             print(f"cpu product: chain sequence OK: {seed}", flush=True)
+    elif what == "unhandled":
+        # OIT and the shade's output stage: their host code is linked and runs up to its first launch, which device.py has no handler for
+        import chain_util
+        from diligentfx_amd import synth
+        from shade_output_util import _case, output_desc_fields
+        from util import blue_noise_tables
+
+        def status_of(fn, *a):
+            try:
+                fn(*a)
+            except B.MifxError as e:
+                return str(e)
+            return "MIFX_OK"
+
+        w, h = 16, 8
+        chain = api.Chain(0, *blue_noise_tables())
+        ibl_np = chain_util.make_ibl(pyref.ref_lib(), "ref_")
+        ibl = api.IBLResources(torch.from_numpy(ibl_np["lut"]), [torch.from_numpy(m) for m in ibl_np["irradiance"]], [torch.from_numpy(m) for m in ibl_np["prefiltered"]])
+        sa = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
+        chain.set_shade_output(output_desc_fields(_case("chain")), True)  # (MIFX_OK: a refusal raises)
+        got = status_of(chain.execute, chain.bind_frame(0, synth.make_frame(synth.Scene(), 0, w, h, chain.device), ibl, sa, torch.zeros(h, w, 4)))
+        assert got.startswith("MIFX_ERR_NOT_IMPLEMENTED") and "launch_pbr_shade_output" in got, got
+        chain.close()
+        ctx = api.PostFXContext(0, *blue_noise_tables())
+        oit = api.OITResources(ctx, 5, 3, 4)
+        got = status_of(oit.clear_layers)
+        assert got.startswith("MIFX_ERR_NOT_IMPLEMENTED") and "launch_oit_clear" in got, got
+        oit.close()
+        ctx.close()
+        print("cpu product: scenario OK: the first launch of the shade's output stage and of OIT is refused by name", flush=True)
     elif what == "dof":
         T.test_depth_of_field_follows_the_reference_sequencing(lib)
         print("cpu product: scenario OK: depth of field", flush=True)

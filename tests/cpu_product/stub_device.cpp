@@ -7,6 +7,7 @@
 // path of the product -- nothing in diligentfx_amd/ builds or loads it, and the library that ships fails without its HIP kernels and a device.
 #include "mifx_host.h"
 #include "mifx_grid_host.h"
+#include "mifx_oit_host.h"
 #include "mifx_selection_host.h"
 #include "mifx_shadows_host.h"
 #include <cstdlib>
@@ -98,7 +99,9 @@ template <class... A> static mifx_status record(const char* name, const A&... a)
     c.name   = name;
     c.stream = t_stream;
     (push(c, a), ...);
-    return static_cast<mifx_status>(g_callback(&c));
+    const mifx_status st = static_cast<mifx_status>(g_callback(&c));
+    if (st == MIFX_ERR_NOT_IMPLEMENTED) set_error("launch_%s: the launch callback has no handler that runs it (tests/cpu_product)", name);
+    return st;
 }
 
 // two host helpers that live beside their kernels
@@ -232,6 +235,11 @@ mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, cons
 {
     t_stream = s;
     return record("pbr_shade_layers", iblApron, g, layers, camera, a, ibl, background, out_radiance, out_spec, row_begin, row_end, reversedDepth, shadows, hit);
+}
+mifx_status launch_pbr_shade_output(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers* layers, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc& output, const mifx_pbr_targets* targets)
+{
+    t_stream = s;
+    return record("pbr_shade_output", iblApron, g, layers, camera, a, ibl, background, out_color, out_spec, row_begin, row_end, reversedDepth, shadows, output, targets);
 }
 mifx_status launch_pbr_hit_fetch(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], Img rays, Img hitCoords, const mifx_image2d* radiance, int shadedBegin, int shadedEnd, bool reversedDepth)
 {
@@ -402,6 +410,36 @@ mifx_status launch_copy_frame_grid(hipStream_t s, Img in, bool packedIn, Img dep
 {
     t_stream = s;
     return record("copy_frame_grid", in, packedIn, depth, out, attr, ave_log_lum, tonemap_flags, aveLum, cam, a, grid_flags);
+}
+mifx_status launch_oit_clear(hipStream_t s, const OitK& k)
+{
+    t_stream = s;
+    return record("oit_clear", k);
+}
+mifx_status launch_oit_update(hipStream_t s, const OitK& k, const OitSliceK& slice)
+{
+    t_stream = s;
+    return record("oit_update", k, slice);
+}
+mifx_status launch_oit_attenuate(hipStream_t s, const OitK& k, const OitTargetsK& targets)
+{
+    t_stream = s;
+    return record("oit_attenuate", k, targets);
+}
+mifx_status launch_oit_blend(hipStream_t s, const OitK& k, const OitSliceK& slice, const OitTargetsK& targets)
+{
+    t_stream = s;
+    return record("oit_blend", k, slice, targets);
+}
+mifx_status launch_oit_build(hipStream_t s, const OitK& k, const OitSlicesK& tab)
+{
+    t_stream = s;
+    return record("oit_build", k, tab);
+}
+mifx_status launch_oit_resolve(hipStream_t s, const OitK& k, const OitSlicesK& tab, const OitTargetsK& targets)
+{
+    t_stream = s;
+    return record("oit_resolve", k, tab, targets);
 }
 mifx_status launch_jump_flood(hipStream_t s, Img selectionDepth, float clearDepth, int iterations, Img tmp0, Img tmp1, Img out, int rowBegin, int rowEnd)
 {

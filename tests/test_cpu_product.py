@@ -47,7 +47,14 @@ def test_the_launcher_stubs_are_what_the_generator_prints():
     marker = [i for i, line in enumerate(lines) if line.startswith("// ---") and "the launchers" in line]
     assert len(marker) == 1, marker
     assert "".join(lines[marker[0] + 1:]) == r.stdout, "stub_device.cpp: re-run tests/cpu_product/gen_stubs.py and paste its output below the marker"
-    assert r.stdout.count("mifx_status launch_") >= 61  # (the 55 launchers of mifx_host.h and the six of the mifx_*_host.h headers)
+    assert r.stdout.count("mifx_status launch_") >= 68  # (the 56 launchers of mifx_host.h and the twelve of the mifx_*_host.h headers)
+
+
+def test_oit_and_the_shade_output_stage_are_linked_and_refused_at_their_first_launch(cpu_lib):
+    """The host code of the shade's output stage (api_pbr.cpp, api_chain.cpp) and of OIT (api_oit.cpp) is part of the CPU build and runs up to its first launch, which has
+    no handler in device.py: mifx_chain_set_shade_output(desc, 1) returns MIFX_OK and the mifx_chain_execute of a 16 x 8 frame behind it MIFX_ERR_NOT_IMPLEMENTED with
+    launch_pbr_shade_output in mifx_last_error; mifx_oit_create at 5 x 3, K = 4 succeeds and mifx_oit_clear_layers answers the same with launch_oit_clear."""
+    assert "cpu product: scenario OK: the first launch of the shade's output stage and of OIT is refused by name" in run(cpu_lib, "unhandled")
 
 
 def test_host_objects_on_the_cpu_equal_the_reference_sequencing(cpu_lib):
