@@ -677,6 +677,35 @@ class ProcessSelection:
         return out
 
 
+def _pbr_shadows(shadows):
+    """mifx_pbr_shadows from (shadow_map float32 tensor (slices, H, W), infos, pcf_filter_size) as pbr_shade() takes it, or None; returns (struct or None, keep-alive)"""
+    if shadows is None:
+        return None, None
+    sm, infos, pcf = shadows
+    assert sm.dtype == torch.float32 and sm.dim() == 3 and sm.is_contiguous()
+    arr = B.ShadowMapArray(sm.data_ptr(), sm.shape[2], sm.shape[1], sm.shape[0], sm.stride(1) * 4, sm.stride(0) * 4)
+    rows = (B.PBRShadowMapInfo * len(infos))()
+    for i, r in enumerate(infos):
+        rows[i] = r if isinstance(r, B.PBRShadowMapInfo) else B.PBRShadowMapInfo.from_buffer_copy(r.astype("float32").tobytes())
+    return B.PBRShadows(ctypes.pointer(arr), ctypes.cast(rows, ctypes.POINTER(B.PBRShadowMapInfo)), len(infos), pcf), (arr, rows, sm)
+
+
+def transparent_slice(s):
+    """mifx_transparent_slice of one transparent draw.  s: dict with `gbuffer` (base_color, normal, material, depth [, emissive, occlusion]: the draw's own G-buffer, depth at
+    the background value where it has no fragment) and optionally `layers` + `flags` [+ iridescence_ior, anisotropy_rotation] as pbr_shade_layers() takes them and
+    `color_alpha`.  Returns (struct, keep-alive)."""
+    g = s["gbuffer"]
+    imgs = {k: B.image(g[k]) for k in ("base_color", "normal", "material", "depth", "emissive", "occlusion") if g.get(k) is not None}
+    p = lambda k: ctypes.pointer(imgs[k]) if k in imgs else None  # noqa: E731
+    gb = B.GBuffer(p("base_color"), p("normal"), p("material"), p("depth"), p("emissive"), p("occlusion"))
+    ly = limgs = None
+    if s.get("layers") is not None and s.get("flags", 0):
+        limgs = {k: B.image(s["layers"][k]) for k in B.PBR_LAYER_PLANES if s["layers"].get(k) is not None}
+        ly = B.PBRLayers(s["flags"], s.get("iridescence_ior", 1.3), s.get("anisotropy_rotation", 0.0), 0, *[ctypes.pointer(limgs[k]) if k in limgs else None for k in B.PBR_LAYER_PLANES])
+    alpha = B.image(s["color_alpha"]) if s.get("color_alpha") is not None else None
+    return B.TransparentSlice(gb, ctypes.pointer(ly) if ly is not None else None, ctypes.pointer(alpha) if alpha is not None else None), (imgs, ly, limgs, alpha, s)
+
+
 OIT_SLICE_PLANES = ("depth", "base_color", "material", "radiance", "specular_ibl", "color_alpha")  # the members of mifx_oit_slice, in order
 OIT_TARGETS = ("color", "base_color", "material", "ibl")  # the members of mifx_oit_targets, in order
 
@@ -746,6 +775,17 @@ class OITResources:
         od = B.image(opaque_depth) if opaque_depth is not None else None
         self.ctx.sync_stream()
         B.check(self.lib.mifx_oit_blend(self.handle, arr, ctypes.byref(od) if od is not None else None, ctypes.byref(camera), ctypes.byref(t)))
+
+    def shade_blend(self, slice_, camera: B.CameraAttribs, attribs: B.PBRShadeAttribs, ibl: "IBLResources", targets, opaque_depth=None, shadows=None):
+        """One transparent draw shaded and blended in one launch (mifx_oit_shade_blend): slice_ as transparent_slice() takes it -- the draw's G-buffer, not shaded
+        planes.  Equals pbr_shade_layers() on the slice (background 0) followed by blend(), bit for bit.  shadows: as pbr_shade()."""
+        x, keep = transparent_slice(slice_)
+        t, keep_t = self._targets(targets)
+        od = B.image(opaque_depth) if opaque_depth is not None else None
+        sh, keep_s = _pbr_shadows(shadows)
+        self.ctx.sync_stream()
+        B.check(self.lib.mifx_oit_shade_blend(self.handle, ctypes.byref(x), ctypes.byref(od) if od is not None else None, ctypes.byref(camera), ctypes.byref(attribs),
+                                              ctypes.byref(ibl.struct), ctypes.byref(sh) if sh is not None else None, ctypes.byref(t)))
 
     def build_layers(self, slices, camera: B.CameraAttribs, opaque_depth=None):
         arr, keep = self._slices(slices)
@@ -1261,6 +1301,34 @@ class Chain:
             assert not desc, f"unknown fields of mifx_pbr_shade_output_desc: {sorted(desc)}"
         B.check(self.lib.mifx_chain_set_shade_output(self.handle, ctypes.byref(d) if d is not None else None, ctypes.c_int32(1 if targets else 0)))
         self._shade_targets = bool(targets)
+
+    def set_transparency(self, slices, layer_count=4):
+        """Transparent draws in the chain (mifx_chain_set_transparency): every frame from now on builds `layer_count` OIT layers over `slices` (each as transparent_slice()
+        takes it), attenuates the colour and the BaseColor / Material / IBL targets and shades and blends every slice behind the opaque shade.  Needs
+        set_shade_output(..., targets=True).  None or an empty list turns it off.  The tensors are kept alive here (the library borrows them)."""
+        if not slices:
+            self._transparency_keep = None
+            B.check(self.lib.mifx_chain_set_transparency(self.handle, ctypes.c_uint32(layer_count), None, ctypes.c_uint32(0)))
+            return
+        made = [transparent_slice(s) for s in slices]
+        arr = (B.TransparentSlice * len(made))(*[m[0] for m in made])
+        B.check(self.lib.mifx_chain_set_transparency(self.handle, ctypes.c_uint32(layer_count), arr, ctypes.c_uint32(len(made))))
+        self._transparency_keep = [m[1] for m in made]
+
+    def oit(self):
+        """Non-owning view of the chain's OITResources (mifx_chain_get_effect "oit"); None until a frame ran with transparency on"""
+        h = ctypes.c_void_p()
+        B.check(self.lib.mifx_chain_get_effect(self.handle, b"oit", ctypes.byref(h)))
+        if not h:
+            return None
+        o = OITResources.__new__(OITResources)
+        o.ctx, o.lib, o.handle, o.plane_dtype = self.postfx, self.lib, h, B.storage_dtype()
+        o.close = lambda: None  # the chain owns it
+        tail, data, words = B.Image2D(), ctypes.c_void_p(), ctypes.c_uint64()
+        B.check(self.lib.mifx_oit_get_tail(h, ctypes.byref(tail)))
+        B.check(self.lib.mifx_oit_get_layers(h, ctypes.byref(data), ctypes.byref(words)))
+        o.width, o.height, o.layer_count = tail.width, tail.height, words.value // (tail.width * tail.height)
+        return o
 
     def shade_target(self, name):
         """One of the chain's target planes ("normal", "base_color", "material", "ibl") as the last frame wrote it (mifx_chain_get_shade_target): a view."""

@@ -376,6 +376,10 @@ class OITTargets(ctypes.Structure):  # mifx_oit_targets: blended in place
     _fields_ = [("color", PImage), ("base_color", PImage), ("material", PImage), ("ibl", PImage)]
 
 
+class TransparentSlice(ctypes.Structure):  # mifx_transparent_slice: one transparent draw as its own G-buffer (mifx_oit_shade_blend, mifx_chain_set_transparency)
+    _fields_ = [("gbuffer", GBuffer), ("layers", ctypes.POINTER(PBRLayers)), ("color_alpha", PImage)]
+
+
 class ChainFrame(ctypes.Structure):
     _fields_ = [("frame", FrameDesc), ("gbuffer", GBuffer), ("motion", PImage), ("prev_depth", PImage),
                 ("curr_camera", ctypes.POINTER(CameraAttribs)), ("prev_camera", ctypes.POINTER(CameraAttribs)),
@@ -432,7 +436,13 @@ def _declare_oit(lib):
     lib.mifx_oit_set_fusion.argtypes, lib.mifx_oit_set_fusion.restype = [c_i], c_i
     lib.mifx_oit_create_check.argtypes = [u, u, u]
     lib.mifx_oit_frame_check.argtypes = [u, u, PS, u, PImage, PC, PT]
-    for name in ("create", "clear_layers", "update_layers", "apply_attenuation", "blend", "build_layers", "resolve", "get_layers", "get_tail", "create_check", "frame_check"):
+    PX, PA, PI, PH = ctypes.POINTER(TransparentSlice), ctypes.POINTER(PBRShadeAttribs), ctypes.POINTER(IBL), ctypes.POINTER(PBRShadows)
+    lib.mifx_oit_shade_blend.argtypes = [c_p, PX, PImage, PC, PA, PI, PH, PT]
+    lib.mifx_oit_shade_blend_check.argtypes = [u, u, u, PX, PImage, PC, PA, PI, PH, PT]
+    lib.mifx_chain_set_transparency.argtypes, lib.mifx_chain_set_transparency.restype = [c_p, u, PX, u], c_i
+    lib.mifx_chain_set_transparency_fusion.argtypes, lib.mifx_chain_set_transparency_fusion.restype = [c_i], c_i
+    for name in ("create", "clear_layers", "update_layers", "apply_attenuation", "blend", "build_layers", "resolve", "get_layers", "get_tail", "create_check", "frame_check",
+                 "shade_blend", "shade_blend_check"):
         getattr(lib, "mifx_oit_" + name).restype = c_i
 
 

@@ -30,6 +30,7 @@ mifx_chain::~mifx_chain()
     if (lane_h) (void)hipStreamDestroy(lane_h);
     mifx::chain_detach_comm(this);
     mifx_selection_destroy(selection);
+    mifx_oit_destroy(oit);
     mifx_autoexposure_destroy(auto_exposure);
     mifx_bloom_destroy(bloom);
     mifx_dof_destroy(dof);
@@ -95,6 +96,7 @@ mifx_status mifx_chain_get_effect(mifx_chain* chain, const char* name, void** ou
     else if (n == "bloom") *out = chain->bloom;
     else if (n == "dof") *out = chain->dof; // NULL until mifx_chain_set_depth_of_field enabled it
     else if (n == "selection") *out = chain->selection; // NULL until mifx_chain_set_selection turned it on
+    else if (n == "oit") *out = chain->oit;             // NULL until a frame ran with mifx_chain_set_transparency on
     else
     {
         set_error("mifx_chain_get_effect: unknown effect '%s'", name);
@@ -115,6 +117,44 @@ mifx_status mifx_chain_reset_history(mifx_chain* chain)
     return mifx_taa_reset_history(chain->taa);
 }
 
+// The chain's transparent draws take the fused launch (mifx_chain_set_transparency_fusion; the measurement behind the default: DESIGN.md section 4)
+static bool g_transparency_fusion = true;
+
+// mifx_chain_set_transparency: HnBeginOITPassTask, the transparent draws and HnEndOITPassTask directly behind the opaque shade, on its stream.  The layers are built over
+// the slices' depth and opacity against the frame's depth, the opaque colour and the BaseColor / Material / IBL targets are attenuated, then every slice is shaded and
+// blended in submission order -- one launch per slice, or (fusion off) the layered shade into the chain's two slice planes and mifx_oit_blend.
+static mifx_status chain_transparency(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* radiance)
+{
+    mifx_postfx*            ctx     = chain->ctx;
+    const uint32_t          n       = uint32_t(chain->transparent.size());
+    const mifx_pbr_shadows* shadows = chain->has_shadows ? &chain->shadows : nullptr;
+    const mifx_oit_targets  tg{radiance, &chain->target_desc[1], &chain->target_desc[2], &chain->target_desc[3]};
+    const mifx_image2d      rad = chain->slice_radiance.desc(), spec = chain->slice_specular_ibl.desc();
+    mifx_oit_slice          slices[MIFX_OIT_MAX_SLICES];
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const mifx_transparent_slice& s = chain->transparent[i].s;
+        // (the two shaded planes exist in the unfused path only, and only mifx_oit_blend reads them)
+        slices[i] = mifx_oit_slice{s.gbuffer.depth, s.gbuffer.base_color, s.gbuffer.material, g_transparency_fusion ? nullptr : &rad, g_transparency_fusion ? nullptr : &spec, s.color_alpha};
+    }
+    MIFX_CHECK(mifx_oit_build_layers(chain->oit, slices, n, f->gbuffer.depth, f->curr_camera));
+    MIFX_CHECK(mifx_oit_apply_attenuation(chain->oit, &tg));
+    const mifx_pbr_layers none{};
+    const float           zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const mifx_transparent_slice& s = chain->transparent[i].s;
+        if (g_transparency_fusion)
+        {
+            MIFX_CHECK(mifx_oit_shade_blend(chain->oit, &s, f->gbuffer.depth, f->curr_camera, f->pbr, f->ibl, shadows, &tg));
+            continue;
+        }
+        MIFX_CHECK(mifx_pbr_shade_execute_layers(ctx, &s.gbuffer, s.layers ? s.layers : &none, f->curr_camera, f->pbr, f->ibl, shadows, zero, &rad, &spec));
+        MIFX_CHECK(mifx_oit_blend(chain->oit, &slices[i], f->gbuffer.depth, f->curr_camera, &tg));
+    }
+    return MIFX_OK;
+}
+
 // The forward shade of the unsharded frame.  With fuse_ssr_mask the kernel also writes SSR's roughness / reflection-mask planes (pass R2 reads the same material
 // and depth texels and nothing else): mifx_ssr_execute then finds them done for this frame.
 // With a row band the shade runs on the rows of the composite; the by-product is needed on the rows of the ray march, a few rows more: the shade then covers
@@ -132,7 +172,8 @@ static mifx_status chain_shade(mifx_chain* chain, const mifx_chain_frame* f, con
         const mifx_pbr_shade_output_desc* desc    = chain->has_output_desc ? &chain->output_desc : nullptr;
         if (!chain->write_targets) return mifx_pbr_shade_output(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, spec);
         const mifx_pbr_targets tg{&chain->target_desc[0], &chain->target_desc[1], &chain->target_desc[2], &chain->target_desc[3]}; // (`spec` is target_desc[3]: chain_frame_planes)
-        return mifx_pbr_shade_targets(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, &tg);
+        MIFX_CHECK(mifx_pbr_shade_targets(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, &tg));
+        return chain->transparent.empty() ? MIFX_OK : chain_transparency(chain, f, radiance);
     }
     if (chain->has_layers || chain->has_shadows) // mifx_chain_set_material_layers: the layered kernel (no R2 by-product: SSR runs the pass itself)
     {
@@ -328,6 +369,27 @@ extern "C++" mifx_status mifx::chain_prepare_resources(mifx_chain* chain, const 
     MIFX_CHECK(chain->composite.alloc(W, H, MIFX_FORMAT_F32X4));
     if (chain->has_shade_output && chain->write_targets)
         for (mifx::Plane& p : chain->targets) MIFX_CHECK(p.alloc(W, H, MIFX_FORMAT_F32X4)); // (once per size; freed with the chain)
+    if (!chain->transparent.empty())
+    {
+        // every refusal of the frame's transparent draws before its first launch: the planes of every slice against the frame's size, what mifx_oit_shade_blend refuses
+        MIFX_REQUIRE(chain->has_shade_output && chain->write_targets && chain->band.empty(),
+                     "mifx_chain_execute: transparency needs mifx_chain_set_shade_output with write_targets and no row band");
+        const mifx_image2d     planes[4] = {chain->radiance.desc(), chain->targets[1].desc(), chain->targets[2].desc(), chain->targets[3].desc()};
+        const mifx_oit_targets tg{&planes[0], &planes[1], &planes[2], &planes[3]};
+        for (const mifx_chain::TransparentSlice& t : chain->transparent)
+            MIFX_CHECK(mifx_oit_shade_blend_check(W, H, ctx->flags, &t.s, f->gbuffer.depth, f->curr_camera, f->pbr, f->ibl, chain->has_shadows ? &chain->shadows : nullptr, &tg));
+        if (chain->oit == nullptr || chain->oit->w != W || chain->oit->h != H || chain->oit->K != chain->oit_layer_count)
+        {
+            mifx_oit_destroy(chain->oit); // (hipFree waits for the kernels that still read it)
+            chain->oit = nullptr;
+            MIFX_CHECK(mifx_oit_create(ctx, W, H, chain->oit_layer_count, &chain->oit));
+        }
+        if (!g_transparency_fusion)
+        {
+            MIFX_CHECK(chain->slice_radiance.alloc(W, H, MIFX_FORMAT_F32X4));
+            MIFX_CHECK(chain->slice_specular_ibl.alloc(W, H, MIFX_FORMAT_F32X4));
+        }
+    }
     return MIFX_OK;
 }
 
@@ -1001,6 +1063,9 @@ mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_
     const bool on = output != nullptr || write_targets != 0;
     MIFX_REQUIRE(!on || chain->band.empty(),
                  "mifx_chain_set_shade_output: not combined with a row band or sharding (mifx_chain_set_row_band / _set_sharding): the sharded hit fetch has no output stage or footer");
+    MIFX_REQUIRE(write_targets != 0 || chain->transparent.empty(),
+                 "mifx_chain_set_shade_output: write_targets goes off while mifx_chain_set_transparency is on: the transparent draws blend into the chain's own target planes "
+                 "(turn transparency off first)");
 #ifdef MIFX_STORAGE_H4
     if (on)
     {
@@ -1026,6 +1091,77 @@ mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_
     }
     chain->prep_consumed = false; // (which planes the lanes trade and read changes: the next frame forks from the context stream once)
     return MIFX_OK;
+}
+
+mifx_status mifx_chain_set_transparency(mifx_chain* chain, uint32_t layer_count, const mifx_transparent_slice* slices, uint32_t count)
+{
+    // (no device call: every refusal is an argument check)
+    const char* who = "mifx_chain_set_transparency";
+    MIFX_REQUIRE(chain != nullptr, "%s: null chain", who);
+    if (slices == nullptr || count == 0u) // off: the chain launches what it launched before
+    {
+        chain->transparent.clear();
+        return MIFX_OK;
+    }
+#ifdef MIFX_STORAGE_H4
+    (void)layer_count;
+    ::mifx::set_error("%s: the fused shade-and-blend is not part of the native-storage build yet", who);
+    return MIFX_ERR_NOT_IMPLEMENTED;
+#else
+    MIFX_REQUIRE(count <= uint32_t(MIFX_OIT_MAX_SLICES), "%s: %u slices are more than MIFX_OIT_MAX_SLICES (%d)", who, count, MIFX_OIT_MAX_SLICES);
+    MIFX_CHECK(mifx_oit_create_check(1u, 1u, layer_count));
+    MIFX_REQUIRE(chain->has_shade_output && chain->write_targets,
+                 "%s: needs mifx_chain_set_shade_output with write_targets: the transparent draws blend into the chain's own BaseColor / Material / IBL planes (without "
+                 "them base colour and material are the caller's const planes)", who);
+    // (a row band needs no check of its own: mifx_chain_set_shade_output and mifx_chain_set_row_band refuse each other, in either order)
+    for (uint32_t i = 0; i < count; ++i)
+    {
+        const mifx_gbuffer& g = slices[i].gbuffer;
+        MIFX_REQUIRE(g.base_color != nullptr && g.normal != nullptr && g.material != nullptr && g.depth != nullptr, "%s: slice %u: base_color, normal, material and depth must not be null",
+                     who, i);
+    }
+    std::vector<mifx_chain::TransparentSlice> copy(count);
+    for (uint32_t i = 0; i < count; ++i) // (the vector has its final size: the pointers below stay good until the next call)
+    {
+        mifx_chain::TransparentSlice& t = copy[i];
+        t.s = slices[i];
+        const mifx_image2d** plane[6] = {&t.s.gbuffer.base_color, &t.s.gbuffer.normal, &t.s.gbuffer.material, &t.s.gbuffer.depth, &t.s.gbuffer.emissive, &t.s.gbuffer.occlusion};
+        for (int j = 0; j < 6; ++j)
+            if (*plane[j] != nullptr)
+            {
+                t.gbuffer_images[j] = **plane[j];
+                *plane[j] = &t.gbuffer_images[j];
+            }
+        if (t.s.color_alpha != nullptr)
+        {
+            t.alpha = *t.s.color_alpha;
+            t.s.color_alpha = &t.alpha;
+        }
+        if (t.s.layers != nullptr)
+        {
+            t.layers = *t.s.layers;
+            t.s.layers = &t.layers;
+            const mifx_image2d** slot[9] = {&t.layers.clearcoat, &t.layers.clearcoat_normal, &t.layers.sheen, &t.layers.anisotropy, &t.layers.tangent,
+                                            &t.layers.iridescence, &t.layers.transmission, &t.layers.sheen_albedo_scaling_lut, &t.layers.preintegrated_charlie};
+            for (int j = 0; j < 9; ++j)
+                if (*slot[j] != nullptr)
+                {
+                    t.layer_images[j] = **slot[j];
+                    *slot[j] = &t.layer_images[j];
+                }
+        }
+    }
+    chain->transparent.swap(copy);
+    chain->oit_layer_count = layer_count;
+    return MIFX_OK;
+#endif
+}
+
+int32_t mifx_chain_set_transparency_fusion(int32_t enable)
+{
+    const int32_t prev    = g_transparency_fusion ? 1 : 0;
+    g_transparency_fusion = enable != 0;
+    return prev;
 }
 
 mifx_status mifx_chain_get_shade_target(mifx_chain* chain, const char* name, mifx_image2d* out)

@@ -1,13 +1,17 @@
 // api_oit.cpp -- C ABI of the layered order-independent transparency (include/mifx.h: mifx_oit_*): the argument checks of its entries and the sequencing of the six
-// kernels, whose launchers are in oit.hip (mifx_oit_host.h).
+// kernels, whose launchers are in oit.hip (mifx_oit_host.h), and of mifx_oit_shade_blend, one transparent draw shaded and blended by one kernel of pbr.hip.
 #include "mifx_objects.h"
 #include "mifx_oit_host.h"
+#include "mifx_oit_shade_launch.h"
 
 using namespace mifx;
 
 // The fused kernels are the default: 2.0 - 3.3 times faster than the sequence at 3840 x 2160, K = 4, L = 2 .. 8, both shapes at the device's copy rate for the bytes
 // they move (profiles/oit_bench.json, tools/oit_bench.py; mifx_oit_set_fusion(0) is the sequence).
 static bool g_oit_fusion = true;
+
+// installed by pbr.hip when the library is loaded (mifx_oit_shade_launch.h); a build without the device code leaves it null
+decltype(&mifx::launch_oit_shade_blend) mifx::g_launch_oit_shade_blend = nullptr;
 
 namespace
 {
@@ -110,6 +114,43 @@ mifx_status run_resolve(mifx_oit* o, const OitFrameK& f)
 {
     MifxKernelTimer timer(o->ctx, "oit_resolve_kernel");
     return launch_oit_resolve(o->ctx->stream, make_oitk(o, f), f.tab, f.targets);
+}
+// mifx_oit_shade_blend and its check entry: the argument checks of frame_check (opaque depth, camera, targets; the slice's depth and base colour are the G-buffer's,
+// checked with it) and of the layered shade (launch_oit_shade_blend: G-buffer, layers, lights, shadows, IBL), every plane of w x h; `o` == nullptr: the checks alone
+mifx_status shade_blend(mifx_oit* o, uint32_t w, uint32_t h, uint32_t postfx_flags, const mifx_transparent_slice* slice, const mifx_image2d* opaque_depth,
+                        const mifx_camera_attribs* camera, const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_oit_targets* targets,
+                        const char* who)
+{
+    MIFX_REQUIRE(slice != nullptr && camera != nullptr && attribs != nullptr && ibl != nullptr && targets != nullptr, "%s: null argument", who);
+#ifdef MIFX_STORAGE_H4
+    (void)o; (void)w; (void)h; (void)postfx_flags; (void)opaque_depth; (void)shadows;
+    ::mifx::set_error("%s: the fused shade-and-blend is not part of the native-storage build yet", who);
+    return MIFX_ERR_NOT_IMPLEMENTED;
+#else
+    OitFrameK f;
+    MIFX_CHECK(frame_check(w, h, nullptr, 0u, opaque_depth, camera, targets, who, f));
+    const bool shadeReversed = (postfx_flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0;
+    MIFX_REQUIRE((f.cam.reversed != 0) == shadeReversed,
+                 "%s: reversed depth disagrees: the camera says %s (fNearPlaneDepth %g, fFarPlaneDepth %g: what the OIT reads), the context's MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH "
+                 "says %s (what the shade reads)",
+                 who, f.cam.reversed ? "reversed" : "not reversed", double(camera->fNearPlaneDepth), double(camera->fFarPlaneDepth), shadeReversed ? "reversed" : "not reversed");
+    if (g_launch_oit_shade_blend == nullptr)
+    {
+        ::mifx::set_error("%s: launch_oit_shade_blend: this build of the library carries no device code for it", who);
+        return MIFX_ERR_NOT_IMPLEMENTED;
+    }
+    if (o == nullptr)
+    {
+        OitK k{};
+        k.w = int(w); k.h = int(h); k.cam = f.cam;
+        IblApronCache none;
+        return g_launch_oit_shade_blend(nullptr, none, k, f.targets, &slice->gbuffer, slice->layers, slice->color_alpha, *camera, *attribs, ibl, shadeReversed, shadows, true);
+    }
+    MIFX_HIP_CHECK(hipSetDevice(o->ctx->device));
+    MifxKernelTimer timer(o->ctx, "oit_shade_blend_kernel"); // (includes the two cube-apron launches of the call, where the maps are not declared static)
+    return g_launch_oit_shade_blend(o->ctx->stream, o->ctx->ibl_apron, make_oitk(o, f), f.targets, &slice->gbuffer, slice->layers, slice->color_alpha, *camera, *attribs, ibl, shadeReversed,
+                                  shadows, false);
+#endif
 }
 } // namespace
 
@@ -216,6 +257,24 @@ mifx_status mifx_oit_blend(mifx_oit* oit, const mifx_oit_slice* slice, const mif
     OitFrameK f;
     MIFX_CHECK(frame_check(oit->w, oit->h, slice, 1u, opaque_depth, camera, targets, who, f));
     MIFX_OIT_RUN(MIFX_CHECK(run_blend(oit, f, 0)););
+}
+
+// one transparent draw, shaded and blended: the layered shade's body and the colour pass above in one launch (mifx_oit_shade.h)
+mifx_status mifx_oit_shade_blend(mifx_oit* oit, const mifx_transparent_slice* slice, const mifx_image2d* opaque_depth, const mifx_camera_attribs* camera,
+                                 const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_oit_targets* targets)
+{
+    const char* who = "mifx_oit_shade_blend";
+    MIFX_REQUIRE(oit != nullptr, "%s: null object", who);
+    return shade_blend(oit, oit->w, oit->h, oit->ctx->flags, slice, opaque_depth, camera, attribs, ibl, shadows, targets, who);
+}
+
+mifx_status mifx_oit_shade_blend_check(uint32_t width, uint32_t height, uint32_t postfx_feature_flags, const mifx_transparent_slice* slice, const mifx_image2d* opaque_depth,
+                                       const mifx_camera_attribs* camera, const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows,
+                                       const mifx_oit_targets* targets)
+{
+    const char* who = "mifx_oit_shade_blend_check";
+    MIFX_CHECK(create_check(width, height, 1u, who));
+    return shade_blend(nullptr, width, height, postfx_feature_flags, slice, opaque_depth, camera, attribs, ibl, shadows, targets, who);
 }
 
 // clear_layers, then update_layers of every slice: one launch where a fused kernel exists for the layer count and the fusion is on

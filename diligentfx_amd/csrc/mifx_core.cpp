@@ -252,6 +252,7 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("comm_stats", mifx_comm_stats);
     MIFX_SZ("oit_slice", mifx_oit_slice);
     MIFX_SZ("oit_targets", mifx_oit_targets);
+    MIFX_SZ("transparent_slice", mifx_transparent_slice);
 #undef MIFX_SZ
     return 0;
 }

@@ -432,6 +432,20 @@ struct mifx_chain
     mifx::Plane                         targets[4]; // normal, base colour, material, IBL
     mifx_image2d                        target_desc[4]{};
     hipEvent_t                          evShade = nullptr; // overlap 1, 2 with targets: SSAO on the side stream reads the normal target the shade writes
+    // mifx_chain_set_transparency: the transparent draws of the frame, blended into the colour and the BaseColor / Material / IBL targets inside the shade stage (chain_shade).
+    // Deep copies (descriptors and layers included), so that only the device planes are borrowed; `oit` is created or re-created per frame size and layer count
+    // (chain_prepare_resources).  The layers, the tail and the two planes of the unfused path exist once: they are written and consumed inside the shade stage, which is
+    // one stream in every overlap mode ("Transparency in the chain").
+    struct TransparentSlice
+    {
+        mifx_transparent_slice s{};
+        mifx_image2d           gbuffer_images[6]{}, layer_images[9]{}, alpha{};
+        mifx_pbr_layers        layers{};
+    };
+    std::vector<TransparentSlice> transparent; // empty = off
+    uint32_t                      oit_layer_count = 0;
+    mifx_oit*                     oit = nullptr;
+    mifx::Plane                   slice_radiance, slice_specular_ibl; // mifx_chain_set_transparency_fusion(0): a slice's shade, reused slice after slice
     // mifx_chain_set_selection: the jump flood + the selection composite in place of the composite (api_selection.cpp); the attribs and the
     // image descriptor are copies, the selection depth plane is borrowed
     bool                   has_selection = false;

@@ -4,6 +4,8 @@
 //     ApplyIBL :501-512 -> ResolveLighting :514), material fetch replaced by the G-buffer (contract: PBR/src/USD_Renderer.cpp:83-162),
 //     world position rebuilt from depth with InvProjectPosition (PostFX_Common.fxh:99-105).  84 B/px: base colour, normal, material
 //     (3 x 16 B) + depth (4 B) in, radiance + specular IBL (2 x 16 B) out; LUT and cube maps are cache-resident (<= 9 MB).
+// Also here, because it is the layered shade's body with the OIT colour pass behind it: oit_shade_blend_kernel, one transparent draw shaded and blended in one launch
+// (mifx_oit_shade.h; launcher launch_oit_shade_blend, mifx_oit_shade_launch.h; entry mifx_oit_shade_blend, api_oit.cpp).
 #include "mifx_host.h"
 #include "mifx_objects.h"
 #include <cmath>
@@ -14,6 +16,8 @@
 #include "mifx_effects.h"
 #include "mifx_tonemap.h"
 #include "mifx_formats.h"
+#include "mifx_oit_shade_launch.h"
+#include "mifx_oit_shade.h"
 
 namespace mifx
 {
@@ -360,6 +364,19 @@ __global__ __launch_bounds__(256) void pbr_shade_targets_kernel(Img baseColor, I
     st<v4>(tg.material, x, y, t.material);
     st<v4>(tg.ibl, x, y, t.ibl);
 }
+// one transparent draw, shaded and blended (mifx_oit_shade.h: oit_px_shade_blend): the layered body with the set as a run-time mask -- a draw carries any set -- and the
+// colour pass of the layered OIT behind it, the shade's two results in registers.  Launched over the frame; the mip pointers are staged before the per-pixel return (a
+// block-wide step); a pixel without a fragment reads two floats and leaves.  Not in the native-storage build (mifx_oit_shade_blend returns MIFX_ERR_NOT_IMPLEMENTED there).
+template <bool SHADOWS>
+__global__ __launch_bounds__(256) void oit_shade_blend_kernel(OitShadeSliceK slice, LutK lut, CubeK irradiance, CubeK prefiltered, CamK cam, ShadeK k, LayersK ly, ShadowK sh, OitK oit,
+                                                              OitTargetsK tg)
+{
+    __shared__ const v4* prefMips[12];
+    stage_cube_mips(prefMips, prefiltered);
+    const int x = int(blockIdx.x * blockDim.x + threadIdx.x), y = int(blockIdx.y * blockDim.y + threadIdx.y);
+    if (x >= oit.w || y >= oit.h) return;
+    oit_px_shade_blend<true, SHADOWS>(oit, slice, tg, lut, irradiance.mip[0], irradiance.size, prefMips, prefiltered.size, prefiltered.mips, cam, k, ly, sh, x, y);
+}
 #endif
 
 static mifx_status make_cubek(const mifx_cubemap* c, const char* what, CubeK& k)
@@ -389,8 +406,9 @@ mifx_status make_lutk(const mifx_image2d* im, LutK& k)
 }
 
 // what both shade launchers share: the IBL look-ups (with their per-call apron copies) and the constant block
+// (checkOnly: the argument checks and the constant block alone -- no device call, the cubes stay the caller's)
 static mifx_status make_shade_constants(hipStream_t s, IblApronCache& cache, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], LutK& lut, CubeK& irr,
-                                        CubeK& pre, ShadeK& k)
+                                        CubeK& pre, ShadeK& k, bool checkOnly = false)
 {
     MIFX_REQUIRE(ibl != nullptr, "ibl must not be null");
     MIFX_REQUIRE(a.Workflow == MIFX_PBR_WORKFLOW_METALLIC_ROUGHNESS || a.Workflow == MIFX_PBR_WORKFLOW_SPECULAR_GLOSSINESS, "unknown PBR workflow %d", a.Workflow);
@@ -403,6 +421,7 @@ static mifx_status make_shade_constants(hipStream_t s, IblApronCache& cache, con
     k.workflow   = a.Workflow;
     for (int i = 0; i < a.LightCount; ++i) k.lights[i] = a.Lights[i];
     for (int i = 0; i < 4; ++i) k.background[i] = background ? background[i] : 0.0f;
+    if (checkOnly) return MIFX_OK;
     // working copies with face aprons (8.3 MB for a 256^2 prefiltered cube: ~10 us per call, repaid many times over in the shade kernel)
     const size_t irrBytes = apron_bytes(irr.size, 1), preBytes = apron_bytes(pre.size, pre.mips);
     DeviceScratch& iblApron = cache.scratch;
@@ -529,18 +548,28 @@ static mifx_status make_lutk_r(const mifx_image2d* im, const char* what, LutK& k
     return MIFX_OK;
 }
 // output != nullptr: the shade's output stage behind the layered body (launch_pbr_shade_output; `out_radiance` is then PSOut.Color), with the footer's four planes where
-// `targets` is given (`out_spec` is then null); both validated by the entries (api_pbr.cpp)
+// `targets` is given (`out_spec` is then null); both validated by the entries (api_pbr.cpp).
+// oit != nullptr: one transparent draw shaded and blended (launch_oit_shade_blend): `g` is the draw's G-buffer, the frame is the OIT object's, nothing is written but the
+// four targets (`out_radiance`, `out_spec` are null); checkOnly stops behind the last argument check, in front of the first device call
+struct OitShadeBlend
+{
+    const OitK&         k;
+    const OitTargetsK&  targets;
+    const mifx_image2d* colorAlpha;
+    bool                checkOnly;
+};
 static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
                                                 const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance,
                                                 const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows,
-                                                const LayeredHitFetch* hit, const mifx_pbr_shade_output_desc* output, const mifx_pbr_targets* targets)
+                                                const LayeredHitFetch* hit, const mifx_pbr_shade_output_desc* output, const mifx_pbr_targets* targets,
+                                                const OitShadeBlend* oit = nullptr)
 {
     const uint32_t known = MIFX_PBR_LAYER_CLEAR_COAT | MIFX_PBR_LAYER_SHEEN | MIFX_PBR_LAYER_ANISOTROPY | MIFX_PBR_LAYER_IRIDESCENCE | MIFX_PBR_LAYER_TRANSMISSION;
     MIFX_REQUIRE((layers.flags & ~known) == 0u, "layers: unknown flag bits 0x%x", layers.flags & ~known);
     Img bc, nrm, mat, depth, emis{}, occ{}, outR, outS{};
-    MIFX_CHECK(to_img(out_radiance, MIFX_FORMAT_F32X4, "out_radiance", outR)); // (hit fetch: the plane the band's rows were shaded into)
-    if (hit == nullptr) outR = rows_of(outR, row_begin, row_end);
-    const uint32_t W = out_radiance->width, H = out_radiance->height;
+    if (oit == nullptr) MIFX_CHECK(to_img(out_radiance, MIFX_FORMAT_F32X4, "out_radiance", outR)); // (hit fetch: the plane the band's rows were shaded into)
+    if (hit == nullptr && oit == nullptr) outR = rows_of(outR, row_begin, row_end);
+    const uint32_t W = oit ? uint32_t(oit->k.w) : out_radiance->width, H = oit ? uint32_t(oit->k.h) : out_radiance->height;
     if (hit != nullptr) MIFX_REQUIRE(W <= 65536u && H <= 65536u, "launch_pbr_shade_layers: frame %ux%u exceeds the 16-bit hit coordinates", W, H);
     MIFX_CHECK(bind_gbuffer(g, out_spec, W, H, bc, nrm, mat, depth, emis, occ, outS));
     MIFX_CHECK(check_lights(a, shadows, "`shadows`"));
@@ -578,10 +607,23 @@ static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& ib
     LutK lut;
     CubeK irr, pre;
     ShadeK k{};
-    MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k));
+    Img alpha{};
+    if (oit != nullptr && oit->colorAlpha != nullptr) MIFX_CHECK(to_img_wh(oit->colorAlpha, MIFX_FORMAT_F32, W, H, "slice color_alpha", alpha));
+    MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k, oit != nullptr && oit->checkOnly));
+    if (oit != nullptr && oit->checkOnly) return MIFX_OK;
     const CamK cam = make_camk(camera, reversedDepth);
     const dim3 block(64, 4, 1);
-    if (output != nullptr)
+    if (oit != nullptr)
+    {
+#ifndef MIFX_STORAGE_H4
+        const OitShadeSliceK slice{bc, nrm, mat, depth, emis, occ, alpha, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, oit->colorAlpha ? 1 : 0};
+        hipLaunchKernelGGL(shadows ? oit_shade_blend_kernel<true> : oit_shade_blend_kernel<false>, grid2d(int(W), int(H), block), block, 0, s, slice, lut, irr, pre, cam, k, ly, sh, oit->k,
+                           oit->targets);
+#else
+        MIFX_REQUIRE(false, "mifx_oit_shade_blend: not part of the native-storage build");
+#endif
+    }
+    else if (output != nullptr)
     {
 #ifndef MIFX_STORAGE_H4
         Img motion{}, meshNormal{};
@@ -669,6 +711,18 @@ mifx_status launch_pbr_shade_output(hipStream_t s, IblApronCache& iblApron, cons
     const mifx_pbr_layers none{};
     return launch_pbr_shade_layers_impl(s, iblApron, g, layers ? *layers : none, camera, a, ibl, background, out_color, out_spec, row_begin, row_end, reversedDepth, shadows, nullptr, &output, targets);
 }
+
+mifx_status launch_oit_shade_blend(hipStream_t s, IblApronCache& iblApron, const OitK& k, const OitTargetsK& targets, const mifx_gbuffer* g, const mifx_pbr_layers* layers,
+                                   const mifx_image2d* color_alpha, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, bool reversedDepth,
+                                   const mifx_pbr_shadows* shadows, bool check_only)
+{
+    const mifx_pbr_layers none{};
+    const OitShadeBlend   oit{k, targets, color_alpha, check_only};
+    return launch_pbr_shade_layers_impl(s, iblApron, g, layers ? *layers : none, camera, a, ibl, nullptr, nullptr, nullptr, 0, 0, reversedDepth, shadows, nullptr, nullptr, nullptr, &oit);
+}
+
+// (mifx_oit_shade_launch.h: how api_oit.cpp finds the launcher)
+static decltype(&launch_oit_shade_blend) g_launch_oit_shade_blend_installed = g_launch_oit_shade_blend = &launch_oit_shade_blend;
 
 mifx_status launch_pbr_hit_fetch(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                                  const float background[4], Img rays, Img hitCoords, const mifx_image2d* radiance, int shadedBegin, int shadedEnd, bool reversedDepth)

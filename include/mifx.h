@@ -1140,6 +1140,29 @@ MIFX_API int32_t mifx_oit_set_fusion(int32_t enable);
 MIFX_API mifx_status mifx_oit_create_check(uint32_t width, uint32_t height, uint32_t layer_count);
 MIFX_API mifx_status mifx_oit_frame_check(uint32_t width, uint32_t height, const mifx_oit_slice* slices, uint32_t count, const mifx_image2d* opaque_depth,
                                           const mifx_camera_attribs* camera, const mifx_oit_targets* targets);
+/* One transparent draw, shaded and blended in one launch ("oit_shade_blend_kernel"), as the reference's transparent draw is one pixel shader: RenderPBR.psh `main`
+ * shades, multiplies by BaseColor.a (:547) and the transmittance (:632), and the blend state does the rest.  The slice is the draw's own G-buffer, not shaded planes. */
+typedef struct mifx_transparent_slice
+{
+    mifx_gbuffer           gbuffer;     /* the draw's own G-buffer; depth holds the background value where the draw has no fragment */
+    const mifx_pbr_layers* layers;      /* or NULL = the empty set */
+    const mifx_image2d*    color_alpha; /* F32 or NULL, as mifx_oit_slice::color_alpha */
+} mifx_transparent_slice;
+/* The result equals mifx_pbr_shade_execute_layers on the slice (background 0, both outputs) followed by mifx_oit_blend of {gbuffer.depth, .base_color, .material, the
+ * two shaded planes, color_alpha}, bit for bit: the kernel runs the two existing bodies one behind the other with the shade's results in registers, touches only pixels
+ * where the draw has a fragment (any other reads its depth and the opaque depth and writes nothing) and needs no intermediate planes.  The layers persist as for
+ * mifx_oit_blend: the caller has run mifx_oit_build_layers (or clear_layers / update_layers) and mifx_oit_apply_attenuation.  `shadows` may be NULL; lights with a
+ * ShadowMapIndex >= 0 need it.  Every plane is of the object's size.
+ * Reversed depth is read twice -- by the OIT from the camera (fNearPlaneDepth > fFarPlaneDepth), by the shade from the context's
+ * MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH: a call where the two disagree is refused (MIFX_ERR_INVALID_ARG).
+ * Native-storage build: MIFX_ERR_NOT_IMPLEMENTED. */
+MIFX_API mifx_status mifx_oit_shade_blend(mifx_oit* oit, const mifx_transparent_slice* slice, const mifx_image2d* opaque_depth, const mifx_camera_attribs* camera,
+                                          const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows /* or NULL */, const mifx_oit_targets* targets);
+/* Its argument checks alone, for an object of width x height on a context created with `postfx_feature_flags` -- no context, no device, nothing read but the
+ * descriptors, the camera and the attribs. */
+MIFX_API mifx_status mifx_oit_shade_blend_check(uint32_t width, uint32_t height, uint32_t postfx_feature_flags, const mifx_transparent_slice* slice, const mifx_image2d* opaque_depth,
+                                                const mifx_camera_attribs* camera, const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows,
+                                                const mifx_oit_targets* targets);
 
 /* ------------------------------------------------------------------------------------------------ whole chain (the caller: HnPostProcessTask::Execute, Hydrogent/src/Tasks/HnPostProcessTask.cpp:743-948) */
 typedef struct mifx_autoexposure mifx_autoexposure; /* auto exposure, declared below */
@@ -1171,7 +1194,8 @@ MIFX_API void        mifx_chain_destroy(mifx_chain* chain);
 MIFX_API mifx_status mifx_chain_execute(mifx_chain* chain, const mifx_chain_frame* frame, const mifx_image2d* out_ldr);
 MIFX_API mifx_status mifx_chain_get_postfx(mifx_chain* chain, mifx_postfx** out);
 /* the effect objects the chain owns, by name: "ssao" (mifx_ssao*), "ssr" (mifx_ssr*), "taa" (mifx_taa*), "bloom" (mifx_bloom*), "dof" (mifx_dof*, NULL while off),
- * "selection" (mifx_selection*, NULL until mifx_chain_set_selection turned it on) -- for their outputs and intermediates */
+ * "selection" (mifx_selection*, NULL until mifx_chain_set_selection turned it on), "oit" (mifx_oit*, NULL until a frame ran with mifx_chain_set_transparency on) -- for
+ * their outputs and intermediates */
 MIFX_API mifx_status mifx_chain_get_effect(mifx_chain* chain, const char* name, void** out);
 /* mifx_chain_execute with the final image in the copy-frame target's own format (e.g. MIFX_NATIVE_FORMAT_RGBA8_UNORM_SRGB), see mifx_tonemap_execute_native.
  * Not available with a row band, together with mifx_chain_set_auto_exposure or with mifx_chain_set_coordinate_grid (MIFX_ERR_INVALID_ARG). */
@@ -1212,6 +1236,22 @@ MIFX_API mifx_status mifx_chain_set_material_layers(mifx_chain* chain, const mif
 MIFX_API mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_output_desc* output /* may be NULL */, int32_t write_targets);
 /* One of the chain's four target planes ("normal", "base_color", "material", "ibl") as the frame executed last wrote it: a view, valid until the next execute or prepare. */
 MIFX_API mifx_status mifx_chain_get_shade_target(mifx_chain* chain, const char* name, mifx_image2d* out);
+/* Transparent draws in the chain (off by default): Hydrogent's frame is the opaque pass, HnBeginOITPassTask, the transparent draws, HnEndOITPassTask, HnPostProcessTask;
+ * with this call the chain runs the three middle steps inside its shade stage, directly behind mifx_pbr_shade_targets and on the same stream: mifx_oit_build_layers over
+ * the slices (opaque depth = frame.gbuffer.depth), mifx_oit_apply_attenuation on {the shaded colour, BaseColor, Material, IBL} -- the four planes HnEndOITPassTask.cpp:68-79
+ * blends into; the Normal target is not blended -- and one mifx_oit_shade_blend per slice in submission order, with the frame's pbr, ibl and camera and the chain's shadow
+ * maps.  Everything behind the shade (SSR's R2 and march, SSAO, the composite, which scales SSR and SSAO by the colour's opacity) reads the blended planes, in every
+ * overlap mode.  The slice structs, their layers and every image descriptor are copied; the device planes are borrowed for every frame until the next call.
+ * count == 0 or slices == NULL: off -- the chain launches exactly what it launches without the call.  The OIT object (created or re-created per frame size and
+ * layer_count) is mifx_chain_get_effect(chain, "oit") (NULL until a frame ran with transparency on).
+ * Refused (MIFX_ERR_INVALID_ARG): transparency without mifx_chain_set_shade_output(..., write_targets != 0) -- without it base colour and material are the caller's const
+ * planes -- in whichever order the two calls come; a row band or sharding, in either order (through the shade output, which is not combined with either); count > MIFX_OIT_MAX_SLICES; layer_count outside 1 .. MIFX_OIT_MAX_LAYERS; at
+ * execute time, a slice whose planes are not of the frame's size, and what mifx_oit_shade_blend refuses.  Native-storage build: MIFX_ERR_NOT_IMPLEMENTED. */
+MIFX_API mifx_status mifx_chain_set_transparency(mifx_chain* chain, uint32_t layer_count, const mifx_transparent_slice* slices, uint32_t count);
+/* Internal A/B switch of the chain's transparent draws: 1 = one mifx_oit_shade_blend per slice, 0 = per slice mifx_pbr_shade_execute_layers into two planes the chain owns
+ * (reused slice after slice), then mifx_oit_blend -- the yardstick, bit-identical by mifx_oit_shade_blend's contract.  Returns the previous value.  The default and the
+ * measurement behind it: DESIGN.md section 4, "Transparency in the chain". */
+MIFX_API int32_t     mifx_chain_set_transparency_fusion(int32_t enable);
 /* Selection highlighting in the chain (off by default): every frame executed from now on runs the jump flood of mifx_selection_execute on `selection_depth` and the
  * composite with the selection tail (mifx_composite_execute_selection).  The attribs are copied, the image descriptor too; the device plane is borrowed for every frame
  * until the next call (like the G-buffer: whole on every rank of a row band, so a band needs no exchange for it).  TAA follows, so with a tone mapping mode other than NONE

@@ -1,0 +1,406 @@
+"""One transparent draw shaded and blended (mifx_oit_shade_blend) without a GPU: the kernel's per-pixel body (diligentfx_amd/csrc/mifx_oit_shade.h) compiled for the host
+and run on the end-to-end case of tests/oit_util.py (24x16, two slices, K = 4) against the composition of the two existing host compilations -- layers_host.cpp shades
+each slice, oit_host.cpp runs the sequence on the shaded planes -- bit for bit, and against the reference's targets of tests/golden/oit_golden.npz by the project's
+contract (util.assert_close at its defaults, no outlier: the rule tests/test_gpu_oit.py::test_end_to_end_shade_two_slices_then_render uses for this fixture); the
+refusals of mifx_oit_shade_blend_check, one test each; and the same host source as a stand-alone program under the address and undefined-behaviour sanitizers."""
+import ctypes
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import oit_util as O
+import test_oit_cpu as C
+from util import assert_close
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "diligentfx_amd", "csrc")
+F = np.float32
+
+
+class HostPlane(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("w", ctypes.c_int), ("h", ctypes.c_int), ("c", ctypes.c_int)]
+
+
+class HostPitched(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_int)]
+
+
+class HostTSlice(ctypes.Structure):
+    _fields_ = [(k, HostPitched) for k in ("base", "normal", "material", "depth", "alpha")]
+
+
+def plane(a):
+    assert a.dtype == np.float32 and a.flags.c_contiguous
+    return HostPlane(a.ctypes.data, a.shape[1], a.shape[0], a.shape[2] if a.ndim == 3 else 1)
+
+
+def pitched(a):
+    if a is None:
+        return HostPitched(None, 0)
+    assert a.dtype == np.float32 and a.flags.c_contiguous
+    return HostPitched(a.ctypes.data, a.strides[0])
+
+
+def _hipcc():
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    return hipcc
+
+
+def _host_so(name, headers, extra=()):
+    hipcc = _hipcc()
+    src = os.path.join(HERE, "host_kernels", name + ".cpp")
+    out_dir = os.path.join(HERE, "host_kernels", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    out = os.path.join(out_dir, name + ".so")
+    deps = [src, os.path.join(ROOT, "include", "mifx.h")] + [os.path.join(CSRC, n) for n in headers]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", *extra, "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", out, src]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-4000:]
+    return ctypes.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def world():
+    """The end-to-end case, its IBL and shade attribs, and the three host libraries"""
+    import chain_util
+    from layers_util import ref_checker
+
+    ibl_np = chain_util.make_ibl(ref_checker(), "ref_")
+    return dict(e=O.e2e_inputs(), ibl=ibl_np, sa=chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1),
+                fused=_host_so("shade_blend_host", ("mifx_oit_shade.h", "mifx_oit.h", "mifx_pbr_layers.h", "mifx_pbr.h", "mifx_device.h")),
+                layers=_host_so("layers_host", ("mifx_pbr_layers.h", "mifx_pbr.h", "mifx_device.h"), extra=("-fopenmp",)), oit=C.build_host_lib(_hipcc()))
+
+
+def _ibl_args(ibl_np):
+    lut, irr = plane(ibl_np["lut"]), plane(ibl_np["irradiance"][0])
+    pre = (HostPlane * len(ibl_np["prefiltered"]))(*[plane(m) for m in ibl_np["prefiltered"]])
+    return lut, irr, pre
+
+
+def fused_on_host(w):
+    """(layers, tail, targets) of the shade-and-blend body inside its frame"""
+    e, wd, ht, k = w["e"], O.E2E["w"], O.E2E["h"], O.E2E["k"]
+    gbs = [{n: np.ascontiguousarray(v) for n, v in gb.items()} for gb in e["gbuffers"]]
+    S = (HostTSlice * len(gbs))(*[HostTSlice(pitched(g["base_color"]), pitched(g["normal"]), pitched(g["material"]), pitched(g["depth"]), pitched(None)) for g in gbs])
+    targets = np.ascontiguousarray(e["targets"]).copy()
+    T = (HostPitched * 4)(*[pitched(targets[j]) for j in range(4)])
+    layers, tail = np.full((ht, wd, k), 0xDEADBEEF, np.uint32), np.full((ht, wd, 2), -7.0, F)
+    lut, irr, pre = _ibl_args(w["ibl"])
+    rc = w["fused"].mifx_host_transparency(k, wd, ht, len(gbs), S, pitched(None), ctypes.byref(lut), ctypes.byref(irr), pre, len(w["ibl"]["prefiltered"]), bytes(e["camera"]),
+                                           bytes(w["sa"]), 0, layers.ctypes.data_as(ctypes.c_void_p), tail.ctypes.data_as(ctypes.c_void_p), T)
+    assert rc == 0
+    return layers, tail, targets
+
+
+def composed_on_host(w):
+    """The same frame by the two existing bodies: the layered shade's host compilation (the empty set, background 0) per slice, then the OIT sequence's"""
+    e, wd, ht, k = w["e"], O.E2E["w"], O.E2E["h"], O.E2E["k"]
+    lut, irr, pre = _ibl_args(w["ibl"])
+    none = HostPlane(None, 0, 0, 0)
+    rads, specs = [], []
+    for gb in e["gbuffers"]:
+        g = {n: np.ascontiguousarray(v) for n, v in gb.items()}
+        rad, spec = np.zeros((ht, wd, 4), F), np.zeros((ht, wd, 4), F)
+        P = (HostPlane * 8)(plane(g["base_color"]), plane(g["normal"]), plane(g["material"]), plane(g["depth"]), none, none, plane(rad), plane(spec))
+        L = (HostPlane * 7)(*[none] * 7)
+        U = (HostPlane * 3)(lut, none, none)
+        rc = w["layers"].mifx_host_pbr_shade_layers(P, L, U, ctypes.byref(irr), pre, len(w["ibl"]["prefiltered"]), bytes(e["camera"]), bytes(w["sa"]), (ctypes.c_float * 4)(0, 0, 0, 0), 0,
+                                                    ctypes.c_float(1.3), ctypes.c_float(0.0), 0, None, 0, None, 0, 0, 1)
+        assert rc == 0
+        rads.append(rad)
+        specs.append(spec)
+    d = dict(depth=np.stack([g["depth"] for g in e["gbuffers"]]), base=np.stack([g["base_color"] for g in e["gbuffers"]]), material=np.stack([g["material"] for g in e["gbuffers"]]),
+             radiance=np.stack(rads), ibl=np.stack(specs), alpha=None, opaque=None, targets=e["targets"], camera=np.frombuffer(bytes(e["camera"]), F).copy())
+    rc, layers, tail, targets = C.host_run(w["oit"], dict(w=wd, h=ht, k=k, l=len(rads)), d, fused=False)
+    assert rc == 0
+    return layers, tail, targets
+
+
+def test_the_body_on_the_host_equals_the_composition_of_the_two_existing_bodies_bit_for_bit(world):
+    fl, ft, fg = fused_on_host(world)
+    cl, ct, cg = composed_on_host(world)
+    print(f"{int((fl != cl).sum())} layer words, {int((ft.view(np.uint32) != ct.view(np.uint32)).sum())} tail values, "
+          f"{int((fg.view(np.uint32) != cg.view(np.uint32)).sum())} of {cg.size} target values differ in their bits")
+    assert (fg != world["e"]["targets"]).any(-1).mean() > 0.5  # most texels are covered by a slice
+    assert np.array_equal(fl, cl) and C.same_bits(ft, ct) and C.same_bits(fg, cg)
+
+
+def test_the_body_on_the_host_meets_the_references_end_to_end_targets(world):
+    g = C.golden()
+    layers, tail, targets = fused_on_host(world)
+    assert np.array_equal(layers, g["e2e_layers"]) and np.array_equal(tail[..., 0], g["e2e_tail"][..., 0])
+    for j, k in enumerate(("color", "base_color", "material", "ibl")):
+        print(f"target {k}: max |diff| {np.abs(targets[j] - g['e2e_targets'][j]).max():.3e}")
+        assert_close(targets[j], g["e2e_targets"][j], what=f"shade-and-blend on the host, end to end: target {k}")
+
+
+# ------------------------------------------------------------------------------------------------ mifx_oit_shade_blend_check: one test per refusal
+W, H = 8, 4
+
+
+class Args:
+    """A call of the check entry that is accepted; a test changes one thing"""
+
+    def __init__(self):
+        from diligentfx_amd import binding as B
+
+        self.B, self.keep = B, []
+        f1 = lambda w=W, h=H: B.Image2D(0x1000, w, h, w * 4, B.FORMAT_F32)  # noqa: E731
+        f4 = lambda w=W, h=H: B.Image2D(0x2000, w, h, w * 16, B.FORMAT_F32X4)  # noqa: E731
+        self.f1, self.f4 = f1, f4
+        self.gbuffer = dict(base_color=f4(), normal=f4(), material=f4(), depth=f1(), emissive=None, occlusion=None)
+        self.layers, self.alpha, self.opaque = None, None, f1()
+        self.targets = dict(color=f4(), base_color=f4(), material=f4(), ibl=f4())
+        self.camera = B.CameraAttribs()
+        self.camera.fNearPlaneDepth, self.camera.fFarPlaneDepth = 0.0, 1.0
+        self.attribs = B.PBRShadeAttribs()
+        self.attribs.Workflow = 0
+        self.lut = B.Image2D(0x3000, 16, 16, 16 * 8, B.FORMAT_F32X2)
+        self.irr, self.pre = B.Cubemap(), B.Cubemap()
+        self.irr.size, self.irr.mip_count, self.pre.size, self.pre.mip_count = 8, 1, 8, 4
+        self.shadows, self.flags, self.w, self.h = None, 0, W, H
+
+    def p(self, x):
+        if x is None:
+            return None
+        self.keep.append(x)
+        return ctypes.pointer(x)
+
+    def call(self, lib):
+        B = self.B
+        g = B.GBuffer(*[self.p(self.gbuffer[k]) for k in ("base_color", "normal", "material", "depth", "emissive", "occlusion")])
+        s = B.TransparentSlice(g, self.p(self.layers), self.p(self.alpha))
+        t = B.OITTargets(*[self.p(self.targets[k]) for k in ("color", "base_color", "material", "ibl")])
+        ibl = B.IBL(self.p(self.lut), self.p(self.irr), self.p(self.pre))
+        rc = lib.mifx_oit_shade_blend_check(self.w, self.h, self.flags, ctypes.byref(s), self.p(self.opaque), self.p(self.camera), self.p(self.attribs), ctypes.byref(ibl),
+                                            self.p(self.shadows), ctypes.byref(t))
+        return rc, lib.mifx_last_error().decode()
+
+
+def _native(mifx_lib):
+    return bool(mifx_lib.mifx_storage_mode())
+
+
+@pytest.fixture
+def args(mifx_lib):
+    if _native(mifx_lib):
+        pytest.skip("the native-storage build returns MIFX_ERR_NOT_IMPLEMENTED for this entry")
+    a = Args()
+    for m in range(4):
+        a.pre.mip_data[m] = 0x8000 + 0x1000 * m
+    a.irr.mip_data[0] = 0x4000
+    rc, err = a.call(mifx_lib)
+    assert rc == 0, err  # what is asked for is accepted
+    return a
+
+
+def test_struct_layout(mifx_lib):
+    from diligentfx_amd import binding as B
+
+    assert ctypes.sizeof(B.TransparentSlice) == 64 == mifx_lib.mifx_sizeof(b"transparent_slice")
+
+
+def test_accepted_with_every_optional_plane(mifx_lib, args):
+    args.alpha, args.gbuffer["emissive"], args.gbuffer["occlusion"] = args.f1(), args.f4(), args.f1()
+    rc, err = args.call(mifx_lib)
+    assert rc == 0, err
+    args.opaque = None
+    assert args.call(mifx_lib)[0] == 0
+
+
+@pytest.mark.parametrize("plane_", ["base_color", "normal", "material", "depth"])
+def test_refuses_a_null_gbuffer_plane(mifx_lib, args, plane_):
+    args.gbuffer[plane_] = None
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "null" in err and plane_ in err
+
+
+@pytest.mark.parametrize("plane_", ["base_color", "normal", "material", "depth", "emissive", "occlusion"])
+def test_refuses_a_gbuffer_plane_of_another_size(mifx_lib, args, plane_):
+    args.gbuffer[plane_] = args.f1(w=W + 1) if plane_ in ("depth", "occlusion") else args.f4(h=H - 1)
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "size" in err and plane_ in err
+
+
+def test_refuses_a_gbuffer_plane_of_another_format(mifx_lib, args):
+    args.gbuffer["normal"] = args.f1()
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "format" in err
+
+
+def test_refuses_a_color_alpha_of_another_size_or_format(mifx_lib, args):
+    args.alpha = args.f1(w=W - 1)
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "color_alpha" in err and "size" in err
+    args.alpha = args.f4()
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "color_alpha" in err and "format" in err
+
+
+def test_refuses_an_opaque_depth_of_another_size(mifx_lib, args):
+    args.opaque = args.f1(h=H + 1)
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "opaque_depth" in err
+
+
+@pytest.mark.parametrize("target", ["color", "base_color", "material", "ibl"])
+def test_refuses_a_null_or_missized_target(mifx_lib, args, target):
+    keep = args.targets[target]
+    args.targets[target] = None
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "null" in err
+    args.targets[target] = args.f4(w=2 * W)
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "target" in err and "size" in err
+    args.targets[target] = keep
+    assert args.call(mifx_lib)[0] == 0
+
+
+def test_refuses_planes_that_are_not_the_objects_size(mifx_lib, args):
+    args.w = W + 1
+    assert args.call(mifx_lib)[0] == -1
+    args.w, args.h = W, 0
+    assert args.call(mifx_lib)[0] == -1
+
+
+def test_refuses_null_arguments(mifx_lib, args):
+    B = args.B
+    t = B.OITTargets()
+    s = B.TransparentSlice()
+    assert mifx_lib.mifx_oit_shade_blend_check(W, H, 0, None, None, ctypes.byref(args.camera), ctypes.byref(args.attribs), None, None, ctypes.byref(t)) == -1
+    assert mifx_lib.mifx_oit_shade_blend_check(W, H, 0, ctypes.byref(s), None, None, None, None, None, None) == -1
+    assert mifx_lib.mifx_oit_shade_blend(None, ctypes.byref(s), None, ctypes.byref(args.camera), ctypes.byref(args.attribs), None, None, ctypes.byref(t)) == -1
+
+
+def test_refuses_reversed_depth_that_disagrees(mifx_lib, args):
+    """The OIT reads it from the camera, the shade from the context's flag: either alone is refused, both together are accepted"""
+    args.camera.fNearPlaneDepth, args.camera.fFarPlaneDepth = 1.0, 0.0
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "reversed depth disagrees" in err and "MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH" in err
+    args.flags = 1
+    rc, err = args.call(mifx_lib)
+    assert rc == 0, err
+    args.camera.fNearPlaneDepth, args.camera.fFarPlaneDepth = 0.0, 1.0
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "reversed depth disagrees" in err
+
+
+def test_refuses_unknown_layer_flags_and_a_missing_layer_plane(mifx_lib, args):
+    B = args.B
+    args.layers = B.PBRLayers()
+    args.layers.flags = 1 << 9
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "unknown flag bits" in err
+    args.layers.flags = B.PBR_LAYER_CLEAR_COAT  # the clear-coat plane is missing
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "clearcoat" in err
+    cc = args.f4(w=W + 2)
+    args.layers.clearcoat = ctypes.pointer(cc)
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "clearcoat" in err and "size" in err
+
+
+def test_refuses_bad_lights(mifx_lib, args):
+    args.attribs.LightCount = 99
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "LightCount" in err
+    args.attribs.LightCount = 1
+    args.attribs.Lights[0].Type = 1
+    args.attribs.Lights[0].ShadowMapIndex = 0  # a shadow-mapped light without `shadows`
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "ShadowMapIndex" in err
+
+
+def test_refuses_a_bad_ibl_or_workflow(mifx_lib, args):
+    args.pre.mip_count = 0
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "prefiltered" in err
+    args.pre.mip_count = 4
+    args.attribs.Workflow = 7
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "workflow" in err
+
+
+def test_native_storage_build_has_the_symbols():
+    """libmifx_h4.so exports the entries (they return MIFX_ERR_NOT_IMPLEMENTED there: the build is out of scope)"""
+    from diligentfx_amd import build
+
+    if not os.path.exists(build.OUT_H4):
+        pytest.skip("libmifx_h4.so is not built")
+    lib = ctypes.CDLL(build.OUT_H4)
+    for name in ("mifx_oit_shade_blend", "mifx_oit_shade_blend_check", "mifx_chain_set_transparency", "mifx_chain_set_transparency_fusion"):
+        assert hasattr(lib, name), name
+    from diligentfx_amd import binding as B
+
+    a = Args()
+    g = B.GBuffer()
+    s, t, ibl = B.TransparentSlice(g, None, None), B.OITTargets(), B.IBL()
+    lib.mifx_status_string.restype = ctypes.c_char_p
+    rc = lib.mifx_oit_shade_blend_check(W, H, 0, ctypes.byref(s), None, ctypes.byref(a.camera), ctypes.byref(a.attribs), ctypes.byref(ibl), None, ctypes.byref(t))
+    assert b"NOT_IMPLEMENTED" in lib.mifx_status_string(rc).upper().replace(b" ", b"_"), (rc, lib.mifx_status_string(rc))
+
+
+def test_the_host_only_build_refuses_the_entry_by_the_launchers_name():
+    """tests/cpu_product links the product's host sources without the device objects: its launcher stand-ins are those of mifx_host.h / mifx_*_host.h, which this launcher
+    is not part of, so nothing installs it (csrc/mifx_oit_shade_launch.h) and the entry answers MIFX_ERR_NOT_IMPLEMENTED with launch_oit_shade_blend in the message --
+    after its own argument checks, which still run.  (A process of its own: the build carries a stand-in for the HIP runtime.)"""
+    import importlib.util
+    import sys
+
+    spec = importlib.util.spec_from_file_location("_cpu_product_build", os.path.join(HERE, "cpu_product", "build.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    lib = m.build()
+    if lib is None:
+        pytest.skip("hipcc not available")
+    code = (
+        "import ctypes, sys\n"
+        "sys.path[:0] = [%r, %r]\n"
+        "import test_shade_blend_cpu as T\n"
+        "lib = ctypes.CDLL(%r)\n"
+        "lib.mifx_last_error.restype = ctypes.c_char_p\n"
+        "lib.mifx_status_string.restype = ctypes.c_char_p\n"
+        "a = T.Args()\n"
+        "a.camera.fNearPlaneDepth, a.camera.fFarPlaneDepth = 1.0, 0.0\n"
+        "rc, err = a.call(lib)\n"
+        "assert rc == -1 and 'reversed depth disagrees' in err, (rc, err)\n"
+        "a.flags = 1\n"
+        "rc, err = a.call(lib)\n"
+        "print(rc, lib.mifx_status_string(rc).decode(), '|', err)\n" % (ROOT, HERE, lib))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert "launch_oit_shade_blend" in r.stdout and "NOT_IMPLEMENTED" in r.stdout.upper().replace(" ", "_"), r.stdout
+
+
+def test_the_library_has_the_launcher_installed(mifx_lib, args):
+    """... and libmifx.so has it: the accepted call of the `args` fixture went through the launcher's own checks (a bad IBL is refused by them, not by a missing launcher)"""
+    args.pre.mip_count = 0
+    rc, err = args.call(mifx_lib)
+    assert rc == -1 and "prefiltered" in err and "launch_oit_shade_blend" not in err
+
+
+# ------------------------------------------------------------------------------------------------ the same source under the sanitizers, as a program of its own
+def test_body_source_under_the_address_and_undefined_behaviour_sanitizers(tmp_path):
+    """The host compilation of the body and a stand-alone program around it (tests/host_kernels/shade_blend_sanitize_main.cpp), both built for the host alone with the address
+    and undefined-behaviour sanitizers (host-side flags only: no device code is built or run), run once as a process of its own over 5x3 and 67x35 frames on pitched planes
+    whose allocations end with their last texel: no report, exit status 0, the row padding untouched"""
+    hipcc = _hipcc()
+    exe = str(tmp_path / "shade_blend_sanitize")
+    hk = os.path.join(HERE, "host_kernels")
+    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
+           "-fno-sanitize-recover=undefined", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(hk, "shade_blend_host.cpp"),
+           os.path.join(hk, "shade_blend_sanitize_main.cpp")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env={**os.environ, "ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0"})
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 4 and "nan" not in r.stdout and "inf" not in r.stdout, r.stdout
+    assert lines[0].startswith("5x3") and lines[2].startswith("67x35")
