@@ -2,16 +2,12 @@
 // kernels, whose launchers are in oit.hip (mifx_oit_host.h), and of mifx_oit_shade_blend, one transparent draw shaded and blended by one kernel of pbr.hip.
 #include "mifx_objects.h"
 #include "mifx_oit_host.h"
-#include "mifx_oit_shade_launch.h"
 
 using namespace mifx;
 
 // The fused kernels are the default: 2.0 - 3.3 times faster than the sequence at 3840 x 2160, K = 4, L = 2 .. 8, both shapes at the device's copy rate for the bytes
 // they move (profiles/oit_bench.json, tools/oit_bench.py; mifx_oit_set_fusion(0) is the sequence).
 static bool g_oit_fusion = true;
-
-// installed by pbr.hip when the library is loaded (mifx_oit_shade_launch.h); a build without the device code leaves it null
-decltype(&mifx::launch_oit_shade_blend) mifx::g_launch_oit_shade_blend = nullptr;
 
 namespace
 {
@@ -134,22 +130,17 @@ mifx_status shade_blend(mifx_oit* o, uint32_t w, uint32_t h, uint32_t postfx_fla
                  "%s: reversed depth disagrees: the camera says %s (fNearPlaneDepth %g, fFarPlaneDepth %g: what the OIT reads), the context's MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH "
                  "says %s (what the shade reads)",
                  who, f.cam.reversed ? "reversed" : "not reversed", double(camera->fNearPlaneDepth), double(camera->fFarPlaneDepth), shadeReversed ? "reversed" : "not reversed");
-    if (g_launch_oit_shade_blend == nullptr)
-    {
-        ::mifx::set_error("%s: launch_oit_shade_blend: this build of the library carries no device code for it", who);
-        return MIFX_ERR_NOT_IMPLEMENTED;
-    }
     if (o == nullptr)
     {
         OitK k{};
         k.w = int(w); k.h = int(h); k.cam = f.cam;
         IblApronCache none;
-        return g_launch_oit_shade_blend(nullptr, none, k, f.targets, &slice->gbuffer, slice->layers, slice->color_alpha, *camera, *attribs, ibl, shadeReversed, shadows, true);
+        return launch_oit_shade_blend(nullptr, none, k, f.targets, &slice->gbuffer, slice->layers, slice->color_alpha, *camera, *attribs, ibl, shadeReversed, shadows, true);
     }
     MIFX_HIP_CHECK(hipSetDevice(o->ctx->device));
     MifxKernelTimer timer(o->ctx, "oit_shade_blend_kernel"); // (includes the two cube-apron launches of the call, where the maps are not declared static)
-    return g_launch_oit_shade_blend(o->ctx->stream, o->ctx->ibl_apron, make_oitk(o, f), f.targets, &slice->gbuffer, slice->layers, slice->color_alpha, *camera, *attribs, ibl, shadeReversed,
-                                  shadows, false);
+    return launch_oit_shade_blend(o->ctx->stream, o->ctx->ibl_apron, make_oitk(o, f), f.targets, &slice->gbuffer, slice->layers, slice->color_alpha, *camera, *attribs, ibl, shadeReversed,
+                                shadows, false);
 #endif
 }
 } // namespace

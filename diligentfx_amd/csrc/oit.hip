@@ -1,5 +1,5 @@
 // oit.hip -- layered order-independent transparency over G-buffer slices (include/mifx.h "layered order-independent transparency"): the six kernels and their
-// launchers (mifx_oit_host.h; launch_oit_shade_blend, the seventh, is in pbr.hip beside the shade it contains: mifx_oit_shade_launch.h).  The per-pixel bodies are mifx_oit.h; the effect object, the argument checks, the sequencing and the C entries are api_oit.cpp.
+// launchers (mifx_oit_host.h; launch_oit_shade_blend, the seventh, is in pbr.hip beside the shade it contains).  The per-pixel bodies are mifx_oit.h; the effect object, the argument checks, the sequencing and the C entries are api_oit.cpp.
 //
 // Two shapes built from the same bodies:
 //   the reference's sequence, one launch each: oit_clear_kernel (ClearOITLayers.csh), oit_update_kernel (one draw of UpdateOITLayers.psh: reads and writes the pixel's K

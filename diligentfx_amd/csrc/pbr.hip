@@ -5,7 +5,7 @@
 //     world position rebuilt from depth with InvProjectPosition (PostFX_Common.fxh:99-105).  84 B/px: base colour, normal, material
 //     (3 x 16 B) + depth (4 B) in, radiance + specular IBL (2 x 16 B) out; LUT and cube maps are cache-resident (<= 9 MB).
 // Also here, because it is the layered shade's body with the OIT colour pass behind it: oit_shade_blend_kernel, one transparent draw shaded and blended in one launch
-// (mifx_oit_shade.h; launcher launch_oit_shade_blend, mifx_oit_shade_launch.h; entry mifx_oit_shade_blend, api_oit.cpp).
+// (mifx_oit_shade.h; launcher launch_oit_shade_blend, mifx_oit_host.h; entry mifx_oit_shade_blend, api_oit.cpp).
 #include "mifx_host.h"
 #include "mifx_objects.h"
 #include <cmath>
@@ -16,7 +16,7 @@
 #include "mifx_effects.h"
 #include "mifx_tonemap.h"
 #include "mifx_formats.h"
-#include "mifx_oit_shade_launch.h"
+#include "mifx_oit_host.h"
 #include "mifx_oit_shade.h"
 
 namespace mifx
@@ -720,9 +720,6 @@ mifx_status launch_oit_shade_blend(hipStream_t s, IblApronCache& iblApron, const
     const OitShadeBlend   oit{k, targets, color_alpha, check_only};
     return launch_pbr_shade_layers_impl(s, iblApron, g, layers ? *layers : none, camera, a, ibl, nullptr, nullptr, nullptr, 0, 0, reversedDepth, shadows, nullptr, nullptr, nullptr, &oit);
 }
-
-// (mifx_oit_shade_launch.h: how api_oit.cpp finds the launcher)
-static decltype(&launch_oit_shade_blend) g_launch_oit_shade_blend_installed = g_launch_oit_shade_blend = &launch_oit_shade_blend;
 
 mifx_status launch_pbr_hit_fetch(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                                  const float background[4], Img rays, Img hitCoords, const mifx_image2d* radiance, int shadedBegin, int shadedEnd, bool reversedDepth)

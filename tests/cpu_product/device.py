@@ -4,6 +4,9 @@ What runs is therefore the product's own sequencing (csrc/api_*.cpp: which plane
 arithmetic; tests compare its outputs with oracle/cpu_chain.py, whose sequencing is pinned to the executed reference host classes (tests/test_host_sequence_vs_ref.py): any
 difference is a difference of sequencing.  Nothing under diligentfx_amd/ imports this."""
 import ctypes
+import os
+import shutil
+import subprocess
 import threading
 
 import numpy as np
@@ -43,6 +46,65 @@ class SsrCleanupIn(ctypes.Structure):  # mifx::SsrCleanupIn (mifx_ssr_cleanup.h)
                 ("BilateralCleanupSpatialSigmaFactor", ctypes.c_float), ("AlphaInterpolation", ctypes.c_float), ("ReversedDepth", ctypes.c_int)]
 
 
+class HostPlane(ctypes.Structure):  # host_plane of tests/host_kernels/*.cpp: a tightly packed plane
+    _fields_ = [("data", ctypes.c_void_p), ("w", ctypes.c_int), ("h", ctypes.c_int), ("c", ctypes.c_int)]
+
+
+class OitCamK(ctypes.Structure):  # mifx::OitCamK (mifx_oit.h)
+    _fields_ = [("S", ctypes.c_float), ("reversed", ctypes.c_int)]
+
+
+class OitSliceK(ctypes.Structure):  # mifx::OitSliceK
+    PLANES = (("depth", 1), ("base", 4), ("material", 4), ("radiance", 4), ("ibl", 4), ("alpha", 1))
+    _fields_ = [(n, ctypes.c_void_p) for n, _ in PLANES] + [("pitch_" + n, ctypes.c_int) for n, _ in PLANES]
+
+
+class OitSlicesK(ctypes.Structure):  # mifx::OitSlicesK (MIFX_OIT_MAX_SLICES = 32)
+    _fields_ = [("s", OitSliceK * 32), ("count", ctypes.c_int)]
+
+
+class OitK(ctypes.Structure):  # mifx::OitK
+    _fields_ = [("layers", ctypes.c_void_p), ("tail", ctypes.c_void_p), ("opaque", ctypes.c_void_p), ("w", ctypes.c_int), ("h", ctypes.c_int), ("K", ctypes.c_int),
+                ("tailPitch", ctypes.c_int), ("opaquePitch", ctypes.c_int), ("cam", OitCamK)]
+
+
+class OitTargetsK(ctypes.Structure):  # mifx::OitTargetsK
+    _fields_ = [("color", Img), ("base", Img), ("material", Img), ("ibl", Img)]
+
+
+class SelectionK(ctypes.Structure):  # mifx::SelectionK (mifx_selection.h)
+    _fields_ = [("depth", Img), ("selectionDepth", Img), ("closest", Img), ("outline", ctypes.c_float * 3), ("occluded", ctypes.c_float * 3), ("desaturation", ctypes.c_float),
+                ("clearDepth", ctypes.c_float), ("outlineWidth", ctypes.c_float)]
+
+
+_HOST_LIBS = {}
+_HOST_LOCK = threading.Lock()
+
+
+def host_lib(name):
+    """tests/host_kernels/<name>.cpp -- the product's own per-pixel bodies compiled for the host, which the suite holds to the reference's fixtures bit for bit
+    (tests/host_kernels/README.md) -- as a library of its own under tests/host_kernels/_build/ (the tests of those bodies build theirs with their own flags)."""
+    with _HOST_LOCK:
+        if name not in _HOST_LIBS:
+            here = os.path.dirname(os.path.abspath(__file__))
+            root = os.path.dirname(os.path.dirname(here))
+            csrc = os.path.join(root, "diligentfx_amd", "csrc")
+            src = os.path.join(root, "tests", "host_kernels", name + ".cpp")
+            out_dir = os.path.join(root, "tests", "host_kernels", "_build")
+            os.makedirs(out_dir, exist_ok=True)
+            out = os.path.join(out_dir, "cpu_product_" + name + ".so")
+            deps = [src, os.path.join(root, "include", "mifx.h")] + [os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith(".h")]
+            if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+                hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+                tmp = f"{out}.{os.getpid()}.tmp"
+                r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-I", csrc, "-I",
+                                    os.path.join(root, "include"), "-o", tmp, src], capture_output=True, text=True)
+                assert r.returncode == 0, r.stderr[-4000:]
+                os.replace(tmp, out)
+            _HOST_LIBS[name] = ctypes.CDLL(out)
+        return _HOST_LIBS[name]
+
+
 TRACK = None  # tests/cpu_product/order.py LaneOrder while a run checks the order of the lanes: every view() is a read, every store() a write of the current launch
 
 
@@ -68,6 +130,20 @@ def store(img, values, c=1):
         v[...] = values
 
 
+def touch(p, write=False):
+    """A buffer of the launch that is no image -- the OIT layer words, the tail, the auto-exposure average: the allocation that starts at p is read / written as a whole."""
+    if TRACK is not None and p:
+        TRACK.access_raw(p, write)
+
+
+def plane(a):
+    """host_plane of a tight float32 array (h, w[, c]); None: the null plane"""
+    if a is None:
+        return HostPlane(None, 0, 0, 0)
+    assert a.dtype == np.float32 and a.flags.c_contiguous
+    return HostPlane(a.ctypes.data, a.shape[1], a.shape[0], a.shape[2] if a.ndim == 3 else 1)
+
+
 def tight(a):
     return np.ascontiguousarray(a, np.float32)
 
@@ -90,6 +166,7 @@ class Device:
         self.algorithm = "gtao"
         self.taa_flags_seen = None
         self.fail_next = None  # the name of a launch that fails once (MIFX_ERR_HIP) instead of running
+        self.names = {}  # address -> what the plane is, for the planes the order runs report by name (run.py order_features): the shade's outputs, the prep pass's
         self.composite_rows = []  # (row_begin, row_end) of every composite launch: the rows a band reads of SSAO's and SSR's outputs (run.py sharded_case empties and reads it)
 
     def chain(self, rev):
@@ -115,14 +192,16 @@ class Device:
                 TRACK.begin_launch(c.stream or 0, name + " (fails)")
                 TRACK.end_launch()
             return -3
+        # (launch_oit_shade_blend with check_only set is the launcher's argument checks alone: nothing is queued on a stream, so the order check sees no launch)
+        tracked = TRACK is not None and not (name == "oit_shade_blend" and a[-1].i)
         try:
             with self._lock:  # (the checker binds its textures to globals: one pass at a time, whichever rank's thread asks)
-                if TRACK is not None:
+                if tracked:
                     TRACK.begin_launch(c.stream or 0, name)
                 try:
                     getattr(self, "do_" + name)(*a)
                 finally:
-                    if TRACK is not None:
+                    if tracked:
                         TRACK.end_launch()
             return 0
         except Exception as e:  # noqa: BLE001 -- reported through the library's status, with the reason on stderr
@@ -150,6 +229,8 @@ class Device:
         ch.call("blue_noise", [s, t], [xy, zw], ival=[int(frame.i)])
         store(noise_xy.img, xy, 2)
         store(noise_zw.img, zw, 2)
+        for a, n in ((reproj, "reprojected depth"), (closest, "closest motion"), (noise_xy, "blue noise xy"), (noise_zw, "blue noise zw")):
+            self.names[a.img.p] = "prep: " + n
         d = tight(view(depth.img))
         rd = cpu_chain.f32(d.shape)
         ch.call("reprojected_depth", [d], [rd], cam0=cam, cam1=prev_cam)
@@ -493,7 +574,9 @@ class Device:
     def do_pbr_shade(self, apron, g, camera, attribs, ibl, background, out_radiance, out_spec, row_begin, row_end, reversed_depth, shadows, ssr_mask):
         from diligentfx_amd import binding as B
 
-        assert not shadows.p, "tests/cpu_product: the chain's shade without shadow maps"
+        if shadows.p:  # (the reference build has the default shade without shadow maps only: the kernel's own body, the empty layer set -- a transparent draw without layers)
+            assert not (ssr_mask.p and ctypes.c_int.from_address(ssr_mask.p + 2 * ctypes.sizeof(Img) + 12).value), "tests/cpu_product: no R2 by-product beside shadow maps"
+            return self._shade_layers_on_the_host(g, type("NoLayers", (), {"p": None})(), camera, attribs, ibl, background, out_radiance, out_spec, row_begin, row_end, reversed_depth, shadows)
         gb, ib = B.GBuffer.from_address(g.p), B.IBL.from_address(ibl.p)
         ch = self.chain(reversed_depth.i)
         img = lambda p, c: self.image(ctypes.addressof(p.contents), c)[0] if p else None  # noqa: E731
@@ -565,6 +648,7 @@ class Device:
 
     def do_tonemap(self, src, out, attribs, ave_log_lum, flags, ave_lum, packed_in):
         assert not packed_in.i
+        touch(ave_lum.p)
         lum = max(0.05, float(ctypes.c_float.from_address(ave_lum.p).value)) if ave_lum.p else ave_log_lum.f  # (auto exposure: GetAverageSceneLuminance of the 1x1 average)
         o = cpu_chain.f32((out.img.h, out.img.w, 4))
         self.chain(False).call("tonemap", [tight(view(src.img, 4))], [o], attribs=ctypes.string_at(attribs.p, attribs.bytes), fval=[lum], ival=[int(flags.i)])
@@ -580,6 +664,8 @@ class Device:
 
     @staticmethod
     def _average_luminance(low, average, elapsed, adapt):
+        touch(average.p)
+        touch(average.p, True)
         v = tight(low)
         while v.shape[0] > 1:
             v = ((v[0::2, 0::2] + v[0::2, 1::2]) + (v[1::2, 0::2] + v[1::2, 1::2])) * np.float32(0.25)
@@ -617,6 +703,11 @@ class Device:
 
         assert not hit.p, "tests/cpu_product: unsharded frames only"
         gb, ib, ly = B.GBuffer.from_address(g.p), B.IBL.from_address(ibl.p), B.PBRLayers.from_address(layers.p)
+        perms = {1: "clearcoat", 2: "sheen", 4: "anisotropy", 8: "iridescence", 16: "transmission", 31: "all"}
+        pcf = B.PBRShadows.from_address(shadows.p).pcf_filter_size if shadows.p else None
+        if ly.flags not in perms or (shadows.p and (ly.flags, pcf) not in ((31, 3), (2, 5))):
+            # no permutation of the reference build for this set (the empty set: a transparent draw without layers, shaded for mifx_oit_blend): the kernel's own body
+            return self._shade_layers_on_the_host(g, layers, camera, attribs, ibl, background, out_radiance, out_spec, row_begin, row_end, reversed_depth, shadows)
         img = lambda p, c: self.image(ctypes.addressof(p.contents), c)[0] if p else None  # noqa: E731
         lim = ib.brdf_lut.contents
         lut = self.image(ctypes.addressof(lim), {B.FORMAT_F32X2: 2, B.FORMAT_F32X4: 4}[lim.format])[0]
@@ -665,3 +756,258 @@ class Device:
 
     def do_pbr_hit_fetch(self, *args):
         pass  # (see do_ssr_intersection)
+
+    # ------------------------------------------------------------------------------------------------ the shade family on the product's own per-pixel bodies
+    # (tests/host_kernels: the reference has no single shader for the output stage, the footer's targets or a transparent draw; the suite holds these host compilations to the
+    # reference's fixtures bit for bit.)  Every plane goes through view() / store(): the order check sees it.
+    def _shade_inputs(self, g, layers, ibl, shadows):
+        """What mifx_host_pbr_shade_layers and its siblings take beside the outputs, from the launcher's arguments: (the six G-buffer planes, the seven layer planes, the
+        three tables, irradiance, prefiltered levels, flags, iridescence IOR, anisotropy rotation, shadow slices or None, shadow infos, PCF size); only the planes of the
+        layers that are switched on are bound, as launch_pbr_shade_layers binds them."""
+        from diligentfx_amd import binding as B
+
+        gb, ib = B.GBuffer.from_address(g.p), B.IBL.from_address(ibl.p)
+        img = lambda p, c: self.image(ctypes.addressof(p.contents), c)[0] if p else None  # noqa: E731
+
+        def table(p):
+            return img(p, {B.FORMAT_F32: 1, B.FORMAT_F32X2: 2, B.FORMAT_F32X4: 4}[p.contents.format])
+
+        def cube(cp):
+            cm = cp.contents
+            return [np.ctypeslib.as_array((ctypes.c_float * (6 * (cm.size >> m) * (cm.size >> m) * 4)).from_address(cm.mip_data[m])).reshape(6 * (cm.size >> m), cm.size >> m, 4).copy()
+                    for m in range(cm.mip_count)]
+
+        planes = [img(gb.base_color, 4), img(gb.normal, 4), img(gb.material, 4), img(gb.depth, 1), img(gb.emissive, 4), img(gb.occlusion, 1)]
+        ly = B.PBRLayers.from_address(layers.p) if layers.p else None
+        flags = ly.flags if ly is not None else 0
+        lp, tables = [None] * 7, [table(ib.brdf_lut), None, None]
+        if flags & B.PBR_LAYER_CLEAR_COAT:
+            lp[0], lp[1] = img(ly.clearcoat, 4), img(ly.clearcoat_normal, 4)
+        if flags & B.PBR_LAYER_SHEEN:
+            lp[2], tables[1], tables[2] = img(ly.sheen, 4), table(ly.sheen_albedo_scaling_lut), table(ly.preintegrated_charlie)
+        if flags & B.PBR_LAYER_ANISOTROPY:
+            lp[3], lp[4] = img(ly.anisotropy, 4), img(ly.tangent, 4)
+        if flags & B.PBR_LAYER_IRIDESCENCE:
+            lp[5] = img(ly.iridescence, 4)
+        if flags & B.PBR_LAYER_TRANSMISSION:
+            lp[6] = img(ly.transmission, 1)
+        slices = infos = None
+        pcf = 0
+        if shadows.p:
+            sh = B.PBRShadows.from_address(shadows.p)
+            sm = sh.shadow_map.contents
+            assert sm.pitch_bytes == sm.width * 4 and sm.slice_pitch_bytes == sm.pitch_bytes * sm.height
+            slices = np.ctypeslib.as_array((ctypes.c_float * (sm.slices * sm.height * sm.width)).from_address(sm.data)).reshape(sm.slices, sm.height, sm.width).copy()
+            infos = np.ctypeslib.as_array((ctypes.c_float * (24 * sh.shadow_map_count)).from_address(ctypes.addressof(sh.shadow_maps.contents))).reshape(-1, 24).copy()
+            pcf = sh.pcf_filter_size
+        return dict(planes=planes, layers=lp, tables=tables, irradiance=cube(ib.irradiance)[0], prefiltered=cube(ib.prefiltered), flags=flags,
+                    ior=ly.iridescence_ior if ly is not None else 1.3, rotation=ly.anisotropy_rotation if ly is not None else 0.0, slices=slices, infos=infos, pcf=pcf)
+
+    @staticmethod
+    def _shade_call(fn, lead, planes, si, camera, attribs, background, reversed_depth, tail):
+        """One of the host compilations of the layered shade family: `lead` arguments, the planes, the shared inputs of _shade_inputs, `tail` arguments"""
+        P = (HostPlane * len(planes))(*[plane(a) for a in planes])
+        L = (HostPlane * 7)(*[plane(a) for a in si["layers"]])
+        U = (HostPlane * 3)(*[plane(a) for a in si["tables"]])
+        irr = plane(si["irradiance"])
+        pre = (HostPlane * len(si["prefiltered"]))(*[plane(m) for m in si["prefiltered"]])
+        sm = infos = None
+        count = ninfo = 0
+        if si["slices"] is not None:
+            s = si["slices"]
+            sm, count = (HostPlane * 1)(HostPlane(s.ctypes.data, s.shape[2], s.shape[1], 1)), s.shape[0]
+            infos, ninfo = si["infos"].ctypes.data_as(ctypes.c_void_p), si["infos"].shape[0]
+        bg = [(ctypes.c_float * 4)(*background)] if background is not None else []
+        rc = fn(*lead, P, L, U, ctypes.byref(irr), pre, len(si["prefiltered"]), ctypes.c_void_p(camera.p), ctypes.c_void_p(attribs.p), *bg, ctypes.c_uint(si["flags"]),
+                ctypes.c_float(si["ior"]), ctypes.c_float(si["rotation"]), int(reversed_depth.i), sm, count, infos, ninfo, int(si["pcf"]), *tail)
+        assert rc == 0, rc
+
+    @staticmethod
+    def _background(background):
+        return [float(x) for x in np.ctypeslib.as_array((ctypes.c_float * 4).from_address(background.p))] if background.p else [0.0] * 4
+
+    @staticmethod
+    def _rows(desc, row_begin, row_end, c=4):
+        """The Img of a mifx_image2d with the launch's row window (row_end <= row_begin: the whole plane)"""
+        rb, re_ = int(row_begin.i), int(row_end.i)
+        return Img(desc.data, desc.width, desc.height, desc.pitch_bytes, rb, re_ - rb if re_ > rb else 0)
+
+    def _shade_layers_on_the_host(self, g, layers, camera, attribs, ibl, background, out_radiance, out_spec, row_begin, row_end, reversed_depth, shadows):
+        """launch_pbr_shade_layers for a layer set the reference build has no permutation of (the empty set: a transparent draw without layers in the unfused path)"""
+        from diligentfx_amd import binding as B
+
+        si = self._shade_inputs(g, layers, ibl, shadows)
+        rad_img = B.Image2D.from_address(out_radiance.p)
+        h, w = rad_img.height, rad_img.width
+        rad, spec = cpu_chain.f32((h, w, 4)), cpu_chain.f32((h, w, 4))
+        self._shade_call(host_lib("layers_host").mifx_host_pbr_shade_layers, (), si["planes"] + [rad, spec], si, camera, attribs, self._background(background), reversed_depth, (0,))
+        store(self._rows(rad_img, row_begin, row_end), rad, 4)
+        if out_spec.p:
+            store(self._rows(B.Image2D.from_address(out_spec.p), row_begin, row_end), spec, 4)
+
+    def do_pbr_shade_output(self, apron, g, layers, camera, attribs, ibl, background, out_color, out_spec, row_begin, row_end, reversed_depth, shadows, output, targets):
+        """pbr_shade_output_kernel / pbr_shade_targets_kernel: the layered shade with its output stage and, `targets`, the USD footer's four planes"""
+        from diligentfx_amd import binding as B
+
+        si = self._shade_inputs(g, layers, ibl, shadows)
+        desc = B.PBRShadeOutputDesc.from_address(output.p)
+        motion = self.image(ctypes.addressof(desc.motion.contents), 2)[0] if desc.motion else None
+        mesh = self.image(ctypes.addressof(desc.mesh_normal.contents), 4)[0] if desc.mesh_normal else None
+        col_img = B.Image2D.from_address(out_color.p)
+        h, w = col_img.height, col_img.width
+        color = cpu_chain.f32((h, w, 4))
+        if targets.p:
+            tg = B.PBRTargets.from_address(targets.p)
+            outs = [cpu_chain.f32((h, w, 4)) for _ in range(4)]
+            self._shade_call(host_lib("shade_targets_host").mifx_host_pbr_shade_targets, (), si["planes"] + [color, None, motion, mesh] + outs, si, camera, attribs,
+                             self._background(background), reversed_depth, (ctypes.c_void_p(output.p),))
+            for p, o, n in zip((tg.normal, tg.base_color, tg.material, tg.ibl), outs, ("normal", "base colour", "material", "IBL")):
+                store(self._rows(p.contents, row_begin, row_end), o, 4)
+                self.names[p.contents.data] = "target: " + n
+        else:
+            spec = cpu_chain.f32((h, w, 4)) if out_spec.p else None
+            self._shade_call(host_lib("shade_output_host").mifx_host_pbr_shade_output, (), si["planes"] + [color, spec, motion, mesh], si, camera, attribs, self._background(background),
+                             reversed_depth, (ctypes.c_void_p(output.p),))
+            if out_spec.p:
+                store(self._rows(B.Image2D.from_address(out_spec.p), row_begin, row_end), spec, 4)
+        store(self._rows(col_img, row_begin, row_end), color, 4)
+        self.names[col_img.data] = "radiance"
+
+    # ------------------------------------------------------------------------------------------------ order-independent transparency (oit.hip; the seventh kernel: pbr.hip)
+    # The bodies run in place on the memory the launcher names (tests/host_kernels/oit_host.cpp mifx_host_oit_launch); what the launch reads and writes is reported here:
+    # the slices' planes and the opaque depth are caller-owned reads, the four targets are read and written, the layer words and the tail are raw buffers (touch).
+    @staticmethod
+    def _oit_reads(k, slices, full):
+        for s in slices:
+            for name, c in OitSliceK.PLANES[: 6 if full else 2]:
+                p = getattr(s, name)
+                if p:
+                    view(Img(p, k.w, k.h, getattr(s, "pitch_" + name), 0, 0), c)
+        if k.opaque:
+            view(Img(k.opaque, k.w, k.h, k.opaquePitch, 0, 0), 1)
+
+    @staticmethod
+    def _oit_buffers(k, read, write):
+        for p in (k.layers, k.tail):
+            if read:
+                touch(p)
+            if write:
+                touch(p, True)
+
+    @staticmethod
+    def _oit_targets(t):
+        for im in (t.color, t.base, t.material, t.ibl):
+            view(im, 4)
+            view(im, 4, _write=True)
+
+    def _oit_launch(self, which, k, slice_=None, tab=None, targets=None):
+        rc = host_lib("oit_host").mifx_host_oit_launch(which, ctypes.c_void_p(k.p), ctypes.c_void_p(slice_.p if slice_ else None), ctypes.c_void_p(tab.p if tab else None),
+                                                       ctypes.c_void_p(targets.p if targets else None))
+        assert rc == 0, rc
+
+    def do_oit_clear(self, k):
+        self._oit_buffers(blob(k, OitK), False, True)
+        self._oit_launch(0, k)
+
+    def do_oit_update(self, k, slice_):
+        K = blob(k, OitK)
+        self._oit_reads(K, [blob(slice_, OitSliceK)], False)
+        self._oit_buffers(K, True, True)
+        self._oit_launch(1, k, slice_=slice_)
+
+    def do_oit_attenuate(self, k, targets):
+        self._oit_buffers(blob(k, OitK), True, False)
+        self._oit_targets(blob(targets, OitTargetsK))
+        self._oit_launch(2, k, targets=targets)
+
+    def do_oit_blend(self, k, slice_, targets):
+        K = blob(k, OitK)
+        self._oit_reads(K, [blob(slice_, OitSliceK)], True)
+        self._oit_buffers(K, True, False)
+        self._oit_targets(blob(targets, OitTargetsK))
+        self._oit_launch(3, k, slice_=slice_, targets=targets)
+
+    def do_oit_build(self, k, tab):
+        K, T = blob(k, OitK), blob(tab, OitSlicesK)
+        self._oit_reads(K, [T.s[i] for i in range(T.count)], False)
+        self._oit_buffers(K, False, True)
+        self._oit_launch(4, k, tab=tab)
+
+    def do_oit_resolve(self, k, tab, targets):
+        K, T = blob(k, OitK), blob(tab, OitSlicesK)
+        self._oit_reads(K, [T.s[i] for i in range(T.count)], True)
+        self._oit_buffers(K, True, False)
+        self._oit_targets(blob(targets, OitTargetsK))
+        self._oit_launch(5, k, tab=tab, targets=targets)
+
+    def do_oit_shade_blend(self, apron, k, targets, g, layers, color_alpha, camera, attribs, ibl, reversed_depth, shadows, check_only):
+        """oit_shade_blend_kernel: one transparent draw shaded and blended (tests/host_kernels/shade_blend_host.cpp); check_only: the launcher's argument checks alone"""
+        if check_only.i:
+            return
+        K = blob(k, OitK)
+        si = self._shade_inputs(g, layers, ibl, shadows)
+        alpha = self.image(color_alpha.p, 1)[0] if color_alpha.p else None
+        if K.opaque:
+            view(Img(K.opaque, K.w, K.h, K.opaquePitch, 0, 0), 1)
+        self._oit_buffers(K, True, False)
+        self._oit_targets(blob(targets, OitTargetsK))
+        self._shade_call(host_lib("shade_blend_host").mifx_host_oit_shade_blend_launch, (ctypes.c_void_p(k.p), ctypes.c_void_p(targets.p)), si["planes"] + [alpha], si, camera, attribs,
+                         None, reversed_depth, ())
+
+    # ------------------------------------------------------------------------------------------------ the selection outline (selection.hip, composite.hip)
+    def do_jump_flood(self, selection_depth, clear_depth, iterations, tmp0, tmp1, out, row_begin, row_end):
+        view(selection_depth.img)
+        if int(iterations.i) > 3:  # (kJfFused: the leading steps go through the two scratch planes, over the whole frame)
+            for t in (tmp0, tmp1):
+                if t.img.p:
+                    view(t.img, 2, _write=True)
+        rb, re_ = int(row_begin.i), int(row_end.i)
+        o = out.img
+        win = Img(o.p, o.w, o.h, o.pitch, rb, re_ - rb)
+        view(win, 2, _write=True)
+        rc = host_lib("selection_host").mifx_host_jump_flood_launch(ctypes.byref(selection_depth.img), ctypes.c_float(clear_depth.f), int(iterations.i), ctypes.byref(o), rb, re_)
+        assert rc == 0, rc
+
+    def do_composite_selection(self, attribs, sel, out_img, row_begin, row_end, r7):
+        """The composite with the selection tail: the reference's composite pass (composite_image), then the tail's body on its colour; the rows of the plain composite"""
+        from diligentfx_amd import binding as B
+
+        oi = B.Image2D.from_address(out_img.p)
+        h, w = oi.height, oi.width
+        colour = self.composite_image(attribs.p, r7.p, h, w)
+        k = blob(sel, SelectionK)
+        view(k.depth)
+        view(k.selectionDepth)
+        view(k.closest, 2)
+        o = cpu_chain.f32((h, w, 4))
+        rc = host_lib("selection_host").mifx_host_selection_tail_launch(colour.ctypes.data_as(ctypes.c_void_p), o.ctypes.data_as(ctypes.c_void_p), w, h, ctypes.c_void_p(sel.p))
+        assert rc == 0, rc
+        rb, re_ = int(row_begin.i), int(row_end.i)
+        self.composite_rows.append((rb, re_))
+        store(Img(oi.data, w, h, oi.pitch_bytes, rb, re_ - rb if re_ > rb else 0), o, 4)
+
+    # ------------------------------------------------------------------------------------------------ the coordinate grid (grid.hip)
+    def do_coordinate_grid(self, rows, target, raw, cam, attribs, flags):
+        d = rows.img
+        view(d)
+        t, r = target.img, raw.img
+        if t.p:
+            win = Img(t.p, t.w, t.h, t.pitch, d.y0, d.yn)
+            view(win, 4)
+            view(win, 4, _write=True)
+        if r.p:
+            view(Img(r.p, r.w, r.h, r.pitch, d.y0, d.yn), 4, _write=True)
+        rc = host_lib("grid_host").mifx_host_coordinate_grid_launch(ctypes.byref(d), ctypes.byref(t), ctypes.byref(r), ctypes.c_void_p(cam.p), ctypes.c_void_p(attribs.p), ctypes.c_uint(flags.i))
+        assert rc == 0, rc
+
+    def do_copy_frame_grid(self, src, packed_in, depth, out, attribs, ave_log_lum, tonemap_flags, ave_lum, cam, grid, grid_flags):
+        """copy_frame_grid_kernel in place of the tone map: the rows of `out`'s window, as the tone-map handler"""
+        assert not packed_in.i
+        view(src.img, 4)
+        view(depth.img)
+        touch(ave_lum.p)
+        view(out.img, 4, _write=True)
+        rc = host_lib("grid_host").mifx_host_copy_frame_grid_launch(ctypes.byref(src.img), ctypes.byref(depth.img), ctypes.byref(out.img), ctypes.c_void_p(attribs.p), ctypes.c_float(ave_log_lum.f),
+                                                                    ctypes.c_uint(tonemap_flags.i), ctypes.c_void_p(ave_lum.p), ctypes.c_void_p(cam.p), ctypes.c_void_p(grid.p),
+                                                                    ctypes.c_uint(grid_flags.i))
+        assert rc == 0, rc

@@ -3,7 +3,8 @@
 The CPU build of the host code (stub_device.cpp) executes every launch at once, in program order, so a missing hipStreamWaitEvent cannot change a result there -- and on the
 device it changes one only when the timing is unlucky.  This module turns the stand-in runtime into a race detector instead: it keeps a vector clock per stream and per
 recorded event (record = a copy of the stream's clock, wait = a merge, a host synchronisation = a merge into the host's clock, which every later operation starts from), and for
-every launch the planes its handler reads (device.view) and writes (device.store), by row window.  An access conflicts with an earlier one of another stream -- write / read,
+every launch the planes its handler reads (device.view) and writes (device.store), by row window, and the raw buffers it names (device.touch: the OIT layer words and
+tail, the auto-exposure average -- whole allocations).  An access conflicts with an earlier one of another stream -- write / read,
 read / write, write / write on overlapping rows of one plane -- unless the earlier one happens-before it by those clocks; every such pair is a finding.
 
 `drop_wait = k` ignores the k-th hipStreamWaitEvent of the run: the control that shows a missing wait IS found (run.py `order` drops every wait of a steady-state frame in turn and
@@ -98,6 +99,13 @@ class LaneOrder:
         s, clock, name = self.cur
         y0, y1 = (img.y0, img.y0 + img.yn) if (write and img.yn) else (0, img.h)  # a windowed launch writes its window; a handler reads the whole plane
         self._access(img.p, y0, y1, write, s, clock, name)
+
+    def access_raw(self, p, write):
+        """A buffer that is no image (the OIT layer words and tail, the auto-exposure average): the launch in progress reads / writes the allocation that starts at p, all of it"""
+        if self.cur is None or not p:
+            return
+        s, clock, name = self.cur
+        self._access(p, 0, 1 << 30, write, s, clock, name)
 
     def _access(self, base, y0, y1, write, s, clock, name):
         rec = self.planes.setdefault(base, {"w": [], "r": []})

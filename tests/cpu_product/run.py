@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY.  Runs scenarios of the DEVICE tests (tests/test_gpu_host_sequence.py: the effect objects driven through the C ABI, compared with oracle/cpu_chain.py)
 on the CPU build of the product's host code (tests/cpu_product/build.py) with the reference's shaders standing in for the kernels (tests/cpu_product/device.py).
 
-    MIFX_LIB_PATH=tests/cpu_product/_build/libmifx_cpu.so python tests/cpu_product/run.py scenarios | dof | chain | random FIRST LAST | chain_random FIRST LAST | order | trace [PART OF A NAME] | lane_errors | ...
+    MIFX_LIB_PATH=tests/cpu_product/_build/libmifx_cpu.so python tests/cpu_product/run.py scenarios | dof | chain | random FIRST LAST | chain_random FIRST LAST | order | order_features [PART] | feature_values [PART] | trace [PART OF A NAME] | lane_errors | ...
 
 (started by tests/test_cpu_product.py in a process of its own: the Python mirror diligentfx_amd/api.py is used as it is, with three of its device plumbing points replaced
 here -- the stream handle, the device of the tensors, the view of an effect-owned plane -- so that torch CPU tensors stand for device memory.)"""
@@ -337,11 +337,114 @@ def local_group_case(lib, case, frames=4, auto_exposure=False):
     return stats, infos
 
 
-def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, size=(96, 64), track=None, reset_at=None, edges=None, fail_at=None, fail="taa", outs=None):
+CONFIGS = {  # the feature configurations of run.py `order_features` (the switches of order_run's `cfg`)
+    "a": dict(output=True, targets=True),
+    "b": dict(output=True, targets=True, transparency=True),
+    "c": dict(output=True, targets=True, transparency=True, unfused=True),
+    "d": dict(selection=True, grid=True, auto_exposure=True),  # (+ depth of field: order_run's own switch)
+    "e": dict(output=True, targets=True, transparency=True, layers=True, selection=True, grid=True, auto_exposure=True),
+}
+CONFIG_NAMES = {"a": "shade output + targets", "b": "a + transparency, fused", "c": "a + transparency, unfused", "d": "selection + grid + depth of field + auto exposure",
+                "e": "b + layers + shadows + selection + grid + depth of field + auto exposure"}
+
+
+class Features:
+    """The chain features a configuration of order_run switches on, with the planes the chain borrows for them, made for one frame size.  cfg: output (the shade's output
+    stage with a desc), targets (write_targets), layers (all five material layers and two shadow-mapped lights), transparency (two slices, K = 4, the second with all five
+    layers and a color_alpha plane), unfused (mifx_chain_set_transparency_fusion 0 for the run), selection, grid, auto_exposure."""
+
+    def __init__(self, cfg):
+        self.cfg = dict(cfg)
+        self.layer_count, self.slice_count = 4, 2
+
+    def shade_attribs(self, last_mip):
+        import chain_util
+
+        return (chain_util.shadowed_shade_attribs if self.cfg.get("layers") else chain_util.shade_attribs)(last_mip)
+
+    def layers(self, normal, seed):
+        """All five layers as Chain.set_material_layers / transparent_slice take them, for the frame size of `normal`"""
+        from layers_util import make_layers
+
+        planes, albedo, charlie = make_layers(np.ascontiguousarray(normal), seed=seed)
+        dev = {k: torch.from_numpy(v) for k, v in planes.items()}
+        dev["transmission"] = dev["transmission"][..., 0].contiguous()
+        dev["sheen_albedo_scaling_lut"], dev["preintegrated_charlie"] = torch.from_numpy(albedo), torch.from_numpy(charlie)
+        return dev
+
+    def slices(self, w, h, normal):
+        import oit_util
+        import transparency_util as T
+        from layers_util import IOR, ROTATION
+
+        s = T.e2e_slices() if (w, h) == (24, 16) else T.make_slices(dict(name="order", w=w, h=h, k=4, l=2, reversed=False, opaque=True, alpha=True, seed=4242))
+        out = [dict(gbuffer={k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in gb.items()}) for gb in s["gbuffers"][:2]]
+        alpha = s["alpha"][1] if s["alpha"] is not None else (np.float32(0.2) + np.float32(0.6) * oit_util.field(77, h, w))
+        out[1].update(layers=self.layers(normal, 11), flags=31, iridescence_ior=IOR, anisotropy_rotation=ROTATION, color_alpha=torch.from_numpy(np.ascontiguousarray(alpha, np.float32)))
+        return out
+
+    def apply(self, chain, frame, what=None):
+        """Switches the configuration's features on for the size of `frame` (a synth frame); what: only these switches"""
+        import chain_util
+        import grid_util
+        from layers_util import IOR, ROTATION
+        from shade_output_util import _case, output_desc_fields
+
+        on = lambda k: self.cfg.get(k) and (what is None or k in what)  # noqa: E731
+        h, w = frame["depth"].shape
+        if on("layers"):
+            slices, infos = chain_util.make_shadow_inputs()
+            chain.set_material_layers(self.layers(frame["normal"].numpy(), 5), 31, IOR, ROTATION, shadows=(torch.from_numpy(np.stack(slices)), infos, 3))
+        if on("output") or on("targets"):
+            chain.set_shade_output(output_desc_fields(_case("chain")) if self.cfg.get("output") else None, bool(self.cfg.get("targets")))
+        if on("transparency"):
+            chain.set_transparency(self.slices(w, h, frame["normal"].numpy())[: self.slice_count], self.layer_count)
+        if on("selection"):
+            sel = torch.ones(h, w)
+            sel[h // 4: h // 2, w // 4: w // 2] = frame["depth"][h // 4: h // 2, w // 4: w // 2]
+            a = B.SelectionAttribs.default(selection_id=5)
+            a.nonselection_desaturation = 0.5
+            chain.set_selection(a, sel)
+        if on("grid"):
+            chain.set_coordinate_grid(B.CoordinateGridAttribs.default(), grid_util.FLAG_XZ | grid_util.AXES)
+        if on("auto_exposure"):
+            chain.set_auto_exposure(True, 1.0 / 60.0, True)
+
+
+def mid_run_sequence(i, chain, feat, frame):
+    """The fixed sequence of switches of tests/transparency_util.py mid_run_state, applied in front of frame i where the state changes (the chain starts with the shade's
+    output stage and targets on; the resize at frame 7 is the caller's: order_run's resize_at)."""
+    import transparency_util as T
+
+    targets, count, k, _ = state = T.mid_run_state(i)
+    if i == 0 or state[:3] == T.mid_run_state(i - 1)[:3]:
+        return
+    if not targets:
+        chain.set_transparency(None)
+        chain.set_shade_output(None, False)
+        return
+    feat.slice_count, feat.layer_count = count, k
+    if not T.mid_run_state(i - 1)[0]:
+        feat.apply(chain, frame, ("output", "targets"))
+    if count:
+        feat.apply(chain, frame, ("transparency",))
+    else:
+        chain.set_transparency(None)
+
+
+PLANES = ("normal", "base_color", "material", "ibl")
+MID_RUN_FRAMES = 10  # (tests/transparency_util.py MID_RUN_FRAMES: the sequence ends with two frames of everything back on)
+
+
+def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, size=(96, 64), track=None, reset_at=None, edges=None, fail_at=None, fail="taa", outs=None, cfg=None,
+              sequence=None, resize_at=None, check=True, planes=None, first_frame=16):
     """One chain object, `frames` frames queued without a host synchronisation in between (as bench.py queues them), under tests/cpu_product/order.py: returns the LaneOrder
     with its findings and the index range of the hipStreamWaitEvent calls of the last frame.  band = (y0, y1): mifx_chain_execute_band on that row band instead.
     track: a LaneOrder of the caller's (call_trace below); reset_at: reset_history before that frame; edges: mifx_chain_set_lane_edges; fail_at: the `fail` launch of that frame
-    fails (device.py fail_next), and `outs` receives every frame's output, or the error its execute raised."""
+    fails (device.py fail_next), and `outs` receives every frame's output, or the error its execute raised.
+    cfg: the feature switches of Features (CONFIGS); sequence(i, chain, features, frame): switches in front of frame i, the chain starting with the shade output and targets
+    alone; resize_at = (i, (w, h)): the frames from i on have that size; check off: no order check, the values alone; planes: receives the four target planes of every frame
+    (where the shade writes them)."""
     import chain_util
     import order as O
     from diligentfx_amd import synth
@@ -351,16 +454,23 @@ def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, s
     sobol, tile = blue_noise_tables()
     ibl_np = chain_util.make_ibl(pyref.ref_lib(), "ref_")
     ibl = api.IBLResources(torch.from_numpy(ibl_np["lut"]), [torch.from_numpy(m) for m in ibl_np["irradiance"]], [torch.from_numpy(m) for m in ibl_np["prefiltered"]])
-    shade = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
+    feat = Features(cfg) if cfg is not None else None
+    shade = feat.shade_attribs(len(ibl_np["prefiltered"]) - 1) if feat else chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
     scene = synth.Scene()
-    fr = [synth.make_frame(scene, 16 + i, W, H, torch.device("cpu")) for i in range(frames)]
+    sizes = [size if resize_at is None or i < resize_at[0] else resize_at[1] for i in range(frames)]
+    fr = [synth.make_frame(scene, first_frame + i, sizes[i][0], sizes[i][1], torch.device("cpu")) for i in range(frames)]
     track = track or O.LaneOrder()
     track.drop_wait = drop_wait
+    DEVICE.names.clear()  # (plane names by address: an address is used again after a resize, a re-created object, another run)
     cb = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)(track.runtime)
-    lib.mifx_cpu_set_runtime_callback(cb)
-    cpu_device.TRACK = track
+    if check:
+        lib.mifx_cpu_set_runtime_callback(cb)
+        cpu_device.TRACK = track
+    fusion = lib.mifx_chain_set_transparency_fusion(0 if feat and feat.cfg.get("unfused") else 1)
     try:
         chain = api.Chain(0, sobol, tile)
+        if feat:
+            feat.apply(chain, fr[0], ("output", "targets") if sequence else None)
         if dof:
             da = B.DOFAttribs.default()
             da.MaxCircleOfConfusion = 0.02
@@ -379,12 +489,17 @@ def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, s
         for i, f in enumerate(fr):
             if i == reset_at:
                 chain.reset_history()
+            if sequence:
+                sequence(i, chain, feat, f)
+            if sizes[i] != (W, H):
+                W, H = sizes[i]
+                out = torch.zeros(H, W, 4)
             DEVICE.cam, DEVICE.prev_cam = bytes(f["camera"]), bytes(f["prev_camera"])
             DEVICE.fail_next = fail if i == fail_at else None
             if i == fail_at and hasattr(track, "note"):
                 track.note("the failing frame begins", "", ())
             w0 = track.waits
-            b = chain.bind_frame(16 + i, f, ibl, shade, out)
+            b = chain.bind_frame(first_frame + i, f, ibl, shade, out)
             try:
                 (chain.execute_band if band else chain.execute)(b)
             except B.MifxError as e:
@@ -395,11 +510,14 @@ def order_run(lib, mode, mask, frames=7, band=None, drop_wait=None, dof=False, s
                     track.note("the failing frame returns", "", ())
             if outs is not None:
                 outs.append(out if isinstance(out, str) else out.clone())
+            if planes is not None:
+                planes.append({p: chain.shade_target(p).clone() for p in PLANES} if getattr(chain, "_shade_targets", False) else None)
             out = torch.zeros(H, W, 4) if isinstance(out, str) else out
             last = (w0, track.waits)
         chain.set_overlap(0)
         chain.close()
     finally:
+        lib.mifx_chain_set_transparency_fusion(fusion)
         cpu_device.TRACK = None
         lib.mifx_cpu_set_runtime_callback(ctypes.cast(None, ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)))
     return track, last
@@ -452,6 +570,33 @@ def call_trace(check_order=True):
                 super().access(img, write)
 
     return CallTrace()
+
+
+def event_trace():
+    """order.py's LaneOrder that also notes, for every hipStreamWaitEvent (by its index in the run), which launch preceded the record of the event it waits for on the
+    recording stream: `wait_after[k]` = "<launch> on <the stream, numbered by first appearance>" -- how run.py order_features tells the waits of a frame apart."""
+    import order as O
+
+    class EventTrace(O.LaneOrder):
+        def __init__(self):
+            super().__init__()
+            self.last_launch, self.event_after, self.wait_after, self.stream_ids = {}, {}, {}, {}
+
+        def runtime(self, op, a, b, n):
+            a0, b0 = a or 0, b or 0
+            if op == O.RT_EVENT_RECORD:
+                sid = self.stream_ids.setdefault(b0, len(self.stream_ids))
+                self.event_after[a0] = f"{self.last_launch.get(b0, 'nothing')} on stream {sid}"
+            elif op == O.RT_STREAM_WAIT:
+                self.wait_after[self.waits] = self.event_after.get(b0, "an event never recorded")
+            super().runtime(op, a, b, n)
+
+        def begin_launch(self, stream, name):
+            self.stream_ids.setdefault(stream, len(self.stream_ids))
+            self.last_launch[stream] = name
+            super().begin_launch(stream, name)
+
+    return EventTrace()
 
 
 def trace_configurations(lib):
@@ -641,6 +786,160 @@ def main():
             assert needed, f"overlap {mode}: no dropped wait was noticed -- the check sees nothing"
             print(f"cpu product: order control: overlap {mode}{', band' if band else ''}{', depth of field' if dof else ''}: of the {last[1] - last[0]} waits of a steady-state frame, dropping "
                   f"{len(needed)} leaves an unordered pair {needed}; {len(silent)} are implied by others or guard what this configuration does not touch {silent}", flush=True)
+    elif what == "order_features":
+        # the order of the lanes with the chain's newer features on (CONFIGS a - e): the shade's output stage and targets, the transparent draws fused and unfused, the
+        # selection outline, the coordinate grid, auto exposure, material layers with shadow maps -- five frames queued without a host synchronisation, every stream mode;
+        # a, b and e also with no fusion and every fusion; the fixed sequence of switches in modes 3 - 5; then the control on a, b and d.  argv[2]: which part
+        part = sys.argv[2] if len(sys.argv) > 2 else "all"
+        if part in ("cases", "all"):
+            for name in "abcde":
+                for mode in range(6):
+                    for mask in ((31, 0, 63) if name in "abe" else (31,)):
+                        t, last = order_run(lib, mode, mask, frames=5, dof=name in "de", cfg=CONFIGS[name])
+                        assert t.launches > 50, t.launches
+                        assert not t.findings, (name, mode, mask, t.describe()[:6], [DEVICE.names.get(f[1]) for f in t.findings[:6]])
+                        print(f"cpu product: feature order OK: {name} ({CONFIG_NAMES[name]}), overlap {mode}, fusion mask {mask}: {t.launches} launches, {t.waits} waits "
+                              f"({last[1] - last[0]} in the last frame), no unordered pair", flush=True)
+        if part in ("sequence", "all"):
+            for mode in (3, 4, 5):
+                t, _ = order_run(lib, mode, 31, frames=MID_RUN_FRAMES, cfg=CONFIGS["b"], sequence=mid_run_sequence, resize_at=(7, (80, 48)))
+                assert not t.findings, (mode, t.describe()[:6], [DEVICE.names.get(f[1]) for f in t.findings[:6]])
+                assert all(DEVICE.log.count(n) for n in ("oit_build", "oit_attenuate", "oit_shade_blend", "pbr_shade_output", "pbr_shade"))
+                print(f"cpu product: feature order OK: the sequence of switches, overlap {mode}: {t.launches} launches, {t.waits} waits, no unordered pair", flush=True)
+        if part.startswith("control") or part == "all":
+            # every wait of the last (steady-state) frame dropped in turn; the waits are told apart by the launch that preceded the record of their event on its stream
+            names = part[7:] or "abd"
+            for name in names:
+                for mode in range(1, 6):
+                    kw = dict(frames=5, dof=name == "d", cfg=CONFIGS[name])
+                    base = event_trace()
+                    _, last = order_run(lib, mode, 31, track=base, **kw)
+                    assert not base.findings
+                    needed, silent, found_by = [], [], {}
+                    for k in range(*last):
+                        t, _ = order_run(lib, mode, 31, drop_wait=k, **kw)
+                        (needed if t.findings else silent).append(k - last[0])
+                        found_by[f"{k - last[0]}, for the event recorded behind {base.wait_after[k]}"] = sorted({DEVICE.names.get(f[1], "another plane") for f in t.findings})
+                    assert needed, f"{name}, overlap {mode}: no dropped wait was noticed -- the check sees nothing"
+                    print(f"cpu product: feature order control: {name}, overlap {mode}: of the {last[1] - last[0]} waits of a steady-state frame, dropping {len(needed)} leaves an "
+                          f"unordered pair {needed}; {len(silent)} are implied by others or guard what this configuration does not touch {silent}", flush=True)
+                    for after, planes in found_by.items():
+                        print(f"    wait {after}: {', '.join(planes) if planes else 'not found'}", flush=True)
+                    if mode <= 2 and name in "ab":  # SSAO on the side stream reads the Normal target the shade writes on the context's stream
+                        shade = [a for a in found_by if a.split(" behind ")[1].split(" on ")[0] in ("pbr_shade_output", "oit_shade_blend", "oit_blend")]
+                        assert len(shade) == 1 and "target: normal" in found_by[shade[0]], (name, mode, found_by)
+                        print(f"cpu product: feature order control: {name}, overlap {mode}: the side stream's wait for evShade is needed: {found_by[shade[0]]}", flush=True)
+                    if mode >= 3 and name == "b":  # lane X behind lane S (evPrep, recorded behind SSR's depth hierarchy on S): through what the shade and the OIT passes write
+                        prep = [a for a in found_by if " behind ssr_hiz_pyramid" in a]
+                        hit = [p for a in prep for p in found_by[a] if p == "radiance" or p.startswith("target: ")]
+                        assert prep and hit, (name, mode, found_by)
+                        print(f"cpu product: feature order control: {name}, overlap {mode}: lane X's wait for evPrep is needed through {sorted(set(hit))}", flush=True)
+    elif what == "feature_values":
+        # sequencing equalities of the chain's newer features on this build (the same code runs on both sides of every comparison: bit for bit), on the frames of
+        # tests/test_gpu_transparency.py ChainCase at 24x16 and one more
+        import chain_util
+        import cpu_chain
+        from diligentfx_amd import synth
+        from layers_util import IOR, ROTATION
+        from shade_output_util import _case, output_desc_fields
+        from util import blue_noise_tables
+
+        W, H, N = 24, 16, 4
+        bits = lambda a, b: torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))  # noqa: E731
+
+        def run(name, mode, mask):
+            outs, planes = [], []
+            order_run(lib, mode, mask, frames=N, dof=name == "e", size=(W, H), cfg=CONFIGS[name], check=False, outs=outs, planes=planes, first_frame=0)
+            return outs, planes
+
+        part = sys.argv[2] if len(sys.argv) > 2 else "all"
+        one_stream = {}
+        for name in "be":
+            if part not in ("modes", "all"):
+                break
+            want = one_stream[name] = run(name, 0, 31)
+            n = 0
+            for mode in range(6):
+                for mask in (31, 0, 63):
+                    if (mode, mask) == (0, 31):
+                        continue
+                    got = run(name, mode, mask)
+                    for i in range(N):
+                        assert bits(got[0][i], want[0][i]), f"{name}, overlap {mode}, fusion mask {mask}, frame {i}: out_ldr differs from one stream with the default mask"
+                        for p in PLANES:
+                            assert bits(got[1][i][p], want[1][i][p]), f"{name}, overlap {mode}, fusion mask {mask}, frame {i}: target {p} differs from one stream with the default mask"
+                    n += 1
+            print(f"cpu product: feature values OK: {name} ({CONFIG_NAMES[name]}): {n} combinations of overlap mode and fusion mask equal one stream with the default mask, "
+                  f"{N} frames, out_ldr and four targets", flush=True)
+        if len(one_stream) == 2:  # (e is another picture than b: what it adds is in the frame)
+            assert not bits(one_stream["b"][0][N - 1], one_stream["e"][0][N - 1]), "configuration e gives the picture of configuration b"
+        ref = pyref.ref_lib()
+        ibl_np = chain_util.make_ibl(ref, "ref_")
+        ibl = api.IBLResources(torch.from_numpy(ibl_np["lut"]), [torch.from_numpy(m) for m in ibl_np["irradiance"]], [torch.from_numpy(m) for m in ibl_np["prefiltered"]])
+        last = len(ibl_np["prefiltered"]) - 1
+        scene = synth.Scene()
+        fr = [synth.make_frame(scene, i, W, H, torch.device("cpu")) for i in range(N)]
+        feat = Features(CONFIGS["b"])
+        slices = feat.slices(W, H, fr[0]["normal"].numpy())
+        ctx = api.PostFXContext(0, *blue_noise_tables())
+        if part in ("entries", "all"):
+            # the chain with configuration b against the public entries run outside it, per frame: all four targets; its out_ldr against oracle/cpu_chain.py fed the entries'
+            # planes and colour (tests/test_gpu_shade_targets.py test_chain_against_the_reference_passes_on_the_entrys_planes, here for equality)
+            outs, planes = one_stream.get("b") or run("b", 0, 31)
+            sa = feat.shade_attribs(last)
+            oit = api.OITResources(ctx, W, H, 4)
+            cpu = cpu_chain.CpuChain(ref, "ref_")
+            for i, f in enumerate(fr):
+                gdev = {k: f[k] for k in ("base_color", "normal", "material", "depth")}
+                color, normal, base, material, ibl_t = api.pbr_shade_targets(ctx, gdev, None, 0, f["camera"], sa, ibl, output=output_desc_fields(_case("chain")),
+                                                                             background=(0.02, 0.03, 0.05, 0.0))
+                untouched = base.clone()
+                t = dict(color=color, base_color=base, material=material, ibl=ibl_t)
+                oit.build_layers([dict(depth=x["gbuffer"]["depth"], base_color=x["gbuffer"]["base_color"]) for x in slices], f["camera"], f["depth"])
+                oit.apply_attenuation(t)
+                for x in slices:
+                    oit.shade_blend(x, f["camera"], sa, ibl, t, f["depth"])
+                assert not torch.equal(untouched, base)  # (something was blended)
+                for p, want in (("normal", normal), ("base_color", base), ("material", material), ("ibl", ibl_t)):
+                    assert bits(planes[i][p], want), f"frame {i}: the chain's target {p} differs from the public entries'"
+                g = {k: np.ascontiguousarray(v.numpy()) for k, v in f.items() if isinstance(v, torch.Tensor)}
+                g["emissive"] = g["occlusion"] = None
+                g["normal"], g["base_color"], g["material"] = (np.ascontiguousarray(x.numpy()) for x in (normal, base, material))
+                shade = lambda gg, cam, a, c=color, s=ibl_t: (np.ascontiguousarray(c.numpy()), np.ascontiguousarray(s.numpy()))  # noqa: E731
+                want = chain_util.run_frame_inputs(cpu, g, bytes(f["camera"]), bytes(f["prev_camera"]), i, ibl_np, sa, shade=shade)
+                exact(np.ascontiguousarray(outs[i].numpy()), want, what=f"frame {i}: the chain's out_ldr against the CPU chain on the entries' planes and colour")
+            oit.close()
+            print(f"cpu product: feature values OK: b equals the public entries outside the chain on four targets and the CPU chain fed their planes on out_ldr, {N} frames", flush=True)
+        if part in ("entry", "all"):
+            # mifx_oit_shade_blend on this build (it used to be refused here) against mifx_pbr_shade_execute_layers + mifx_oit_blend: one slice without layers, one with all
+            # five and a color_alpha plane, without and with two shadow-mapped lights
+            import oit_util
+
+            f = fr[1]
+            sm_np, infos = chain_util.make_shadow_inputs()
+            start = oit_util.e2e_inputs()["targets"]
+            for shadows, sa in ((None, chain_util.shade_attribs(last)), ((torch.from_numpy(np.stack(sm_np)), infos, 3), chain_util.shadowed_shade_attribs(last))):
+                oit = api.OITResources(ctx, W, H, 4)
+                sets = [{k: torch.from_numpy(start[j].copy()) for j, k in enumerate(api.OIT_TARGETS)} for _ in range(2)]
+                oit.build_layers([dict(depth=x["gbuffer"]["depth"], base_color=x["gbuffer"]["base_color"]) for x in slices], f["camera"], f["depth"])
+                for t in sets:
+                    oit.apply_attenuation(t)
+                for x in slices:
+                    g = x["gbuffer"]
+                    rad, spec = api.pbr_shade_layers(ctx, g, x.get("layers") or {}, x.get("flags", 0), f["camera"], sa, ibl, background=(0.0, 0.0, 0.0, 0.0), iridescence_ior=IOR,
+                                                     anisotropy_rotation=ROTATION, shadows=shadows)
+                    two = dict(depth=g["depth"], base_color=g["base_color"], material=g["material"], radiance=rad, specular_ibl=spec)
+                    if x.get("color_alpha") is not None:
+                        two["color_alpha"] = x["color_alpha"]
+                    oit.blend(two, f["camera"], sets[0], f["depth"])
+                    oit.shade_blend(x, f["camera"], sa, ibl, sets[1], f["depth"], shadows=shadows)
+                changed = sum(int((sets[1][k] != torch.from_numpy(start[j])).any(-1).sum()) for j, k in enumerate(api.OIT_TARGETS))
+                assert changed > W * H  # (blended, not merely attenuated: every target of most texels)
+                for k in api.OIT_TARGETS:
+                    assert bits(sets[0][k], sets[1][k]), f"mifx_oit_shade_blend, {'two shadow-mapped lights' if shadows else 'no shadow maps'}: target {k} differs from shade + blend"
+                oit.close()
+            print("cpu product: feature values OK: the host-only build runs mifx_oit_shade_blend: equal to mifx_pbr_shade_execute_layers + mifx_oit_blend, without and with shadow maps", flush=True)
+        ctx.close()
     elif what == "trace":
         # every stream / event call and launch of every frame path, per calling thread: diffed between two builds of the host code (a refactor keeps it identical)
         for name, fn, check in trace_configurations(lib):
@@ -750,35 +1049,19 @@ def main():
             chain_random(lib, seed, exact)
             print(f"cpu product: chain sequence OK: {seed}", flush=True)
     elif what == "unhandled":
-        # OIT and the shade's output stage: their host code is linked and runs up to its first launch, which device.py has no handler for
-        import chain_util
-        from diligentfx_amd import synth
-        from shade_output_util import _case, output_desc_fields
-        from util import blue_noise_tables
+        # a launcher without a handler in device.py fails loudly: the shadow maps' host code is linked and runs up to its first launch
+        import shadows_util
 
-        def status_of(fn, *a):
-            try:
-                fn(*a)
-            except B.MifxError as e:
-                return str(e)
-            return "MIFX_OK"
-
-        w, h = 16, 8
-        chain = api.Chain(0, *blue_noise_tables())
-        ibl_np = chain_util.make_ibl(pyref.ref_lib(), "ref_")
-        ibl = api.IBLResources(torch.from_numpy(ibl_np["lut"]), [torch.from_numpy(m) for m in ibl_np["irradiance"]], [torch.from_numpy(m) for m in ibl_np["prefiltered"]])
-        sa = chain_util.shade_attribs(len(ibl_np["prefiltered"]) - 1)
-        chain.set_shade_output(output_desc_fields(_case("chain")), True)  # (MIFX_OK: a refusal raises)
-        got = status_of(chain.execute, chain.bind_frame(0, synth.make_frame(synth.Scene(), 0, w, h, chain.device), ibl, sa, torch.zeros(h, w, 4)))
-        assert got.startswith("MIFX_ERR_NOT_IMPLEMENTED") and "launch_pbr_shade_output" in got, got
-        chain.close()
-        ctx = api.PostFXContext(0, *blue_noise_tables())
-        oit = api.OITResources(ctx, 5, 3, 4)
-        got = status_of(oit.clear_layers)
-        assert got.startswith("MIFX_ERR_NOT_IMPLEMENTED") and "launch_oit_clear" in got, got
-        oit.close()
+        ctx = api.PostFXContext(0)
+        mgr = api.ShadowMapManager(ctx, B.SHADOW_MODE_VSM)
+        try:
+            mgr.convert_to_filterable(torch.full((1, 8, 8), 0.5), shadows_util.make_attribs(1, 8, 8))
+            got = "MIFX_OK"
+        except B.MifxError as e:
+            got = str(e)
+        assert got.startswith("MIFX_ERR_NOT_IMPLEMENTED") and "launch_shadow_convert" in got, got
         ctx.close()
-        print("cpu product: scenario OK: the first launch of the shade's output stage and of OIT is refused by name", flush=True)
+        print("cpu product: scenario OK: the first launch of the shadow-map conversion is refused by name", flush=True)
     elif what == "dof":
         T.test_depth_of_field_follows_the_reference_sequencing(lib)
         print("cpu product: scenario OK: depth of field", flush=True)

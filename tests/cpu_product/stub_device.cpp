@@ -441,6 +441,11 @@ mifx_status launch_oit_resolve(hipStream_t s, const OitK& k, const OitSlicesK& t
     t_stream = s;
     return record("oit_resolve", k, tab, targets);
 }
+mifx_status launch_oit_shade_blend(hipStream_t s, IblApronCache& iblApron, const OitK& k, const OitTargetsK& targets, const mifx_gbuffer* g, const mifx_pbr_layers* layers, const mifx_image2d* color_alpha, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, bool reversedDepth, const mifx_pbr_shadows* shadows, bool check_only)
+{
+    t_stream = s;
+    return record("oit_shade_blend", iblApron, k, targets, g, layers, color_alpha, camera, a, ibl, reversedDepth, shadows, check_only);
+}
 mifx_status launch_jump_flood(hipStream_t s, Img selectionDepth, float clearDepth, int iterations, Img tmp0, Img tmp1, Img out, int rowBegin, int rowEnd)
 {
     t_stream = s;

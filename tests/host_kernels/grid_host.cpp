@@ -111,4 +111,61 @@ int mifx_host_copy_frame(const float* color, const float* depth, int w, int h, c
 }
 
 float mifx_host_grid_ipow(float s, float e) { return grid_ipow(s, e); }
+
+// The two launches of grid.hip on the launchers' own arguments, in place on the planes they name (tests/cpu_product/device.py: the handlers of the host-only build); the
+// rows of the launch are the row window of `depth` (coordinate_grid_kernel) / of `out` (copy_frame_grid_kernel), the whole plane without one.
+int mifx_host_coordinate_grid_launch(const Img* depth, const Img* target, const Img* raw, const GridCamK* cam, const mifx_coordinate_grid_attribs* a, uint32_t flags)
+{
+    const int y0 = depth->yn ? depth->y0 : 0, y1 = depth->yn ? depth->y0 + depth->yn : depth->h;
+    for (int y = y0; y < y1; ++y)
+        for (int x = 0; x < depth->w; ++x)
+        {
+            const float d = ld<float>(*depth, x, y);
+            const v4    g = shade(x, y, depth->w, depth->h, *cam, d, d, *a, flags);
+            if (raw->p)
+            {
+                float* o = reinterpret_cast<float*>(raw->p + size_t(y) * raw->pitch + size_t(x) * 16u);
+                o[0] = g.x; o[1] = g.y; o[2] = g.z; o[3] = g.w;
+            }
+            if (target->p)
+            {
+                const v4 dst = ld<v4>(*target, x, y);
+                st<v4>(*target, x, y, mk4(grid_blend(xyz(dst), g), dst.w));
+            }
+        }
+    return 0;
+}
+
+// ave_lum != null: the tone map's average from the auto-exposure object, as the kernel reads it
+int mifx_host_copy_frame_grid_launch(const Img* in, const Img* depth, const Img* out, const mifx_tone_mapping_attribs* tm, float ave_log_lum, uint32_t tonemap_flags, const float* ave_lum,
+                                     const GridCamK* cam, const mifx_coordinate_grid_attribs* a, uint32_t grid_flags)
+{
+    ToneMapK   k    = make_tonemapk(*tm, ave_log_lum);
+    const bool srgb = (tonemap_flags & MIFX_TONEMAP_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0;
+    if (ave_lum) k.aveLogLum = fmaxf(0.05f, *ave_lum);
+    const int w = out->w, h = out->h;
+    const int y0 = out->yn ? out->y0 : 0, y1 = out->yn ? out->y0 + out->yn : h;
+    auto at = [&](int x, int y) { return (x < 0 || y < 0 || x >= w || y >= h) ? 0.0f : ld<float>(*depth, x, y); };
+    for (int y = y0; y < y1; ++y)
+        for (int x = 0; x < w; ++x)
+        {
+            const v4 c = ld<v4>(*in, x, y);
+            v3 t{};
+#define MIFX_HOST_TM(M) t = tone_map<M>(xyz(c), k)
+            MIFX_TONEMAP_DISPATCH(tm->iToneMappingMode, MIFX_HOST_TM)
+#undef MIFX_HOST_TM
+            float lo = 1.0f, hi = 0.0f;
+            for (int dx = -1; dx <= 1; ++dx)
+                for (int dy = -1; dy <= 1; ++dy)
+                {
+                    const float d = at(x + dx, y + dy);
+                    lo = fminf(lo, d);
+                    hi = fmaxf(hi, d);
+                }
+            t = grid_lerp(t, coordinate_grid_at(x, y, w, h, *cam, lo, hi, *a, grid_flags));
+            if (srgb) t = linear_to_srgb(t);
+            st<v4>(*out, x, y, mk4(t, c.w));
+        }
+    return 0;
+}
 }

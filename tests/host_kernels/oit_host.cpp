@@ -82,6 +82,39 @@ int mifx_host_oit_fused(int K, int W, int H, int L, const float* depth, const fl
     return 0;
 }
 
+// One launch of oit.hip on the launcher's own arguments, in place on the memory they name, every pixel in order (tests/cpu_product/device.py: the handlers of the
+// host-only build).  which: 0 oit_clear_kernel, 1 oit_update_kernel, 2 oit_attenuate_kernel, 3 oit_blend_kernel, 4 oit_build_kernel<K>, 5 oit_resolve_kernel<K>;
+// the arguments a launch does not take are null.  Returns 0; -1 for an unknown launch; -2 for a fused launch at a layer count without a fused kernel.
+int mifx_host_oit_launch(int which, const OitK* k, const OitSliceK* slice, const OitSlicesK* tab, const OitTargetsK* t)
+{
+    const int W = k->w, H = k->h;
+    switch (which)
+    {
+        case 0: every_pixel(W, H, [&](int x, int y) { oit_px_clear(*k, x, y); }); return 0;
+        case 1: every_pixel(W, H, [&](int x, int y) { oit_px_update(*k, *slice, x, y); }); return 0;
+        case 2: every_pixel(W, H, [&](int x, int y) { oit_px_attenuate(*k, *t, x, y); }); return 0;
+        case 3: every_pixel(W, H, [&](int x, int y) { oit_px_blend(*k, *slice, *t, x, y); }); return 0;
+        case 4:
+        case 5: break;
+        default: return -1;
+    }
+#define MIFX_HOST_OIT_FUSED(K)                                                                      \
+    case K:                                                                                         \
+        if (which == 4) every_pixel(W, H, [&](int x, int y) { oit_px_build<K>(*k, *tab, x, y); });  \
+        else every_pixel(W, H, [&](int x, int y) { oit_px_resolve<K>(*k, *tab, *t, x, y); });       \
+        return 0;
+    switch (k->K)
+    {
+        MIFX_HOST_OIT_FUSED(1)
+        MIFX_HOST_OIT_FUSED(2)
+        MIFX_HOST_OIT_FUSED(3)
+        MIFX_HOST_OIT_FUSED(4)
+        MIFX_HOST_OIT_FUSED(8)
+        default: return -2;
+    }
+#undef MIFX_HOST_OIT_FUSED
+}
+
 // PackOITLayer and the two unpackers, for the test of the packing itself
 uint32_t mifx_host_oit_pack(float depth, float transmittance) { return oit_pack(depth, transmittance); }
 float    mifx_host_oit_layer_transmittance(uint32_t layer) { return oit_layer_transmittance(layer); }

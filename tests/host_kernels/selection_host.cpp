@@ -60,4 +60,43 @@ int mifx_host_selection_tail(const float* rgba_in, const float* depth, const flo
         }
     return 0;
 }
+
+// The two launches of the selection outline on the launchers' own arguments, in place on the planes they name (tests/cpu_product/device.py: the handlers of the host-only
+// build).  The jump flood: `iterations` steps as launch_jump_flood takes them, rows [row_begin, row_end) of `out` (F32X2) written.
+int mifx_host_jump_flood_launch(const Img* selection_depth, float clear_depth, int iterations, const Img* out, int row_begin, int row_end)
+{
+    const int w = selection_depth->w, h = selection_depth->h;
+    row_begin = row_begin < 0 ? 0 : row_begin; // (as launch_jump_flood clamps the band to the plane)
+    row_end   = row_end > out->h ? out->h : row_end;
+    std::vector<v2> a(size_t(w) * h), b(size_t(w) * h);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) a[size_t(y) * w + x] = jf_init(x, y, ld<float>(*selection_depth, x, y), clear_depth, w, h);
+    for (int i = 0; i < iterations; ++i)
+    {
+        const int range = 1 << (iterations - 1 - i);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) b[size_t(y) * w + x] = jf_step(x, y, range, w, h, [&](int tx, int ty) { return a[size_t(ty) * w + tx]; });
+        a.swap(b);
+    }
+    for (int y = row_begin; y < row_end; ++y)
+        for (int x = 0; x < w; ++x) st<v2>(*out, x, y, a[size_t(y) * w + x]);
+    return 0;
+}
+
+// the composite's selection tail on the composite's colour (rgba_in: w x h float4, tightly packed) with the kernel's own SelectionK; rgba_out: w x h float4
+int mifx_host_selection_tail_launch(const float* rgba_in, float* rgba_out, int w, int h, const SelectionK* k)
+{
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x)
+        {
+            const size_t i = size_t(y) * w + x;
+            const v3 rgb = selection_tail(v3{rgba_in[4 * i], rgba_in[4 * i + 1], rgba_in[4 * i + 2]}, x, y, w, h, ld<float>(k->depth, x, y), ld<float>(k->selectionDepth, x, y),
+                                          ld<v2>(k->closest, x, y), *k, [&](int lx, int ly, float& d, float& sd) {
+                                              d  = ld<float>(k->depth, lx, ly);
+                                              sd = ld<float>(k->selectionDepth, lx, ly);
+                                          });
+            rgba_out[4 * i] = rgb.x; rgba_out[4 * i + 1] = rgb.y; rgba_out[4 * i + 2] = rgb.z; rgba_out[4 * i + 3] = rgba_in[4 * i + 3];
+        }
+    return 0;
+}
 }

@@ -7,6 +7,7 @@
 #undef __device__
 #define __device__ __attribute__((host)) __attribute__((device))
 #include "mifx_oit_shade.h"
+#include <cmath>
 #include <cstring>
 
 using namespace mifx;
@@ -60,6 +61,63 @@ int mifx_host_transparency(int K, int W, int H, int L, const host_tslice* slices
             oit_px_shade_blend<false, false>(k, slice, t, lut, reinterpret_cast<const v4*>(irradiance->data), irradiance->w, pref, prefiltered[0].w, pref_levels, cam, sk, ly, sh, x, y);
         });
     }
+    return 0;
+}
+
+// One launch of oit_shade_blend_kernel on the launcher's own OitK / OitTargetsK, in place on the memory they name (tests/cpu_product/device.py: the handler of the
+// host-only build), with every other input as mifx_host_pbr_shade_layers (layers_host.cpp) takes it -- tightly packed planes, the layer set a run-time mask as in the kernel.
+// planes: base colour, normal, material (c = 4), depth (c = 1), emissive (c = 4) or null, occlusion (c = 1) or null, colour alpha (c = 1) or null.
+int mifx_host_oit_shade_blend_launch(const OitK* k, const OitTargetsK* t, const host_plane* planes, const host_plane* layers, const host_plane* luts, const host_plane* irradiance,
+                                     const host_plane* prefiltered, int pref_levels, const mifx_camera_attribs* camera, const mifx_pbr_shade_attribs* a, unsigned flags,
+                                     float iridescence_ior, float anisotropy_rotation, int reversed_depth, const host_plane* shadow_slices, int shadow_slice_count,
+                                     const mifx_pbr_shadow_map_info* shadow_infos, int shadow_info_count, int pcf_filter_size)
+{
+    auto img  = [](const host_plane& p) { return p.data ? Img{reinterpret_cast<unsigned char*>(p.data), p.w, p.h, p.w * p.c * 4, 0, 0} : Img{}; };
+    auto lutk = [](const host_plane& p) { return LutK{p.data, p.w, p.h, p.w * p.c, p.c}; };
+    const OitShadeSliceK slice{img(planes[0]), img(planes[1]), img(planes[2]), img(planes[3]), img(planes[4]), img(planes[5]), img(planes[6]),
+                               planes[4].data != nullptr, planes[5].data != nullptr, planes[6].data != nullptr};
+    LayersK ly{};
+    ly.flags = flags;
+    ly.iridescenceIor = iridescence_ior;
+    ly.rotationCos = std::cos(anisotropy_rotation);
+    ly.rotationSin = std::sin(anisotropy_rotation);
+    ly.clearcoat = img(layers[0]); ly.clearcoatNormal = img(layers[1]); ly.sheen = img(layers[2]); ly.anisotropy = img(layers[3]); ly.tangent = img(layers[4]);
+    ly.iridescence = img(layers[5]); ly.transmission = img(layers[6]);
+    ly.hasClearcoatNormal = layers[1].data != nullptr;
+    ly.hasTangent = layers[4].data != nullptr;
+    const LutK lut = lutk(luts[0]);
+    if (luts[1].data) ly.albedoScaling = lutk(luts[1]);
+    if (luts[2].data) ly.charlie = lutk(luts[2]);
+    ShadeK sk{};
+    sk.iblScale[0] = a->IBLScale[0]; sk.iblScale[1] = a->IBLScale[1]; sk.iblScale[2] = a->IBLScale[2];
+    sk.occlusionStrength = a->OcclusionStrength; sk.emissionScale = a->EmissionScale; sk.prefilteredCubeLastMip = a->PrefilteredCubeLastMip;
+    sk.lightCount = a->LightCount; sk.workflow = a->Workflow;
+    for (int i = 0; i < a->LightCount; ++i) sk.lights[i] = a->Lights[i];
+    CamK cam{}; // make_camk (mifx_core.cpp)
+    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
+    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
+    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
+    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
+    cam.reversedDepth = reversed_depth;
+    ShadowK sh{};
+    if (shadow_slices != nullptr)
+    {
+        sh.data = reinterpret_cast<const unsigned char*>(shadow_slices[0].data);
+        sh.w = shadow_slices[0].w; sh.h = shadow_slices[0].h; sh.slices = shadow_slice_count; sh.pitch = sh.w * 4;
+        sh.slicePitch = static_cast<unsigned long long>(sh.pitch) * sh.h;
+        sh.pcf = pcf_filter_size;
+        for (int i = 0; i < shadow_info_count && i < MIFX_PBR_MAX_SHADOW_MAPS; ++i) sh.info[i] = shadow_infos[i];
+    }
+    const v4* pref[12] = {};
+    for (int l = 0; l < pref_levels && l < 12; ++l) pref[l] = reinterpret_cast<const v4*>(prefiltered[l].data);
+    for (int y = 0; y < k->h; ++y)
+        for (int x = 0; x < k->w; ++x)
+        {
+            if (shadow_slices != nullptr)
+                oit_px_shade_blend<false, true>(*k, slice, *t, lut, reinterpret_cast<const v4*>(irradiance->data), irradiance->w, pref, prefiltered[0].w, pref_levels, cam, sk, ly, sh, x, y);
+            else
+                oit_px_shade_blend<false, false>(*k, slice, *t, lut, reinterpret_cast<const v4*>(irradiance->data), irradiance->w, pref, prefiltered[0].w, pref_levels, cam, sk, ly, sh, x, y);
+        }
     return 0;
 }
 }

@@ -47,14 +47,15 @@ def test_the_launcher_stubs_are_what_the_generator_prints():
     marker = [i for i, line in enumerate(lines) if line.startswith("// ---") and "the launchers" in line]
     assert len(marker) == 1, marker
     assert "".join(lines[marker[0] + 1:]) == r.stdout, "stub_device.cpp: re-run tests/cpu_product/gen_stubs.py and paste its output below the marker"
-    assert r.stdout.count("mifx_status launch_") >= 68  # (the 56 launchers of mifx_host.h and the twelve of the mifx_*_host.h headers)
+    assert r.stdout.count("mifx_status launch_") >= 69  # (the 56 launchers of mifx_host.h and the thirteen of the mifx_*_host.h headers)
+    assert "mifx_status launch_oit_shade_blend(" in r.stdout
 
 
-def test_oit_and_the_shade_output_stage_are_linked_and_refused_at_their_first_launch(cpu_lib):
-    """The host code of the shade's output stage (api_pbr.cpp, api_chain.cpp) and of OIT (api_oit.cpp) is part of the CPU build and runs up to its first launch, which has
-    no handler in device.py: mifx_chain_set_shade_output(desc, 1) returns MIFX_OK and the mifx_chain_execute of a 16 x 8 frame behind it MIFX_ERR_NOT_IMPLEMENTED with
-    launch_pbr_shade_output in mifx_last_error; mifx_oit_create at 5 x 3, K = 4 succeeds and mifx_oit_clear_layers answers the same with launch_oit_clear."""
-    assert "cpu product: scenario OK: the first launch of the shade's output stage and of OIT is refused by name" in run(cpu_lib, "unhandled")
+def test_the_shadow_map_conversion_is_linked_and_refused_at_its_first_launch(cpu_lib):
+    """A launcher without a handler in device.py fails loudly.  The host code of the shadow maps (api_shadows.cpp) is part of the CPU build and runs up to its first launch:
+    mifx_shadow_convert_to_filterable of an 8 x 8 map with one cascade passes its argument checks and answers MIFX_ERR_NOT_IMPLEMENTED with launch_shadow_convert in
+    mifx_last_error.  (The shade's output stage, OIT, the selection outline and the coordinate grid were refused this way until their handlers were written.)"""
+    assert "cpu product: scenario OK: the first launch of the shadow-map conversion is refused by name" in run(cpu_lib, "unhandled")
 
 
 def test_host_objects_on_the_cpu_equal_the_reference_sequencing(cpu_lib):
@@ -195,3 +196,75 @@ def test_blooms_level_0_halo_exchange_runs_and_shortens_the_history_halos(cpu_li
     Three ranks on uneven bands, the switch off and on (MIFX_SHARD_BLOOM_HALO, read per frame): one more exchange group per frame, fewer bytes per frame in total, shorter history
     halos reported by mifx_chain_get_shard_info -- and both frames equal the unsharded chain object's bit for bit."""
     assert "cpu product: Bloom level-0 halo OK" in run(cpu_lib, "bloom_halo", timeout=900)
+
+
+CONFIGURATIONS = ("a", "b", "c", "d", "e")  # tests/cpu_product/run.py CONFIGS
+
+
+def test_the_order_of_the_lanes_with_the_newer_features_has_no_unordered_pair(cpu_lib):
+    """tests/cpu_product/order.py over the features that run inside mifx_chain_execute since the plain chain was order-checked -- a: the shade's output stage with a desc and
+    its G-buffer targets; b: a + two transparent slices, K = 4, one with all five layers and a color_alpha plane, the fused launch; c: the same unfused; d: selection
+    outline + coordinate grid + depth of field + auto exposure; e: b + material layers + two shadow-mapped lights + everything of d.  Five frames at 96x64 queued without a
+    host synchronisation (modes 4 / 5 take their two-frames-in-flight path more than once), every overlap mode 0 - 5; a, b and e also with no fusion and every fusion.
+    The handlers report every plane through view() / store() and the OIT layer words, the tail and the auto-exposure average as raw buffers: no pair of conflicting
+    accesses of two streams without a happens-before edge."""
+    out = run(cpu_lib, "order_features", "cases", timeout=1500)
+    for name in CONFIGURATIONS:
+        for mode in range(6):
+            for mask in ((31, 0, 63) if name in "abe" else (31,)):
+                assert sum(1 for line in out.splitlines() if line.startswith(f"cpu product: feature order OK: {name} (") and f"overlap {mode}, fusion mask {mask}:" in line
+                           and line.endswith("no unordered pair")) == 1, (name, mode, mask, out)
+    assert out.count("cpu product: feature order OK") == 66, out
+
+
+def test_switching_the_features_mid_run_keeps_the_lanes_ordered(cpu_lib):
+    """Ten frames in modes 3, 4 and 5 under order.py, the chain starting with the shade output and targets: transparency on at frame 2, one slice instead of two at 3,
+    another layer_count at 4 (the OIT object is destroyed and re-created: hipFree), transparency off at 5, mifx_chain_set_shade_output(NULL, 0) at 6, a resize to 80x48 at
+    7, everything back on at 8 -- no unordered pair; every kind of launch the sequence is about did run."""
+    out = run(cpu_lib, "order_features", "sequence", timeout=900)
+    assert out.count("cpu product: feature order OK: the sequence of switches") == 3 and all(f"the sequence of switches, overlap {m}:" in out for m in (3, 4, 5)), out
+
+
+@pytest.mark.parametrize("name", ["a", "b", "d"])
+def test_a_dropped_wait_is_found_with_the_newer_features_on(cpu_lib, name):
+    """The control of the check above: in every mode 1 - 5 each hipStreamWaitEvent of the fifth (steady-state) frame is ignored in turn; per mode at least one drop leaves an
+    unordered pair.  With write_targets on (a, b) in modes 1 and 2 the side stream's wait for evShade -- the event recorded behind the shade, or behind the last transparent
+    draw -- is among them, found on the Normal target SSAO reads; with transparency on (b) in modes 3 - 5 the wait of lane X for evPrep is found through the radiance or a
+    target plane, not only through the prep pass's planes.  The run prints which planes each dropped wait was found on."""
+    out = run(cpu_lib, "order_features", "control" + name, timeout=1500)
+    lines = out.splitlines()
+    for mode in range(1, 6):
+        head = [ln for ln in lines if ln.startswith(f"cpu product: feature order control: {name}, overlap {mode}: of the ")]
+        assert len(head) == 1 and " dropping 0 leaves" not in head[0], (mode, out)
+    if name in "ab":
+        for mode in (1, 2):
+            assert any(ln.startswith(f"cpu product: feature order control: {name}, overlap {mode}: the side stream's wait for evShade is needed") and "target: normal" in ln
+                       for ln in lines), (mode, out)
+    if name == "b":
+        for mode in (3, 4, 5):
+            assert any(ln.startswith(f"cpu product: feature order control: {name}, overlap {mode}: lane X's wait for evPrep is needed through") and
+                       ("radiance" in ln or "target: " in ln) for ln in lines), (mode, out)
+
+
+def test_the_newer_features_equal_one_stream_in_every_mode_on_the_cpu(cpu_lib):
+    """Configurations b and e on the frames of tests/test_gpu_transparency.py ChainCase at 24x16 (and one more): every overlap mode 0 - 5 with fusion masks 31, 0 and 63
+    equals one stream with the default mask over four frames, bit for bit, on out_ldr and the four target planes.  Streams do nothing in this build; which plane set a kernel
+    is handed in modes 4 / 5 (the targets joined the double-buffered set) is host logic and shows here."""
+    out = run(cpu_lib, "feature_values", "modes", timeout=1500)
+    assert out.count("17 combinations of overlap mode and fusion mask equal one stream with the default mask, 4 frames, out_ldr and four targets") == 2, out
+
+
+def test_the_chain_with_transparency_equals_the_public_entries_on_the_cpu(cpu_lib):
+    """Configuration b against mifx_pbr_shade_targets, mifx_oit_build_layers, mifx_oit_apply_attenuation and one mifx_oit_shade_blend per slice with the frame's depth, run
+    outside the chain on the same build: the four targets per frame, bit for bit; and the chain's out_ldr against oracle/cpu_chain.py fed those planes and that colour --
+    the radiance the chain blends the transparent colour into, which no entry reads back, is held through the picture made from it."""
+    assert "cpu product: feature values OK: b equals the public entries outside the chain on four targets and the CPU chain fed their planes on out_ldr, 4 frames" in run(
+        cpu_lib, "feature_values", "entries", timeout=900)
+
+
+def test_the_host_only_build_runs_the_shade_blend_entry(cpu_lib):
+    """launch_oit_shade_blend is one of the generated stand-ins now (it used to be reached through a pointer nothing installed here, and the entry was refused): on this
+    build mifx_oit_shade_blend equals mifx_pbr_shade_execute_layers + mifx_oit_blend on all four targets, for a slice without layers and one with all five and a color_alpha
+    plane, without and with two shadow-mapped lights."""
+    assert "cpu product: feature values OK: the host-only build runs mifx_oit_shade_blend" in run(cpu_lib, "feature_values", "entry", timeout=900)
+

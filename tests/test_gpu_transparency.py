@@ -2,7 +2,8 @@
 -- mifx_pbr_shade_execute_layers into two planes, then mifx_oit_blend -- bit for bit on all four targets, at the fixture's boundary frame sizes, every plane pitched and
 offset inside a sentinel block; the 24x16 end-to-end case against the reference's targets (tests/golden/oit_golden.npz) by the project's contract, util.assert_close at
 its defaults with no outlier; and mifx_chain_set_transparency: fused against unfused, the overlap modes against one stream, the chain against the public entries run
-outside it -- all bit for bit --, the chain with transparency off, and its refusals.  Inputs: tests/transparency_util.py."""
+outside it -- all bit for bit --, the chain with transparency off, and its refusals; then the chain's picture against the CPU chain fed the entries' planes, layers / shadow maps / color_alpha passed
+through the chain, the boundary frame sizes, and a fixed sequence of switches in the middle of a run.  Inputs: tests/transparency_util.py."""
 import numpy as np
 import pytest
 import torch
@@ -29,7 +30,7 @@ def world(mifx_lib):
     ctx = api.PostFXContext(0, *blue_noise_tables())
     slices, infos = chain_util.make_shadow_inputs()
     last = len(ibl_np["prefiltered"]) - 1
-    return dict(ctx=ctx, ibl=ibl_to_device(ibl_np, ctx.device), sa=chain_util.shade_attribs(last), sa_shadowed=chain_util.shadowed_shade_attribs(last),
+    return dict(ctx=ctx, ibl=ibl_to_device(ibl_np, ctx.device), ibl_np=ibl_np, sa=chain_util.shade_attribs(last), sa_shadowed=chain_util.shadowed_shade_attribs(last),
                 shadows=(torch.from_numpy(np.stack(slices)).to(ctx.device), infos, 3))
 
 
@@ -329,3 +330,210 @@ def test_chain_refusals(world):
     with pytest.raises(B.MifxError, match="write_targets"):
         chain.set_transparency(cc.slices, 4)
     chain.close()
+
+
+# ------------------------------------------------------------------------------------------------ the chain: the picture, what it passes through, boundary sizes, switches
+class FeatureCase:
+    """Consecutive frames of one history at w x h with two hash-made transparent slices (T.chain_slices: its coverage conditions are asserted there on the CPU and here
+    against the device's own frame depth), made once and left unchanged.  rich: both slices carry all five material layers (layers_util.make_layers), the second a
+    color_alpha plane, and the chain shades with all five layers and two shadow-mapped lights (set_material_layers(..., shadows=...))."""
+
+    def __init__(self, world, w, h, frames=3, rich=True, first=0):
+        from diligentfx_amd import synth
+        from layers_util import IOR, ROTATION
+
+        dev = world["ctx"].device
+        self.w, self.h, self.world, self.rich = w, h, world, rich
+        scene = synth.Scene()
+        self.f = [synth.make_frame(scene, first + i, w, h, dev) for i in range(frames)]
+        self.index = [first + i for i in range(frames)]
+        s = T.chain_slices(w, h)
+        depth = np.stack([g["depth"] for g in s["gbuffers"]])
+        for f in self.f:
+            T.check_coverage(T.fragment_mask(depth, f["depth"].cpu().numpy(), False), f"{w}x{h}")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        self.slices = [dict(gbuffer={k: up(v) for k, v in gb.items()}) for gb in s["gbuffers"]]
+        self.sa, self.shadows, self.layers = world["sa"], None, None
+        if rich:
+            for j, sl in enumerate(self.slices):
+                sl.update(layers=_layers(world, s, 11 + j), flags=31, iridescence_ior=IOR, anisotropy_rotation=ROTATION)
+            self.sa, self.shadows = world["sa_shadowed"], world["shadows"]
+            self.layers = _layers(world, dict(gbuffers=[dict(normal=self.f[0]["normal"].cpu().numpy())]), 5)
+        self.slices[1]["color_alpha"] = up(s["alpha"][1])
+
+    def set_layers(self, chain):
+        from layers_util import IOR, ROTATION
+
+        if self.rich:
+            chain.set_material_layers(self.layers, 31, IOR, ROTATION, shadows=self.shadows)
+
+    def entries(self, i, oit, count=2):
+        """The public entries outside the chain for frame i: mifx_pbr_shade_targets, then -- `count` slices -- build_layers, apply_attenuation and one shade_blend per slice
+        with the frame's depth.  Returns (colour, {plane: tensor})"""
+        from diligentfx_amd import api
+        from layers_util import IOR, ROTATION
+
+        world, f = self.world, self.f[i]
+        gdev = {k: f[k] for k in ("base_color", "normal", "material", "depth")}
+        color, normal, base, material, ibl = api.pbr_shade_targets(world["ctx"], gdev, self.layers, 31 if self.rich else 0, f["camera"], self.sa, world["ibl"], shadows=self.shadows,
+                                                                   background=(0.02, 0.03, 0.05, 0.0), iridescence_ior=IOR, anisotropy_rotation=ROTATION)
+        if count:
+            t = dict(color=color, base_color=base, material=material, ibl=ibl)
+            sl = self.slices[:count]
+            oit.build_layers([dict(depth=x["gbuffer"]["depth"], base_color=x["gbuffer"]["base_color"]) for x in sl], f["camera"], f["depth"])
+            oit.apply_attenuation(t)
+            for x in sl:
+                oit.shade_blend(x, f["camera"], self.sa, world["ibl"], t, f["depth"], shadows=self.shadows)
+        torch.cuda.synchronize()
+        return color, dict(normal=normal, base_color=base, material=material, ibl=ibl)
+
+    def run(self, configure=None):
+        """(out_ldr, {plane: tensor}) per frame of a chain with the shade's targets and the case's slices"""
+        from diligentfx_amd import api
+
+        chain = api.Chain(0, *blue_noise_tables())
+        chain.set_shade_output(None, True)
+        self.set_layers(chain)
+        chain.set_transparency(self.slices, 4)
+        if configure:
+            configure(chain)
+        outs = []
+        for i, f in enumerate(self.f):
+            out = torch.zeros(self.h, self.w, 4, device=chain.device)
+            chain.execute(chain.bind_frame(self.index[i], f, self.world["ibl"], self.sa, out))
+            torch.cuda.synchronize()
+            outs.append((out, {p: chain.shade_target(p).clone() for p in PLANES}))
+        chain.close()
+        return outs
+
+
+def _equal_to_the_entries(mifx_lib, case, what):
+    """The chain of `case`, fused and unfused, against the public entries outside it: all four targets of every frame, bit for bit"""
+    from diligentfx_amd import api
+
+    default = mifx_lib.mifx_chain_set_transparency_fusion(0)
+    try:
+        unfused = case.run()
+        mifx_lib.mifx_chain_set_transparency_fusion(1)
+        fused = case.run()
+    finally:
+        mifx_lib.mifx_chain_set_transparency_fusion(default)
+    oit = api.OITResources(case.world["ctx"], case.w, case.h, 4)
+    for i in range(len(case.f)):
+        _, opaque = case.entries(i, oit, count=0)
+        _, want = case.entries(i, oit)
+        assert not torch.equal(opaque["base_color"], want["base_color"])  # (something was blended)
+        for p in PLANES:
+            assert torch.equal(fused[i][1][p].view(torch.int32), want[p].view(torch.int32)), (what, "fused", i, p)
+            assert torch.equal(unfused[i][1][p].view(torch.int32), want[p].view(torch.int32)), (what, "unfused", i, p)
+        assert torch.equal(fused[i][0].view(torch.int32), unfused[i][0].view(torch.int32)), (what, i, "out_ldr, fused against unfused")
+    oit.close()
+
+
+@pytest.mark.parametrize("size", CHAIN_SIZES, ids=[f"{w}x{h}" for w, h in CHAIN_SIZES])
+def test_chain_passes_layers_shadow_maps_and_color_alpha_through(mifx_lib, world, size):
+    """test_chain_equals_the_public_entries_outside_it with what chain_transparency passes through and the other chain tests leave out: both slices carry all five material
+    layers, the second a color_alpha plane, and the chain itself shades with all five layers and two shadow-mapped lights, which the transparent draws share.  All four
+    targets bit for bit, the fused launch and the unfused sequence."""
+    _equal_to_the_entries(mifx_lib, FeatureCase(world, *size), f"layers, shadow maps, color_alpha at {size}")
+
+
+@pytest.mark.parametrize("size", [(8, 8), (33, 17)], ids=["8x8", "33x17"])
+def test_chain_equals_the_public_entries_at_boundary_sizes(mifx_lib, world, size):
+    """The same equality at the frame sizes of test_chain_edges -- 8x8: one partial workgroup; 33x17: one texel beyond a tile in x, one row beyond in y -- with slices made
+    for those sizes (transparency_util.CHAIN_SEEDS: every slice covers 5 % of the texels, one texel is covered by none)"""
+    _equal_to_the_entries(mifx_lib, FeatureCase(world, *size), f"boundary size {size}")
+
+
+def test_chain_picture_against_the_cpu_chain_on_the_entries_planes(world):
+    """The chain blends the transparent colour into its own radiance plane, which no entry reads back: held here through the picture made from it.  Three frames at 224x128,
+    two hash-made slices, the final image against the CPU chain whose shade is the colour and the IBL target the stand-alone entries produced for the frame (shade targets,
+    build_layers, apply_attenuation, one shade_blend per slice) and whose passes read those entries' normal / base colour / material.  The budget of
+    tests/test_gpu_shade_targets.py::test_chain_against_the_reference_passes_on_the_entrys_planes, whose later passes are the same."""
+    import chain_util
+    import cpu_chain
+    from diligentfx_amd import api
+    from layers_util import ref_checker
+
+    case = FeatureCase(world, 224, 128, rich=False)
+    got = case.run()
+    cpu = cpu_chain.CpuChain(ref_checker(), "ref_")
+    oit = api.OITResources(world["ctx"], case.w, case.h, 4)
+    to_np = lambda t: np.ascontiguousarray(t.detach().cpu().numpy())  # noqa: E731
+    fracs = []
+    for i, f in enumerate(case.f):
+        opaque_color, _ = case.entries(i, oit, count=0)
+        color, planes = case.entries(i, oit)
+        assert float((color - opaque_color).abs().max()) > 1e-2  # (the transparent colour is in the radiance the passes are fed)
+        g = {k: to_np(v) for k, v in f.items() if isinstance(v, torch.Tensor)}
+        g["emissive"] = g["occlusion"] = None
+        g["normal"], g["base_color"], g["material"] = to_np(planes["normal"]), to_np(planes["base_color"]), to_np(planes["material"])
+        shade = lambda gg, cam, a, c=color, s=planes["ibl"]: (to_np(c), to_np(s))  # noqa: E731
+        want = chain_util.run_frame_inputs(cpu, g, bytes(f["camera"]), bytes(f["prev_camera"]), i, world["ibl_np"], case.sa, shade=shade)
+        out = to_np(got[i][0])
+        assert np.isfinite(out).all()
+        _, frac = assert_close(out, want, max_outlier_frac=5e-3, outlier_cap=(5e-2, 2e-4), what=f"chain with transparency, final image frame {i}")
+        fracs.append(frac)
+        mean = float(np.abs(out[..., :3] - want[..., :3]).mean())
+        print(f"chain with transparency at 224x128, frame {i}: outlier fraction {frac:.5f}, mean |RGB difference| {mean:.3e}")
+        assert mean < 1e-3
+    print("chain with transparency, outlier fractions per frame:", [round(x, 5) for x in fracs])
+    oit.close()
+
+
+def _mid_run(world, cases, mode, read_planes):
+    """The sequence of T.mid_run_state through one chain object in overlap `mode`.  read_planes: the four target planes of every frame where the shade writes them (a host
+    synchronisation per frame, to read them); otherwise every frame's out_ldr, the frames queued without a host synchronisation, as an application queues them."""
+    from diligentfx_amd import api
+
+    chain = api.Chain(0, *blue_noise_tables())
+    chain.set_overlap(mode)
+    outs, before = [], None
+    for i in range(T.MID_RUN_FRAMES):
+        targets, count, k, second = state = T.mid_run_state(i)
+        case = cases[1 if second else 0]
+        if before is None or state[:3] != before[:3]:
+            if not targets:
+                chain.set_transparency(None)
+                chain.set_shade_output(None, False)
+            else:
+                chain.set_shade_output(None, True)
+                chain.set_transparency(case.slices[:count], k)
+        before = state
+        out = torch.zeros(case.h, case.w, 4, device=chain.device)
+        chain.execute(chain.bind_frame(i, case.f[i], world["ibl"], case.sa, out))
+        if read_planes:
+            torch.cuda.synchronize()
+            outs.append({p: chain.shade_target(p).clone() for p in PLANES} if targets else None)
+        else:
+            outs.append(out)
+    torch.cuda.synchronize()
+    chain.close()
+    return outs
+
+
+def test_chain_switches_in_the_middle_of_a_run(world):
+    """One chain object through transparency on (frame 2), one slice instead of two (3), another layer_count (4: the OIT object is destroyed and re-created), transparency
+    off (5), the shade output off (6), a resize from 24x16 to 33x17 (7) and everything back on (8), in overlap modes 0, 3, 4 and 5.  Wherever the shade writes its targets
+    they equal the public entries run outside the chain for that frame's state -- those do not depend on history -- and, the ten frames queued without a host
+    synchronisation, the final images of modes 3, 4 and 5 equal one stream's, bit for bit."""
+    from diligentfx_amd import api
+
+    cases = [FeatureCase(world, 24, 16, frames=T.MID_RUN_FRAMES, rich=False), FeatureCase(world, 33, 17, frames=T.MID_RUN_FRAMES, rich=False)]
+    planes = {mode: _mid_run(world, cases, mode, True) for mode in (0, 3, 4, 5)}
+    images = {mode: _mid_run(world, cases, mode, False) for mode in (0, 3, 4, 5)}
+    oits = {}
+    for i in range(T.MID_RUN_FRAMES):
+        targets, count, k, second = T.mid_run_state(i)
+        case = cases[1 if second else 0]
+        if targets:
+            oit = oits.setdefault((case.w, k), api.OITResources(world["ctx"], case.w, case.h, k))
+            _, want = case.entries(i, oit, count=count)
+        for mode in (0, 3, 4, 5):
+            if targets:
+                for p in PLANES:
+                    assert torch.equal(planes[mode][i][p].view(torch.int32), want[p].view(torch.int32)), (mode, i, p)
+            assert torch.equal(images[mode][i].view(torch.int32), images[0][i].view(torch.int32)), (mode, i, "out_ldr against one stream")
+    assert not torch.equal(images[0][4], images[0][5]) and float((images[0][4] - images[0][5]).abs().max()) > 1e-3  # (the switches are in the picture)
+    for oit in oits.values():
+        oit.close()

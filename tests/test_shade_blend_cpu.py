@@ -347,43 +347,7 @@ def test_native_storage_build_has_the_symbols():
     assert b"NOT_IMPLEMENTED" in lib.mifx_status_string(rc).upper().replace(b" ", b"_"), (rc, lib.mifx_status_string(rc))
 
 
-def test_the_host_only_build_refuses_the_entry_by_the_launchers_name():
-    """tests/cpu_product links the product's host sources without the device objects: its launcher stand-ins are those of mifx_host.h / mifx_*_host.h, which this launcher
-    is not part of, so nothing installs it (csrc/mifx_oit_shade_launch.h) and the entry answers MIFX_ERR_NOT_IMPLEMENTED with launch_oit_shade_blend in the message --
-    after its own argument checks, which still run.  (A process of its own: the build carries a stand-in for the HIP runtime.)"""
-    import importlib.util
-    import sys
-
-    spec = importlib.util.spec_from_file_location("_cpu_product_build", os.path.join(HERE, "cpu_product", "build.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    lib = m.build()
-    if lib is None:
-        pytest.skip("hipcc not available")
-    code = (
-        "import ctypes, sys\n"
-        "sys.path[:0] = [%r, %r]\n"
-        "import test_shade_blend_cpu as T\n"
-        "lib = ctypes.CDLL(%r)\n"
-        "lib.mifx_last_error.restype = ctypes.c_char_p\n"
-        "lib.mifx_status_string.restype = ctypes.c_char_p\n"
-        "a = T.Args()\n"
-        "a.camera.fNearPlaneDepth, a.camera.fFarPlaneDepth = 1.0, 0.0\n"
-        "rc, err = a.call(lib)\n"
-        "assert rc == -1 and 'reversed depth disagrees' in err, (rc, err)\n"
-        "a.flags = 1\n"
-        "rc, err = a.call(lib)\n"
-        "print(rc, lib.mifx_status_string(rc).decode(), '|', err)\n" % (ROOT, HERE, lib))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "launch_oit_shade_blend" in r.stdout and "NOT_IMPLEMENTED" in r.stdout.upper().replace(" ", "_"), r.stdout
-
-
-def test_the_library_has_the_launcher_installed(mifx_lib, args):
-    """... and libmifx.so has it: the accepted call of the `args` fixture went through the launcher's own checks (a bad IBL is refused by them, not by a missing launcher)"""
-    args.pre.mip_count = 0
-    rc, err = args.call(mifx_lib)
-    assert rc == -1 and "prefiltered" in err and "launch_oit_shade_blend" not in err
+# (The launcher is one of the host-only build's stand-ins, tests/cpu_product: tests/test_cpu_product.py::test_the_host_only_build_runs_the_shade_blend_entry runs the entry there.)
 
 
 # ------------------------------------------------------------------------------------------------ the same source under the sanitizers, as a program of its own
