@@ -30,7 +30,7 @@ mifx_chain::~mifx_chain()
     if (lane_h) (void)hipStreamDestroy(lane_h);
     mifx::chain_detach_comm(this);
     mifx_selection_destroy(selection);
-    mifx_oit_destroy(oit);
+    mifx_oit_destroy(shade.oit);
     mifx_autoexposure_destroy(auto_exposure);
     mifx_bloom_destroy(bloom);
     mifx_dof_destroy(dof);
@@ -96,7 +96,7 @@ mifx_status mifx_chain_get_effect(mifx_chain* chain, const char* name, void** ou
     else if (n == "bloom") *out = chain->bloom;
     else if (n == "dof") *out = chain->dof; // NULL until mifx_chain_set_depth_of_field enabled it
     else if (n == "selection") *out = chain->selection; // NULL until mifx_chain_set_selection turned it on
-    else if (n == "oit") *out = chain->oit;             // NULL until a frame ran with mifx_chain_set_transparency on
+    else if (n == "oit") *out = chain->shade.oit;       // NULL until a frame ran with mifx_chain_set_transparency on
     else
     {
         set_error("mifx_chain_get_effect: unknown effect '%s'", name);
@@ -125,78 +125,76 @@ static bool g_transparency_fusion = true;
 // blended in submission order -- one launch per slice, or (fusion off) the layered shade into the chain's two slice planes and mifx_oit_blend.
 static mifx_status chain_transparency(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* radiance)
 {
-    mifx_postfx*            ctx     = chain->ctx;
-    const uint32_t          n       = uint32_t(chain->transparent.size());
-    const mifx_pbr_shadows* shadows = chain->has_shadows ? &chain->shadows : nullptr;
-    const mifx_oit_targets  tg{radiance, &chain->target_desc[1], &chain->target_desc[2], &chain->target_desc[3]};
-    const mifx_image2d      rad = chain->slice_radiance.desc(), spec = chain->slice_specular_ibl.desc();
+    mifx_chain::ShadeStage& sh = chain->shade;
+    const uint32_t          n  = uint32_t(sh.transparent.size());
+    const mifx_oit_targets  tg = sh.oit_targets(radiance);
+    const mifx_image2d      rad = sh.slice_radiance.desc(), spec = sh.slice_specular_ibl.desc();
     mifx_oit_slice          slices[MIFX_OIT_MAX_SLICES];
     for (uint32_t i = 0; i < n; ++i)
     {
-        const mifx_transparent_slice& s = chain->transparent[i].s;
+        const mifx_transparent_slice& s = sh.transparent[i].s;
         // (the two shaded planes exist in the unfused path only, and only mifx_oit_blend reads them)
         slices[i] = mifx_oit_slice{s.gbuffer.depth, s.gbuffer.base_color, s.gbuffer.material, g_transparency_fusion ? nullptr : &rad, g_transparency_fusion ? nullptr : &spec, s.color_alpha};
     }
-    MIFX_CHECK(mifx_oit_build_layers(chain->oit, slices, n, f->gbuffer.depth, f->curr_camera));
-    MIFX_CHECK(mifx_oit_apply_attenuation(chain->oit, &tg));
-    const mifx_pbr_layers none{};
-    const float           zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    MIFX_CHECK(mifx_oit_build_layers(sh.oit, slices, n, f->gbuffer.depth, f->curr_camera));
+    MIFX_CHECK(mifx_oit_apply_attenuation(sh.oit, &tg));
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (uint32_t i = 0; i < n; ++i)
     {
-        const mifx_transparent_slice& s = chain->transparent[i].s;
+        const mifx_transparent_slice& s = sh.transparent[i].s;
         if (g_transparency_fusion)
         {
-            MIFX_CHECK(mifx_oit_shade_blend(chain->oit, &s, f->gbuffer.depth, f->curr_camera, f->pbr, f->ibl, shadows, &tg));
+            MIFX_CHECK(mifx_oit_shade_blend(sh.oit, &s, f->gbuffer.depth, f->curr_camera, f->pbr, f->ibl, sh.shadows(), &tg));
             continue;
         }
-        MIFX_CHECK(mifx_pbr_shade_execute_layers(ctx, &s.gbuffer, s.layers ? s.layers : &none, f->curr_camera, f->pbr, f->ibl, shadows, zero, &rad, &spec));
-        MIFX_CHECK(mifx_oit_blend(chain->oit, &slices[i], f->gbuffer.depth, f->curr_camera, &tg));
+        MIFX_CHECK(mifx_pbr_shade_execute_layers(chain->ctx, &s.gbuffer, &sh.transparent[i].layers.v, f->curr_camera, f->pbr, f->ibl, sh.shadows(), zero, &rad, &spec));
+        MIFX_CHECK(mifx_oit_blend(sh.oit, &slices[i], f->gbuffer.depth, f->curr_camera, &tg));
     }
     return MIFX_OK;
 }
 
-// The forward shade of the unsharded frame.  With fuse_ssr_mask the kernel also writes SSR's roughness / reflection-mask planes (pass R2 reads the same material
-// and depth texels and nothing else): mifx_ssr_execute then finds them done for this frame.
-// With a row band the shade runs on the rows of the composite; the by-product is needed on the rows of the ray march, a few rows more: the shade then covers
-// those (+3 % of its rows against a pass over the material and depth planes).
+// Which shade the frame takes, decided here alone from the chain and the frame: the shade, the sharded frame's hit fetch and the choice of the planes behind the shade ask here or
+// ask the stage (mifx_chain::ShadeStage).  Plain: mifx_pbr_shade_execute; PlainWithMask: with SSR's roughness / reflection-mask planes as a by-product (fuse_ssr_mask: pass R2
+// reads the same material and depth texels and nothing else); Layered: mifx_chain_set_material_layers (no by-product: SSR runs R2 itself); Output: mifx_chain_set_shade_output, to
+// the end of the pixel shader's `main` (no by-product either); OutputTargets: and the USD footer's four targets, which the passes behind the shade then read, with the transparent draws
+enum class Shade { Plain, PlainWithMask, Layered, Output, OutputTargets };
+static Shade chain_shade_kind(const mifx_chain* chain, const mifx_chain_frame* f)
+{
+    const mifx_chain::ShadeStage& sh = chain->shade;
+    if (sh.output_stage()) return sh.targets_on ? Shade::OutputTargets : Shade::Output;
+    if (sh.layers().flags != 0u || sh.shadows() != nullptr) return Shade::Layered;
+    return !chain->fuse_ssr_mask || f->ssr->RoughnessChannel > 3u ? Shade::Plain : Shade::PlainWithMask;
+}
+
+// The forward shade of the frame.  With a row band the shade runs on the rows of the composite; the R2 by-product is needed on the rows of the ray march, a few rows
+// more: the shade then covers those (+3 % of its rows against a pass over the material and depth planes), and mifx_ssr_execute finds the planes done for this frame.
 static mifx_status chain_shade(mifx_chain* chain, const mifx_chain_frame* f, const mifx_image2d* radiance, const mifx_image2d* spec)
 {
-    mifx_postfx* ctx = chain->ctx;
-    mifx_ssr*    ssr = chain->ssr;
-    if (chain->has_shade_output) // mifx_chain_set_shade_output: the shade to the end of the pixel shader's `main` (no R2 by-product either); absent layers = the empty set
+    mifx_postfx*            ctx  = chain->ctx;
+    mifx_ssr*               ssr  = chain->ssr;
+    mifx_chain::ShadeStage& sh   = chain->shade;
+    const Shade             kind = chain_shade_kind(chain, f);
+    const int               H    = int(radiance->height);
+    const bool              wide = kind == Shade::PlainWithMask && !ctx->band.empty(); // (the by-product on the rows of the ray march)
+    sh.shaded_rows  = wide ? mifx_ssr::march_rows(*f->ssr, ctx->needed_rows(H), H, (chain->ssr_flags & MIFX_SSR_FEATURE_FLAG_HALF_RESOLUTION) != 0) : ctx->needed_rows(H);
+    sh.shaded_frame = f->frame.Index;
+    switch (kind)
     {
-        chain->shaded_rows  = ctx->needed_rows(int(radiance->height));
-        chain->shaded_frame = f->frame.Index;
-        const mifx_pbr_layers*            layers  = chain->has_layers ? &chain->layers : nullptr;
-        const mifx_pbr_shadows*           shadows = chain->has_shadows ? &chain->shadows : nullptr;
-        const mifx_pbr_shade_output_desc* desc    = chain->has_output_desc ? &chain->output_desc : nullptr;
-        if (!chain->write_targets) return mifx_pbr_shade_output(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, spec);
-        const mifx_pbr_targets tg{&chain->target_desc[0], &chain->target_desc[1], &chain->target_desc[2], &chain->target_desc[3]}; // (`spec` is target_desc[3]: chain_frame_planes)
-        MIFX_CHECK(mifx_pbr_shade_targets(ctx, &f->gbuffer, layers, f->curr_camera, f->pbr, f->ibl, shadows, desc, f->background, radiance, &tg));
-        return chain->transparent.empty() ? MIFX_OK : chain_transparency(chain, f, radiance);
+    case Shade::Plain: return mifx_pbr_shade_execute(ctx, &f->gbuffer, f->curr_camera, f->pbr, f->ibl, f->background, radiance, spec);
+    case Shade::Layered: return mifx_pbr_shade_execute_layers(ctx, &f->gbuffer, &sh.layers(), f->curr_camera, f->pbr, f->ibl, sh.shadows(), f->background, radiance, spec);
+    case Shade::Output: return mifx_pbr_shade_output(ctx, &f->gbuffer, &sh.layers(), f->curr_camera, f->pbr, f->ibl, sh.shadows(), sh.output_desc(), f->background, radiance, spec);
+    case Shade::OutputTargets:
+    {
+        const mifx_pbr_targets tg = sh.pbr_targets(); // (`spec` is the IBL target: chain_frame_planes)
+        MIFX_CHECK(mifx_pbr_shade_targets(ctx, &f->gbuffer, &sh.layers(), f->curr_camera, f->pbr, f->ibl, sh.shadows(), sh.output_desc(), f->background, radiance, &tg));
+        return sh.transparent.empty() ? MIFX_OK : chain_transparency(chain, f, radiance);
     }
-    if (chain->has_layers || chain->has_shadows) // mifx_chain_set_material_layers: the layered kernel (no R2 by-product: SSR runs the pass itself)
-    {
-        const mifx_pbr_layers none{};
-        chain->shaded_rows  = ctx->needed_rows(int(radiance->height));
-        chain->shaded_frame = f->frame.Index;
-        return mifx_pbr_shade_execute_layers(ctx, &f->gbuffer, chain->has_layers ? &chain->layers : &none, f->curr_camera, f->pbr, f->ibl, chain->has_shadows ? &chain->shadows : nullptr,
-                                             f->background, radiance, spec);
-    }
-    if (!chain->fuse_ssr_mask || f->ssr->RoughnessChannel > 3u)
-    {
-        chain->shaded_rows  = ctx->needed_rows(int(radiance->height));
-        chain->shaded_frame = f->frame.Index;
-        return mifx_pbr_shade_execute(ctx, &f->gbuffer, f->curr_camera, f->pbr, f->ibl, f->background, radiance, spec);
+    case Shade::PlainWithMask: break;
     }
     MIFX_HIP_CHECK(hipSetDevice(ctx->device));
-    const int  H    = int(radiance->height);
-    const Rows rows = ctx->band.empty() ? ctx->needed_rows(H) : mifx_ssr::march_rows(*f->ssr, ctx->needed_rows(H), H, (chain->ssr_flags & MIFX_SSR_FEATURE_FLAG_HALF_RESOLUTION) != 0);
-    chain->shaded_rows  = rows;
-    chain->shaded_frame = f->frame.Index;
     SsrMaskOut r2{ssr->roughness.view(), ssr->mask.view(), f->ssr->RoughnessThreshold, f->ssr->IsRoughnessPerceptual, f->ssr->RoughnessChannel, 1};
     MifxKernelTimer timer(ctx, "pbr_shade_ssr_mask_kernel"); // (includes the two cube-apron launches of the call)
-    MIFX_CHECK(launch_pbr_shade(ctx->stream, ctx->ibl_apron, &f->gbuffer, *f->curr_camera, *f->pbr, f->ibl, f->background, radiance, spec, rows.b, rows.e,
+    MIFX_CHECK(launch_pbr_shade(ctx->stream, ctx->ibl_apron, &f->gbuffer, *f->curr_camera, *f->pbr, f->ibl, f->background, radiance, spec, sh.shaded_rows.b, sh.shaded_rows.e,
                                 (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, nullptr, &r2));
     ssr->mask_provided_for = f->frame.Index;
     return MIFX_OK;
@@ -238,7 +236,7 @@ struct ChainGBuffer
 };
 static ChainGBuffer chain_gbuffer(const mifx_chain* chain, const mifx_chain_frame* f)
 {
-    if (chain->has_shade_output && chain->write_targets) return {&chain->target_desc[0], &chain->target_desc[1], &chain->target_desc[2]};
+    if (chain_shade_kind(chain, f) == Shade::OutputTargets) return {&chain->shade.target_desc[0], &chain->shade.target_desc[1], &chain->shade.target_desc[2]};
     return {f->gbuffer.normal, f->gbuffer.base_color, f->gbuffer.material};
 }
 // The chain's colour planes of this frame: radiance, the composite's specular IBL (the IBL target with targets on), the composite
@@ -248,10 +246,9 @@ struct ChainPlanes
 };
 static ChainPlanes chain_frame_planes(mifx_chain* chain)
 {
-    const bool targets = chain->has_shade_output && chain->write_targets;
-    if (targets)
-        for (int i = 0; i < 4; ++i) chain->target_desc[i] = chain->targets[i].desc();
-    return {chain->radiance.desc(), targets ? chain->target_desc[3] : chain->specular_ibl.desc(), chain->composite.desc()};
+    mifx_chain::ShadeStage& sh = chain->shade;
+    if (sh.targets_on) sh.frame_targets();
+    return {chain->radiance.desc(), sh.targets_on ? sh.target_desc[3] : chain->specular_ibl.desc(), chain->composite.desc()};
 }
 
 // The composite draw (HnPostProcess.psh:145-185).  With fuse_ssr_cleanup the kernel evaluates SSR's last pass (R7, the bilateral cleanup) for its own pixel from the
@@ -367,27 +364,28 @@ extern "C++" mifx_status mifx::chain_prepare_resources(mifx_chain* chain, const 
     MIFX_CHECK(chain->radiance.alloc(W, H, MIFX_FORMAT_F32X4));
     MIFX_CHECK(chain->specular_ibl.alloc(W, H, MIFX_FORMAT_F32X4));
     MIFX_CHECK(chain->composite.alloc(W, H, MIFX_FORMAT_F32X4));
-    if (chain->has_shade_output && chain->write_targets)
-        for (mifx::Plane& p : chain->targets) MIFX_CHECK(p.alloc(W, H, MIFX_FORMAT_F32X4)); // (once per size; freed with the chain)
-    if (!chain->transparent.empty())
+    mifx_chain::ShadeStage& sh = chain->shade;
+    if (sh.targets_on)
+        for (mifx::Plane& p : sh.targets) MIFX_CHECK(p.alloc(W, H, MIFX_FORMAT_F32X4)); // (once per size; freed with the chain)
+    if (!sh.transparent.empty())
     {
         // every refusal of the frame's transparent draws before its first launch: the planes of every slice against the frame's size, what mifx_oit_shade_blend refuses
-        MIFX_REQUIRE(chain->has_shade_output && chain->write_targets && chain->band.empty(),
-                     "mifx_chain_execute: transparency needs mifx_chain_set_shade_output with write_targets and no row band");
-        const mifx_image2d     planes[4] = {chain->radiance.desc(), chain->targets[1].desc(), chain->targets[2].desc(), chain->targets[3].desc()};
-        const mifx_oit_targets tg{&planes[0], &planes[1], &planes[2], &planes[3]};
-        for (const mifx_chain::TransparentSlice& t : chain->transparent)
-            MIFX_CHECK(mifx_oit_shade_blend_check(W, H, ctx->flags, &t.s, f->gbuffer.depth, f->curr_camera, f->pbr, f->ibl, chain->has_shadows ? &chain->shadows : nullptr, &tg));
-        if (chain->oit == nullptr || chain->oit->w != W || chain->oit->h != H || chain->oit->K != chain->oit_layer_count)
+        MIFX_REQUIRE(sh.targets_on && chain->band.empty(), "mifx_chain_execute: transparency needs mifx_chain_set_shade_output with write_targets and no row band");
+        sh.frame_targets();
+        const mifx_image2d     radiance = chain->radiance.desc();
+        const mifx_oit_targets tg       = sh.oit_targets(&radiance);
+        for (const mifx::KeptTransparentSlice& t : sh.transparent)
+            MIFX_CHECK(mifx_oit_shade_blend_check(W, H, ctx->flags, &t.s, f->gbuffer.depth, f->curr_camera, f->pbr, f->ibl, sh.shadows(), &tg));
+        if (sh.oit == nullptr || sh.oit->w != W || sh.oit->h != H || sh.oit->K != sh.oit_layer_count)
         {
-            mifx_oit_destroy(chain->oit); // (hipFree waits for the kernels that still read it)
-            chain->oit = nullptr;
-            MIFX_CHECK(mifx_oit_create(ctx, W, H, chain->oit_layer_count, &chain->oit));
+            mifx_oit_destroy(sh.oit); // (hipFree waits for the kernels that still read it)
+            sh.oit = nullptr;
+            MIFX_CHECK(mifx_oit_create(ctx, W, H, sh.oit_layer_count, &sh.oit));
         }
         if (!g_transparency_fusion)
         {
-            MIFX_CHECK(chain->slice_radiance.alloc(W, H, MIFX_FORMAT_F32X4));
-            MIFX_CHECK(chain->slice_specular_ibl.alloc(W, H, MIFX_FORMAT_F32X4));
+            MIFX_CHECK(sh.slice_radiance.alloc(W, H, MIFX_FORMAT_F32X4));
+            MIFX_CHECK(sh.slice_specular_ibl.alloc(W, H, MIFX_FORMAT_F32X4));
         }
     }
     return MIFX_OK;
@@ -474,8 +472,8 @@ static void chain_swap_shadow(mifx_chain* chain)
     mifx_chain::Shadow& sh = chain->shadow;
     chain->radiance.swap(sh.radiance);
     chain->specular_ibl.swap(sh.specular_ibl);
-    if (chain->has_shade_output && chain->write_targets)
-        for (int i = 0; i < 4; ++i) chain->targets[i].swap(sh.targets[i]);
+    if (chain->shade.targets_on)
+        for (int i = 0; i < 4; ++i) chain->shade.targets[i].swap(sh.targets[i]);
     ctx->reproj_depth.swap(sh.reproj_depth);
     ctx->closest_motion.swap(sh.closest_motion);
     ctx->noise_xy.swap(sh.noise_xy);
@@ -494,8 +492,8 @@ static mifx_status chain_prepare_shadow(mifx_chain* chain)
     mifx_chain::Shadow& sh = chain->shadow;
     MIFX_CHECK(sh.radiance.alloc_like(chain->radiance));
     MIFX_CHECK(sh.specular_ibl.alloc_like(chain->specular_ibl));
-    if (chain->has_shade_output && chain->write_targets)
-        for (int i = 0; i < 4; ++i) MIFX_CHECK(sh.targets[i].alloc_like(chain->targets[i]));
+    if (chain->shade.targets_on)
+        for (int i = 0; i < 4; ++i) MIFX_CHECK(sh.targets[i].alloc_like(chain->shade.targets[i]));
     MIFX_CHECK(sh.reproj_depth.alloc_like(ctx->reproj_depth));
     MIFX_CHECK(sh.closest_motion.alloc_like(ctx->closest_motion));
     MIFX_CHECK(sh.noise_xy.alloc_like(ctx->noise_xy));
@@ -645,7 +643,7 @@ static mifx_status chain_execute_impl(mifx_chain* chain, const mifx_chain_frame*
         // (only while nothing else was queued on the context stream in between -- a reset's or a re-allocating prepare's history fills, an import: chain_lanes_continue)
         MIFX_CHECK(chain_fork_lanes(chain, {{chain->side, chain->evPrepConsumed}}, chain->overlap >= 2));
         // (with the shade's targets on, SSAO reads the normal target: the shade is then queued first and SSAO waits for it; prep still runs beside it)
-        const bool ssao_reads_shade = chain->has_shade_output && chain->write_targets;
+        const bool ssao_reads_shade = chain_shade_kind(chain, f) == Shade::OutputTargets;
         if (ssao_reads_shade)
         {
             MIFX_CHECK(chain_shade(chain, f, &radiance, &spec));
@@ -765,7 +763,7 @@ ShardRows shard_rows(const mifx_chain* chain, const mifx_chain_frame* f, Rows ba
 extern "C" mifx_status mifx_chain_set_row_band(mifx_chain* chain, int32_t row_begin, int32_t row_end, int32_t max_motion_rows)
 {
     MIFX_REQUIRE(chain != nullptr && row_begin >= 0 && row_end >= row_begin && max_motion_rows >= 0, "mifx_chain_set_row_band: bad argument");
-    MIFX_REQUIRE(row_end == row_begin || !chain->has_shade_output,
+    MIFX_REQUIRE(row_end == row_begin || !chain->shade.output_stage(),
                  "mifx_chain_set_row_band: a row band (or sharding) is not combined with mifx_chain_set_shade_output: the sharded hit fetch has no output stage or footer");
     chain->band       = Rows{row_begin, row_end}; // {0, 0} switches sharding off
     chain->max_motion = max_motion_rows;
@@ -791,7 +789,7 @@ extern "C++" mifx_status mifx::chain_execute_phase(mifx_chain* chain, const mifx
 {
     MIFX_REQUIRE(chain != nullptr && f != nullptr && out_ldr != nullptr && phase >= 0 && phase <= 4, "mifx_chain_execute_phase: bad argument");
     MIFX_REQUIRE(!chain->band.empty(), "mifx_chain_execute_phase: no row band set (mifx_chain_set_row_band)");
-    MIFX_REQUIRE(!chain->has_shade_output, "mifx_chain_execute_phase: a row band is not combined with mifx_chain_set_shade_output (the sharded hit fetch has no output stage or footer)");
+    MIFX_REQUIRE(!chain->shade.output_stage(), "mifx_chain_execute_phase: a row band is not combined with mifx_chain_set_shade_output (the sharded hit fetch has no output stage or footer)");
     MIFX_CHECK(chain_check_frame(f, "mifx_chain_execute_phase"));
     mifx_postfx* ctx = chain->ctx;
     if (phase == 0) MIFX_CHECK(mifx::chain_prepare_resources(chain, f));
@@ -835,26 +833,23 @@ extern "C++" mifx_status mifx::chain_execute_phase(mifx_chain* chain, const mifx
         ctx->need = r.comp;
         // No exchange of the shaded radiance: the ray march records where every ray hit, and the hit fetch loads the colour from the rows this rank shaded in
         // phase 0 or shades the hit pixel itself (the G-buffer and the IBL maps are whole on every rank; same kernel body, bit-identical colour).
-        if (chain->shaded_rows.empty() || chain->shaded_frame != f->frame.Index)
+        if (chain->shade.shaded_rows.empty() || chain->shade.shaded_frame != f->frame.Index)
         {
             set_error("mifx_chain_execute_phase: phase 2 of frame %u before its phase 0 (the hit fetch needs the rows that phase shaded)", f->frame.Index);
             return MIFX_ERR_INVALID_OP;
         }
         mifx_ssr::Request ssr_req{chain->fuse_ssr_cleanup, req.hiz_stream, req.hiz_done};
-        ssr_req.after_trace = [chain, f, ctx, radiance](Img rays, Img coords) -> mifx_status {
+        ssr_req.after_trace = [chain, f, ctx, radiance, kind = chain_shade_kind(chain, f)](Img rays, Img coords) -> mifx_status {
+            const mifx_chain::ShadeStage& sh       = chain->shade;
+            const bool                    reversed = (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0;
             MIFX_HIP_CHECK(hipSetDevice(ctx->device));
             MifxKernelTimer timer(ctx, "pbr_hit_fetch_kernel");
-            if (chain->has_layers || chain->has_shadows) // the frame was shaded with mifx_chain_set_material_layers: the hit pixels take the same permutation
-            {
-                const mifx_pbr_layers none{};
-                const LayeredHitFetch hit{rays, coords, chain->shaded_rows.b, chain->shaded_rows.e};
-                return launch_pbr_shade_layers(ctx->stream, ctx->ibl_apron, &f->gbuffer, chain->has_layers ? chain->layers : none, *f->curr_camera, *f->pbr, f->ibl, f->background, &radiance,
-                                               nullptr, 0, 0, (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0, chain->has_shadows ? &chain->shadows : nullptr, &hit);
-            }
-            return launch_pbr_hit_fetch(ctx->stream, ctx->ibl_apron, &f->gbuffer, *f->curr_camera, *f->pbr, f->ibl, f->background, rays, coords, &radiance, chain->shaded_rows.b,
-                                        chain->shaded_rows.e, (ctx->flags & MIFX_POSTFX_FEATURE_FLAG_REVERSED_DEPTH) != 0);
+            if (kind != Shade::Layered) // (the hit pixels take the permutation that shaded the frame; a row band has no output stage)
+                return launch_pbr_hit_fetch(ctx->stream, ctx->ibl_apron, &f->gbuffer, *f->curr_camera, *f->pbr, f->ibl, f->background, rays, coords, &radiance, sh.shaded_rows.b, sh.shaded_rows.e, reversed);
+            const LayeredHitFetch hit{rays, coords, sh.shaded_rows.b, sh.shaded_rows.e};
+            return launch_pbr_shade_layers(ctx->stream, ctx->ibl_apron, &f->gbuffer, sh.layers(), *f->curr_camera, *f->pbr, f->ibl, f->background, &radiance, nullptr, 0, 0, reversed, sh.shadows(), &hit);
         };
-        ssr_req.hit_local_rows = chain->shaded_rows; // (R4 loads the colour of a hit in these rows itself; only the others go through the fetch)
+        ssr_req.hit_local_rows = chain->shade.shaded_rows; // (R4 loads the colour of a hit in these rows itself; only the others go through the fetch)
         MIFX_CHECK(chain->ssr->run(&sr, ssr_req));
         if (req.wait_before_composite) MIFX_HIP_CHECK(hipStreamWaitEvent(ctx->stream, req.wait_before_composite, 0)); // (the end of SSAO on its lane)
         CompositeHandOver hand;
@@ -1021,29 +1016,8 @@ mifx_status mifx_chain_set_material_layers(mifx_chain* chain, const mifx_pbr_lay
     if (shadows != nullptr)
         MIFX_REQUIRE(shadows->shadow_map != nullptr && shadows->shadow_map_count <= MIFX_PBR_MAX_SHADOW_MAPS && (shadows->shadow_map_count == 0 || shadows->shadow_maps != nullptr),
                      "mifx_chain_set_material_layers: bad shadows block");
-    chain->has_layers = chain->has_shadows = false;
-    if (layers != nullptr && layers->flags != 0u)
-    {
-        chain->layers = *layers;
-        const mifx_image2d** slot[9] = {&chain->layers.clearcoat, &chain->layers.clearcoat_normal, &chain->layers.sheen, &chain->layers.anisotropy, &chain->layers.tangent,
-                                        &chain->layers.iridescence, &chain->layers.transmission, &chain->layers.sheen_albedo_scaling_lut, &chain->layers.preintegrated_charlie};
-        for (int i = 0; i < 9; ++i)
-            if (*slot[i] != nullptr)
-            {
-                chain->layer_images[i] = **slot[i];
-                *slot[i] = &chain->layer_images[i];
-            }
-        chain->has_layers = true;
-    }
-    if (shadows != nullptr)
-    {
-        chain->shadows      = *shadows;
-        chain->shadow_array = *shadows->shadow_map;
-        for (uint32_t i = 0; i < shadows->shadow_map_count; ++i) chain->shadow_infos[i] = shadows->shadow_maps[i];
-        chain->shadows.shadow_map  = &chain->shadow_array;
-        chain->shadows.shadow_maps = chain->shadow_infos;
-        chain->has_shadows = true;
-    }
+    chain->shade.kept_layers.keep(layers != nullptr && layers->flags != 0u ? layers : nullptr);
+    chain->shade.kept_shadows.keep(shadows);
     return MIFX_OK;
 }
 
@@ -1063,7 +1037,7 @@ mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_
     const bool on = output != nullptr || write_targets != 0;
     MIFX_REQUIRE(!on || chain->band.empty(),
                  "mifx_chain_set_shade_output: not combined with a row band or sharding (mifx_chain_set_row_band / _set_sharding): the sharded hit fetch has no output stage or footer");
-    MIFX_REQUIRE(write_targets != 0 || chain->transparent.empty(),
+    MIFX_REQUIRE(write_targets != 0 || chain->shade.transparent.empty(),
                  "mifx_chain_set_shade_output: write_targets goes off while mifx_chain_set_transparency is on: the transparent draws blend into the chain's own target planes "
                  "(turn transparency off first)");
 #ifdef MIFX_STORAGE_H4
@@ -1073,22 +1047,8 @@ mifx_status mifx_chain_set_shade_output(mifx_chain* chain, const mifx_pbr_shade_
         return MIFX_ERR_NOT_IMPLEMENTED;
     }
 #endif
-    chain->has_shade_output = on;
-    chain->has_output_desc  = output != nullptr;
-    chain->write_targets    = write_targets != 0;
-    if (output != nullptr)
-    {
-        chain->output_desc          = *output;
-        chain->output_renderer      = *output->renderer;
-        chain->output_desc.renderer = &chain->output_renderer;
-        const mifx_image2d** slot[2] = {&chain->output_desc.motion, &chain->output_desc.mesh_normal};
-        for (int i = 0; i < 2; ++i)
-            if (*slot[i] != nullptr)
-            {
-                chain->output_images[i] = **slot[i];
-                *slot[i] = &chain->output_images[i];
-            }
-    }
+    chain->shade.kept_output.keep(output);
+    chain->shade.targets_on = write_targets != 0;
     chain->prep_consumed = false; // (which planes the lanes trade and read changes: the next frame forks from the context stream once)
     return MIFX_OK;
 }
@@ -1100,7 +1060,7 @@ mifx_status mifx_chain_set_transparency(mifx_chain* chain, uint32_t layer_count,
     MIFX_REQUIRE(chain != nullptr, "%s: null chain", who);
     if (slices == nullptr || count == 0u) // off: the chain launches what it launched before
     {
-        chain->transparent.clear();
+        chain->shade.transparent.clear();
         return MIFX_OK;
     }
 #ifdef MIFX_STORAGE_H4
@@ -1110,7 +1070,7 @@ mifx_status mifx_chain_set_transparency(mifx_chain* chain, uint32_t layer_count,
 #else
     MIFX_REQUIRE(count <= uint32_t(MIFX_OIT_MAX_SLICES), "%s: %u slices are more than MIFX_OIT_MAX_SLICES (%d)", who, count, MIFX_OIT_MAX_SLICES);
     MIFX_CHECK(mifx_oit_create_check(1u, 1u, layer_count));
-    MIFX_REQUIRE(chain->has_shade_output && chain->write_targets,
+    MIFX_REQUIRE(chain->shade.targets_on,
                  "%s: needs mifx_chain_set_shade_output with write_targets: the transparent draws blend into the chain's own BaseColor / Material / IBL planes (without "
                  "them base colour and material are the caller's const planes)", who);
     // (a row band needs no check of its own: mifx_chain_set_shade_output and mifx_chain_set_row_band refuse each other, in either order)
@@ -1120,39 +1080,10 @@ mifx_status mifx_chain_set_transparency(mifx_chain* chain, uint32_t layer_count,
         MIFX_REQUIRE(g.base_color != nullptr && g.normal != nullptr && g.material != nullptr && g.depth != nullptr, "%s: slice %u: base_color, normal, material and depth must not be null",
                      who, i);
     }
-    std::vector<mifx_chain::TransparentSlice> copy(count);
-    for (uint32_t i = 0; i < count; ++i) // (the vector has its final size: the pointers below stay good until the next call)
-    {
-        mifx_chain::TransparentSlice& t = copy[i];
-        t.s = slices[i];
-        const mifx_image2d** plane[6] = {&t.s.gbuffer.base_color, &t.s.gbuffer.normal, &t.s.gbuffer.material, &t.s.gbuffer.depth, &t.s.gbuffer.emissive, &t.s.gbuffer.occlusion};
-        for (int j = 0; j < 6; ++j)
-            if (*plane[j] != nullptr)
-            {
-                t.gbuffer_images[j] = **plane[j];
-                *plane[j] = &t.gbuffer_images[j];
-            }
-        if (t.s.color_alpha != nullptr)
-        {
-            t.alpha = *t.s.color_alpha;
-            t.s.color_alpha = &t.alpha;
-        }
-        if (t.s.layers != nullptr)
-        {
-            t.layers = *t.s.layers;
-            t.s.layers = &t.layers;
-            const mifx_image2d** slot[9] = {&t.layers.clearcoat, &t.layers.clearcoat_normal, &t.layers.sheen, &t.layers.anisotropy, &t.layers.tangent,
-                                            &t.layers.iridescence, &t.layers.transmission, &t.layers.sheen_albedo_scaling_lut, &t.layers.preintegrated_charlie};
-            for (int j = 0; j < 9; ++j)
-                if (*slot[j] != nullptr)
-                {
-                    t.layer_images[j] = **slot[j];
-                    *slot[j] = &t.layer_images[j];
-                }
-        }
-    }
-    chain->transparent.swap(copy);
-    chain->oit_layer_count = layer_count;
+    std::vector<mifx::KeptTransparentSlice> copy(count);
+    for (uint32_t i = 0; i < count; ++i) copy[i].keep(slices[i]);
+    chain->shade.transparent.swap(copy);
+    chain->shade.oit_layer_count = layer_count;
     return MIFX_OK;
 #endif
 }
@@ -1171,9 +1102,9 @@ mifx_status mifx_chain_get_shade_target(mifx_chain* chain, const char* name, mif
     for (int i = 0; i < 4; ++i)
         if (std::string(name) == names[i])
         {
-            MIFX_REQUIRE(chain->has_shade_output && chain->write_targets && chain->targets[i].data != nullptr,
+            MIFX_REQUIRE(chain->shade.targets_on && chain->shade.targets[i].data != nullptr,
                          "mifx_chain_get_shade_target: no '%s' target (mifx_chain_set_shade_output with write_targets, and a frame executed)", name);
-            *out = chain->targets[i].desc();
+            *out = chain->shade.targets[i].desc();
             return MIFX_OK;
         }
     set_error("mifx_chain_get_shade_target: unknown target '%s' (normal, base_color, material, ibl)", name);

@@ -397,6 +397,74 @@ struct mifx_oit // == PBR_Renderer::CreateOITResources (api_oit.cpp)
     ~mifx_oit() { if (layers) (void)hipFree(layers); }
 };
 
+namespace mifx
+{
+// How the chain keeps a caller's descriptors beyond the call: a copy of the pointer struct, and keep_images re-aims each image pointer that is set at a copy of the
+// descriptor in `store` (one slot per pointer, in order), so that only the device planes stay borrowed.  The holders below point into themselves: they are neither
+// copied nor moved (a std::vector of them is made with its size and swapped).
+inline void keep_images(std::initializer_list<const mifx_image2d**> slots, mifx_image2d* store)
+{
+    for (const mifx_image2d** slot : slots)
+    {
+        if (*slot != nullptr) *slot = &(*store = **slot);
+        ++store;
+    }
+}
+struct Pinned { Pinned() = default; Pinned(const Pinned&) = delete; Pinned& operator=(const Pinned&) = delete; };
+struct KeptLayers : Pinned
+{
+    mifx_pbr_layers v{}; // (nothing kept: the empty set)
+    mifx_image2d    images[9]{};
+    void keep(const mifx_pbr_layers* src)
+    {
+        v = src ? *src : mifx_pbr_layers{};
+        keep_images({&v.clearcoat, &v.clearcoat_normal, &v.sheen, &v.anisotropy, &v.tangent, &v.iridescence, &v.transmission, &v.sheen_albedo_scaling_lut, &v.preintegrated_charlie}, images);
+    }
+};
+struct KeptShadows : Pinned
+{
+    mifx_pbr_shadows         v{}; // (nothing kept: no shadow map)
+    mifx_shadow_map_array    array{};
+    mifx_pbr_shadow_map_info infos[MIFX_PBR_MAX_SHADOW_MAPS]{};
+    void keep(const mifx_pbr_shadows* src)
+    {
+        v = src ? *src : mifx_pbr_shadows{};
+        if (src == nullptr) return;
+        array = *src->shadow_map;
+        for (uint32_t i = 0; i < src->shadow_map_count; ++i) infos[i] = src->shadow_maps[i];
+        v.shadow_map  = &array;
+        v.shadow_maps = infos;
+    }
+};
+struct KeptOutputDesc : Pinned
+{
+    mifx_pbr_shade_output_desc          v{}; // (nothing kept: no renderer block)
+    mifx_pbr_renderer_shader_parameters renderer{};
+    mifx_image2d                        images[2]{};
+    void keep(const mifx_pbr_shade_output_desc* src)
+    {
+        v = src ? *src : mifx_pbr_shade_output_desc{};
+        if (src == nullptr) return;
+        renderer   = *src->renderer;
+        v.renderer = &renderer;
+        keep_images({&v.motion, &v.mesh_normal}, images);
+    }
+};
+struct KeptTransparentSlice : Pinned
+{
+    mifx_transparent_slice s{};
+    mifx_image2d           images[7]{};
+    KeptLayers             layers; // (a slice without layers: the empty set, for the unfused path's layered shade)
+    void keep(const mifx_transparent_slice& src)
+    {
+        s = src;
+        keep_images({&s.gbuffer.base_color, &s.gbuffer.normal, &s.gbuffer.material, &s.gbuffer.depth, &s.gbuffer.emissive, &s.gbuffer.occlusion, &s.color_alpha}, images);
+        layers.keep(src.layers);
+        if (src.layers != nullptr) s.layers = &layers.v;
+    }
+};
+} // namespace mifx
+
 struct mifx_chain
 {
     mifx_postfx* ctx   = nullptr;
@@ -405,8 +473,6 @@ struct mifx_chain
     mifx_taa*    taa   = nullptr;
     mifx_bloom*  bloom = nullptr;
     mifx::Plane  radiance, specular_ibl, composite;
-    mifx::Rows   shaded_rows{0, 0}; // rows of `radiance` the last shade of this chain wrote (row-band sharding: what the SSR hit fetch may load instead of shading)
-    uint32_t     shaded_frame = ~0u; // ... and the frame index of that shade
     bool         profiling = false, timed = false;
     hipEvent_t   ev[MIFX_CHAIN_STAGE_COUNT + 1] = {};
     // PostFX prep + SSAO do not depend on the shaded radiance: they run on a second stream beside PBR shade + SSR (fork / join with events)
@@ -415,37 +481,38 @@ struct mifx_chain
     mifx_dof*    dof = nullptr;            // optional (mifx_chain_set_depth_of_field): between TAA and Bloom, HnPostProcessTask.cpp:899-909
     mifx_dof_attribs dof_attribs{};
     uint32_t     dof_flags = 0;
-    // mifx_chain_set_material_layers: deep copies (descriptors included), so that only the device planes are borrowed
-    bool                     has_layers = false, has_shadows = false;
-    mifx_pbr_layers          layers{};
-    mifx_image2d             layer_images[9]{};
-    mifx_pbr_shadows         shadows{};
-    mifx_shadow_map_array    shadow_array{};
-    mifx_pbr_shadow_map_info shadow_infos[MIFX_PBR_MAX_SHADOW_MAPS]{};
-    // mifx_chain_set_shade_output: the shade is mifx_pbr_shade_output / mifx_pbr_shade_targets (deep copies of the desc and its renderer block; the motion / mesh-normal
-    // planes are borrowed).  With write_targets the chain owns the footer's four planes, and every pass behind the shade reads them in place of gbuffer.normal / .base_color /
-    // .material and of the specular-IBL plane (target_desc: this frame's descriptors, set at the start of every frame -- the planes trade places with `shadow` in modes 4, 5).
-    bool                                has_shade_output = false, has_output_desc = false, write_targets = false;
-    mifx_pbr_shade_output_desc          output_desc{};
-    mifx_pbr_renderer_shader_parameters output_renderer{};
-    mifx_image2d                        output_images[2]{};
-    mifx::Plane                         targets[4]; // normal, base colour, material, IBL
-    mifx_image2d                        target_desc[4]{};
-    hipEvent_t                          evShade = nullptr; // overlap 1, 2 with targets: SSAO on the side stream reads the normal target the shade writes
-    // mifx_chain_set_transparency: the transparent draws of the frame, blended into the colour and the BaseColor / Material / IBL targets inside the shade stage (chain_shade).
-    // Deep copies (descriptors and layers included), so that only the device planes are borrowed; `oit` is created or re-created per frame size and layer count
-    // (chain_prepare_resources).  The layers, the tail and the two planes of the unfused path exist once: they are written and consumed inside the shade stage, which is
-    // one stream in every overlap mode ("Transparency in the chain").
-    struct TransparentSlice
+    // The frame's shade stage (api_chain.cpp: chain_shade): what mifx_chain_set_material_layers, _set_shade_output and _set_transparency keep, the planes the stage owns and
+    // what its last run wrote.  The frame asks it the questions below and nothing else; which of the five shades a frame takes is chain_shade_kind's one decision.
+    struct ShadeStage
     {
-        mifx_transparent_slice s{};
-        mifx_image2d           gbuffer_images[6]{}, layer_images[9]{}, alpha{};
-        mifx_pbr_layers        layers{};
-    };
-    std::vector<TransparentSlice> transparent; // empty = off
-    uint32_t                      oit_layer_count = 0;
-    mifx_oit*                     oit = nullptr;
-    mifx::Plane                   slice_radiance, slice_specular_ibl; // mifx_chain_set_transparency_fusion(0): a slice's shade, reused slice after slice
+        mifx::KeptLayers  kept_layers;  // mifx_chain_set_material_layers (a set without a flag is the empty set)
+        mifx::KeptShadows kept_shadows;
+        // mifx_chain_set_shade_output: the shade is mifx_pbr_shade_output / mifx_pbr_shade_targets (the motion / mesh-normal planes are borrowed), on with a desc, with the
+        // targets or with both.  With the targets the chain owns the footer's four planes, and every pass behind the shade reads them in place of gbuffer.normal / .base_color /
+        // .material and of the specular-IBL plane (target_desc: this frame's descriptors, frame_targets() -- the planes trade places with `shadow` in modes 4, 5).
+        mifx::KeptOutputDesc kept_output;
+        bool                 targets_on = false;
+        mifx::Plane          targets[4]; // normal, base colour, material, IBL
+        mifx_image2d         target_desc[4]{};
+        // mifx_chain_set_transparency: the transparent draws of the frame, blended into the colour and the BaseColor / Material / IBL targets inside the stage.  `oit` is
+        // created or re-created per frame size and layer count (chain_prepare_resources).  The layers, the tail and the two planes of the unfused path exist once: they are
+        // written and consumed inside the stage, which is one stream in every overlap mode ("Transparency in the chain").
+        std::vector<mifx::KeptTransparentSlice> transparent; // empty = off
+        uint32_t                                oit_layer_count = 0;
+        mifx_oit*                               oit = nullptr;
+        mifx::Plane                             slice_radiance, slice_specular_ibl; // mifx_chain_set_transparency_fusion(0): a slice's shade, reused slice after slice
+        mifx::Rows shaded_rows{0, 0}; // rows of `radiance` the last shade of this chain wrote (row-band sharding: what the SSR hit fetch may load instead of shading)
+        uint32_t   shaded_frame = ~0u; // ... and the frame index of that shade
+
+        bool                              output_stage() const { return output_desc() != nullptr || targets_on; }
+        const mifx_pbr_layers&            layers() const { return kept_layers.v; } // (off: the empty set)
+        const mifx_pbr_shadows*           shadows() const { return kept_shadows.v.shadow_map ? &kept_shadows.v : nullptr; }
+        const mifx_pbr_shade_output_desc* output_desc() const { return kept_output.v.renderer ? &kept_output.v : nullptr; }
+        void frame_targets() { for (int i = 0; i < 4; ++i) target_desc[i] = targets[i].desc(); } // the planes as they are now (allocated; traded with the shadow set)
+        mifx_pbr_targets pbr_targets() const { return {&target_desc[0], &target_desc[1], &target_desc[2], &target_desc[3]}; }
+        mifx_oit_targets oit_targets(const mifx_image2d* radiance) const { return {radiance, &target_desc[1], &target_desc[2], &target_desc[3]}; }
+    } shade;
+    hipEvent_t evShade = nullptr; // overlap 1, 2 with targets: SSAO on the side stream reads the normal target the shade writes
     // mifx_chain_set_selection: the jump flood + the selection composite in place of the composite (api_selection.cpp); the attribs and the
     // image descriptor are copies, the selection depth plane is borrowed
     bool                   has_selection = false;

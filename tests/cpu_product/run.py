@@ -601,8 +601,8 @@ def event_trace():
 
 def trace_configurations(lib):
     """What run.py `trace` runs: (name, function of a CallTrace) for every frame path of the chain -- mifx_chain_execute in every stream mode with the default fusions, all and
-    none (reset_history before frame 4: the lanes fork again; depth of field on for one mask per mode; modes 4 and 5 once more with lane edges), mifx_chain_execute_band,
-    mifx_chain_execute_sharded over the in-library group (per rank), and the synchronous five-plane exchange with the luminance gather, with and without Bloom's level-0 halos."""
+    none (reset_history before frame 4: the lanes fork again; depth of field on for one mask per mode; modes 4 and 5 once more with lane edges), mifx_chain_execute_band, the shade stage's
+    features (CONFIGS a, b, c, e in modes 0, 2, 5), mifx_chain_execute_sharded over the in-library group (per rank), and the synchronous five-plane exchange with the luminance gather, with and without Bloom's level-0 halos."""
     import order as O
 
     rt_type = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)
@@ -630,6 +630,12 @@ def trace_configurations(lib):
         out.append((f"execute, overlap {m}, lane edges", lambda t, m=m: order_run(lib, m, 31, track=t, reset_at=4, edges=edges)))
     for m in (0, 2, 3):
         out.append((f"execute_band (20, 44), overlap {m}", lambda t, m=m: order_run(lib, m, 31, band=(20, 44), track=t)))
+    # the shade stage's features (CONFIGS of order_features): one stream, the two streams where SSAO waits for the shade's targets (evShade), the deepest lanes
+    for name in "abce":
+        for m in (0, 2, 5):
+            out.append((f"execute, shade features {name} ({CONFIG_NAMES[name]}), overlap {m}", lambda t, m=m, name=name: order_run(lib, m, 31, frames=5, dof=name == "e", track=t, cfg=CONFIGS[name])))
+    # (not here: mifx_chain_execute_band with layers and shadows on -- the layered hit fetch.  device.py runs launch_pbr_shade_layers for unsharded frames only and refuses
+    #  the launch with a hit list; tests/test_gpu_sharded.py, case "layers", runs it on the device)
     for case in range(len(GROUP_CASES)):
         out.append((f"execute_sharded, group case {case} {GROUP_CASES[case]}", lambda t, case=case: group(t, case, {})))
     sync = {"MIFX_SHARD_ASYNC_HALOS": "0"}
