@@ -39,7 +39,7 @@ HIPCC_FLAGS = [
 # ssao.hip / ssr_temporal.hip as well gains 2 % more on those kernels but pushes SSAO end-to-end and the SSR per-pass cases over their outlier budgets
 # (history-rejection thresholds), and whole-file fusion of the march (ssr_trace.hip), R5 (ssr.hip) and A3 (ssao_ao.hip) moves rays / taps: those stay strict
 # and fuse only the expressions that carry an explicit __builtin_fmaf / MIFX_FMA_BLOCK.
-# Round 4: NONE by default.  The contraction of pbr.hip / taa.hip / composite.hip (and the fused multiply-adds of SSR's march step, ssr_trace.hip MIFX_R4_FUSED_MARCH) bought
+# Round 4: NONE by default.  The contraction of pbr.hip / taa.hip / composite.hip (and hand-fused multiply-adds in SSR's march step, ssr_trace.hip) bought
 # 1.0 % of the 4K frame (1.721 -> 1.740 ms, 1.724 -> 1.733 ms, two A/B pairs on one box: profiles/r04_ab_nofma_vs_fast.txt) and cost every value-level deviation the parity
 # suite could still see per pass: with it 2.5e-4 of the shade's radiance values, 1.6e-4 .. 8.7e-4 of TAA's (by flag set) and 1.4e-3 of the ray march's differ from the
 # reference by more than 1e-3; without it not one value of any per-pass comparison of the shade, TAA, R4, R5, R7, Bloom, SSAO A3 .. A8 or depth of field does

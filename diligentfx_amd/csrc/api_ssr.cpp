@@ -35,9 +35,6 @@ mifx_status mifx_ssr_create(mifx_postfx* ctx, mifx_ssr** out)
     (*out)->ctx = ctx;
     if (const char* e = std::getenv("MIFX_SSR_DIRECT_LEVEL0")) (*out)->direct_level0 = std::atoi(e) < 0 ? -1 : std::atoi(e) > 0 ? 1 : 0; // (A/B runs; default -1: row bands only)
     if (const char* e = std::getenv("MIFX_SSR_CLEAN_TILES")) (*out)->clean_tiles = std::atoi(e) != 0; // (A/B runs; read here once, never per frame)
-#if defined(MIFX_R4_TWO_RAYS) && MIFX_R4_TWO_RAYS
-    (*out)->clean_tiles = false; // the two-rays-per-lane experiment kernel (ssr_trace.hip) always clears
-#endif
     return MIFX_OK;
 }
 void mifx_ssr_destroy(mifx_ssr* fx) { delete fx; }
@@ -45,9 +42,6 @@ void mifx_ssr_destroy(mifx_ssr* fx) { delete fx; }
 mifx_status mifx_debug_ssr_set_clean_tiles(mifx_ssr* fx, int32_t enable)
 {
     MIFX_REQUIRE(fx != nullptr, "mifx_debug_ssr_set_clean_tiles: null argument");
-#if defined(MIFX_R4_TWO_RAYS) && MIFX_R4_TWO_RAYS
-    enable = 0;
-#endif
     // (the words go stale while the march always clears: the next launch that uses them rebuilds them)
     fx->clean_tiles      = enable != 0;
     fx->tile_flags_valid = false;

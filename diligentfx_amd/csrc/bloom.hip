@@ -30,7 +30,6 @@ template <int TW, int TH, bool BORDER, class TAG = v4, class LT = v4> struct Til
     // Round 5: all of a thread's texels are requested before the first is written.  The fill used to be a loop of  load - wait - write  per texel (one load in flight:
     // tools/isa_roundtrips.py), i.e. seven dependent round trips for the 72 x 24 tile of B1 / B2 in front of the barrier -- on kernels whose whole life is ~ten.
     // NT = the block's thread count (32 x 8); a thread's surplus slots repeat its first texel (no branch between the loads) and are not written.
-#ifndef MIFX_BLOOM_FILL_ROLLED
     template <int NT = 256> MIFX_D void fill() const
     {
         constexpr int N = (TW * TH + NT - 1) / NT;
@@ -54,20 +53,6 @@ template <int TW, int TH, bool BORDER, class TAG = v4, class LT = v4> struct Til
             if (i < TW * TH) lds[i] = to_lds((!border || (gx >= 0 && gy >= 0 && gx < im.w && gy < im.h)) ? v[k] : mk4(0.0f), static_cast<const LT*>(nullptr));
         }
     }
-#else
-    MIFX_D void fill() const // (the form of rounds 1-4, for A/B builds)
-    {
-        const int tid = threadIdx.y * blockDim.x + threadIdx.x, nthreads = blockDim.x * blockDim.y;
-        for (int i = tid; i < TW * TH; i += nthreads)
-        {
-            const int tx = i % TW, ty = i / TW, gx = x0 + tx, gy = y0 + ty;
-            v4 v = mk4(0.0f);
-            if (border) { if (gx >= 0 && gy >= 0 && gx < im.w && gy < im.h) v = ld<TAG>(im, gx, gy); }
-            else v = ld<TAG>(im, clampi(gx, 0, im.w - 1), clampi(gy, 0, im.h - 1));
-            lds[i] = to_lds(v, static_cast<const LT*>(nullptr));
-        }
-    }
-#endif
     static MIFX_D v4 to_lds(v4 v, const v4*) { return v; }
     static MIFX_D v3 to_lds(v4 v, const v3*) { return xyz(v); }
     static MIFX_D v4 from_lds(v4 v) { return v; }

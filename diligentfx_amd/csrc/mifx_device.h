@@ -15,15 +15,6 @@ namespace mifx
 // minimum waves per SIMD the register allocator must leave room for (caps VGPRs at 512 / n): straight-line filter kernels otherwise hoist
 // all their taps into registers and drop to 2-3 waves per SIMD, too few to hide the load latency
 #define MIFX_WAVES(n) __attribute__((amdgpu_waves_per_eu(n)))
-#define MIFX_WAVES_OPT_0
-#define MIFX_WAVES_OPT_3 MIFX_WAVES(3)
-#define MIFX_WAVES_OPT_4 MIFX_WAVES(4)
-#define MIFX_WAVES_OPT_5 MIFX_WAVES(5)
-#define MIFX_WAVES_OPT_6 MIFX_WAVES(6)
-#define MIFX_WAVES_OPT_7 MIFX_WAVES(7)
-#define MIFX_WAVES_OPT_8 MIFX_WAVES(8)
-#define MIFX_WAVES_CAT(n) MIFX_WAVES_OPT_##n
-#define MIFX_WAVES_OPT(n) MIFX_WAVES_CAT(n) // experiment knob: MIFX_WAVES_OPT(0) = no hint
 // Weighted sums of fetched texels (filter taps) may fuse each multiply-add: one rounding instead of two, half the instructions.  Only for
 // smooth accumulations whose result does not steer addressing or thresholds; everything else keeps the reference's separate mul / add.
 #define MIFX_FMA_BLOCK _Pragma("clang fp contract(fast)")
@@ -491,17 +482,14 @@ MIFX_D float depth16(float v, int on)
 template <class T> MIFX_D typename Stored<T>::value ld(const Img& im, int x, int y) { return GlobalAccess<T>::load(im.p + size_t(y) * im.pitch + size_t(x) * TexelBytes<T>::value); }
 template <class T> MIFX_D void st(const Img& im, int x, int y, typename Stored<T>::value v) { GlobalAccess<T>::store(im.p + size_t(y) * im.pitch + size_t(x) * TexelBytes<T>::value, v); }
 // A texel that is read ONCE in the whole launch (the thread's own texel of a plane nobody else touches): loaded with the non-temporal hint, so that the line is not kept in
-// the L2 in front of lines that will be asked for again (-DMIFX_NT_LOADS=0: plain loads, for A/B builds).  Planes that neighbouring threads read as well -- filter taps,
+// the L2 in front of lines that will be asked for again.  Planes that neighbouring threads read as well -- filter taps,
 // bilinear footprints, tiles -- keep plain loads: with the hint on the history taps of TAA and R6 (planes those passes are the last readers of) TAA takes 268.7 instead of 162.3 us
 // and R6 116.8 instead of 98.8 -- the neighbours' re-reads of a line miss.
-#ifndef MIFX_NT_LOADS
-#define MIFX_NT_LOADS 1
-#endif
 template <class T> struct StreamAccess
 {
     static MIFX_D typename Stored<T>::value load(const unsigned char* p) { return GlobalAccess<T>::load(p); }
 };
-#if defined(__HIP_DEVICE_COMPILE__) && MIFX_NT_LOADS
+#if defined(__HIP_DEVICE_COMPILE__)
 template <> struct StreamAccess<float>
 {
     static MIFX_D float load(const unsigned char* p) { return __builtin_nontemporal_load((const MIFX_GLOBAL float*)p); }
@@ -557,42 +545,12 @@ template <class T = v2> MIFX_D v2 ld_zero_v2(const Img& im, int x, int y) { retu
 // (An XCD-contiguous remap of the workgroup index -- XCD k <- the k-th eighth of the image -- was measured and rejected: +35 % on R4 and
 //  +20 % on A3, because the work per block is very uneven (sky / masked-out regions) and the round-robin placement balances it.  Round 3: the balanced
 //  form of the same idea -- super-blocks of 16 x 8 workgroups, every XCD walks its own 4 x 4 chunk (128 x 32 pixels) of each -- is +3.5 % on R4 and +9 % on
-//  A3 (profiles/r03_ab_xcd_chunks.txt): the L2s are not what these kernels wait for.)
+//  A3 (profiles/r03_ab_xcd_chunks.txt): the L2s are not what these kernels wait for.  Round 6: XCD k serving the k-th eighth of every tile row, a contiguous column
+//  block per L2 -- R4 309.1 -> 343.5 us, A3 unmoved, the third form of this idea and the third loss: profiles/r06_ab_xcd_columns.txt.)
 MIFX_D bool tiled_xy(const Img& out, int& x, int& y) // false: outside the image / the row window of `out`
 {
     const int t = threadIdx.x, lane = t & 63;
     x = int(blockIdx.x) * int(blockDim.x >> 3) + (t >> 6) * 8 + (lane & 7); // (256 threads: 32 pixels per block row; 64 threads: one 8x8 tile per block)
-    y = int(blockIdx.y) * 8 + (lane >> 3) + out.y0;
-    return x < out.w && y < row_end(out);
-}
-// EXPERIMENT (round 6, -DMIFX_XCD_COLUMNS=1; R4 and A3 only): the workgroups of a grid row go to the eight XCDs round-robin (workgroup i of a row whose length is a multiple
-// of eight runs on XCD i % 8), so with the plain mapping every XCD -- every L2 -- serves 32-pixel columns spread over the whole width.  Here XCD k gets the k-th eighth of every
-// tile row instead: a contiguous column block per L2, all XCDs still walking down the image together (the vertical work profile -- sky above, reflective ground below -- is what
-// unbalanced the "k-th eighth of the image" of round 1, and the 128 x 32 chunks of round 3 kept an L2's tiles apart in both directions).  The launcher rounds the grid's x up to a
-// multiple of eight (xcd_grid_x); the tiles beyond the image fall out at the bounds test.
-// MEASURED AND NOT TAKEN (profiles/r06_ab_xcd_columns.txt): R4 309.1 -> 343.5 us, A3 209.8 -> 209.9 us, same box, bit-identical output.  A column block per XCD unbalances
-// the march as well (an eighth of the width is one or two spheres wide), and A3 does not notice where its L2 lines come from: the third form of this idea, the third loss.
-// (Also measured: the tile rows dispatched from the last to the first -- the reflective ground before the sky -- R4 310.1 -> 316.7 us, A3 209.1 -> 205.9 us: nothing.)
-#ifndef MIFX_XCD_COLUMNS
-#define MIFX_XCD_COLUMNS 0
-#endif
-MIFX_D bool tiled_xy_xcd(const Img& out, int& x, int& y)
-{
-#if MIFX_XCD_COLUMNS
-    const int t = threadIdx.x, lane = t & 63;
-    const int perXcd = int(gridDim.x) >> 3, b = int(blockIdx.x), bx = (b & 7) * perXcd + (b >> 3);
-    x = bx * int(blockDim.x >> 3) + (t >> 6) * 8 + (lane & 7);
-    y = int(blockIdx.y) * 8 + (lane >> 3) + out.y0;
-    return x < out.w && y < row_end(out);
-#else
-    return tiled_xy(out, x, y);
-#endif
-}
-MIFX_HD unsigned xcd_grid_x(unsigned gx) { return MIFX_XCD_COLUMNS ? (gx + 7u) / 8u * 8u : gx; }
-MIFX_D bool tiled_xy_at(const Img& out, int bx, int& x, int& y) // the same with the workgroup's column given (a grid whose workgroups do not all compute pixels)
-{
-    const int t = threadIdx.x, lane = t & 63;
-    x = bx * int(blockDim.x >> 3) + (t >> 6) * 8 + (lane & 7);
     y = int(blockIdx.y) * 8 + (lane >> 3) + out.y0;
     return x < out.w && y < row_end(out);
 }

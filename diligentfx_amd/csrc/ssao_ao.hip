@@ -3,9 +3,6 @@
 // Shaders/PostProcess/ScreenSpaceAmbientOcclusion/private/SSAO_*.fx; the host sequence is in api_ssao.cpp.
 //
 // All planes are fp32 (AO, history length, depth).  Bandwidth accounting per pass: SURVEY.md Appendix C.
-#include <cstdlib>
-#include <cstring>
-
 #include "mifx_host.h"
 #include "mifx_effects.h"
 
@@ -110,47 +107,10 @@ MIFX_D float fast_acos_q(float v)
 #ifndef MIFX_A3_WAVES
 #define MIFX_A3_WAVES 7
 #endif
-#ifdef MIFX_A3_CAP // experiment knob: at most this many waves per SIMD
-#define MIFX_A3_OCC __attribute__((amdgpu_waves_per_eu(MIFX_A3_CAP, MIFX_A3_CAP)))
-#else
-#define MIFX_A3_OCC MIFX_WAVES(MIFX_A3_WAVES)
-#endif
-// EXPERIMENT (round 6, MIFX_A3_COPY_ROLE=k; never the shipped launch): the verdict's question "does the dispatcher refuse to mix two grids on a CU, or is the mixed CU
-// slower?" needs ONE grid whose workgroups alternate roles.  ROLES = true: of every k + 1 consecutive workgroups of a block row, k run A3 and one streams its share of
-// `copy.bytes` from copy.src to copy.dst, 16 bytes per lane and access (the composite's traffic: tools/exp_a3_copy_role.py times the mixed grid against A3 and the copy
-// alone).  The A3 role's arithmetic and tap order are those of the shipped kernel (same body).
-struct CopyRole
+// (Round 6, measured and not taken: one grid whose workgroups alternate between this kernel and a streaming copy -- does mixing a gather kernel and a streaming kernel on a
+//  CU hide anything?  10 % at best: profiles/r06_exp_a3_copy_role.txt.)
+template <int ALGO> __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_A3_WAVES) void ssao_compute_ao_kernel(Pyr depthPyr, HizSlab camzSlab, Img normal, Img noiseZW, Img out, CamK cam, SsaoK k)
 {
-    const mifx_f4* src;
-    mifx_f4*       dst;
-    unsigned     perBlock; // 16-byte elements each copy workgroup moves (a multiple of 256 x MIFX_A3_COPY_DEPTH)
-    unsigned     k;        // A3 workgroups per copy workgroup
-    unsigned     copiesPerRow;
-};
-template <int ALGO, bool ROLES = false> __global__ __launch_bounds__(256) MIFX_A3_OCC void ssao_compute_ao_kernel(Pyr depthPyr, HizSlab camzSlab, Img normal, Img noiseZW, Img out, CamK cam, SsaoK k, CopyRole copy)
-{
-    int bx = int(blockIdx.x);
-    if (ROLES)
-    {
-        const unsigned q = blockIdx.x / (copy.k + 1u), r = blockIdx.x - q * (copy.k + 1u);
-        if (r == copy.k)
-        {
-            const size_t base = (size_t(blockIdx.y) * copy.copiesPerRow + q) * copy.perBlock + threadIdx.x;
-#ifndef MIFX_A3_COPY_DEPTH
-#define MIFX_A3_COPY_DEPTH 8 // independent 16-byte loads in flight per lane: 8 KB per wave (4: the first version of the experiment)
-#endif
-            for (unsigned i = 0; i < copy.perBlock; i += 256u * MIFX_A3_COPY_DEPTH)
-            {
-                mifx_f4 v[MIFX_A3_COPY_DEPTH];
-#pragma unroll
-                for (int j = 0; j < MIFX_A3_COPY_DEPTH; ++j) v[j] = __builtin_nontemporal_load(copy.src + base + i + 256u * unsigned(j));
-#pragma unroll
-                for (int j = 0; j < MIFX_A3_COPY_DEPTH; ++j) __builtin_nontemporal_store(v[j], copy.dst + base + i + 256u * unsigned(j));
-            }
-            return;
-        }
-        bx = int(q * copy.k + r);
-    }
     // taps read the camera-z pyramid (A2 writes depth_to_camera_z of every level beside the depth pyramid): one division less per tap
     __shared__ CamzLevel camzLv[8];
     if (threadIdx.x < 8u)
@@ -163,8 +123,8 @@ template <int ALGO, bool ROLES = false> __global__ __launch_bounds__(256) MIFX_A
     const int levels = camzSlab.levels;
     const int t0BitsBiased = int(__float_as_uint(k.MipLenSq[0])) - (1 << 24);
     int x, y;
-    bool inside = ROLES ? tiled_xy_at(out, bx, x, y) : tiled_xy_xcd(out, x, y);
-    if (!ROLES && (MIFX_ROWS_UP & 1024)) // (experiment bit: the tile rows from the last to the first)
+    bool inside = tiled_xy(out, x, y);
+    if (MIFX_ROWS_UP & 1024) // A3's bit of MIFX_ROWS_UP (mifx_device.h), on in the shipped build: the tile rows from the last to the first
     {
         y      = int(gridDim.y - 1u - blockIdx.y) * 8 + (int(threadIdx.x & 63u) >> 3) + out.y0;
         inside = x < out.w && y < row_end(out);
@@ -196,30 +156,11 @@ template <int ALGO, bool ROLES = false> __global__ __launch_bounds__(256) MIFX_A
     if (cam.proj.m[15] == 0.0f) sampleRadius = fdiv(sampleRadius, positionVS.z); // perspective
 
     constexpr bool QUICK = ALGO != MIFX_SSAO_ALGORITHM_VBAO; // the bitmask variant thresholds its angles into 32 sectors: keep it strict
-#ifndef MIFX_A3_VGPR_SCALES
-#define MIFX_A3_VGPR_SCALES 0
-#endif
-#if MIFX_A3_VGPR_SCALES
-    // Round 6, MEASURED AND NOT TAKEN (profiles/r06_ab_a3_vgpr_scales.txt: 209.7 us with, 209.4 us without, same box, 60 frames).  A full-rate vector instruction with a
-    // scalar-register source issues at half rate in the microbenchmark (profiles/r03_valu_issue_rate.txt), and a slice of this loop holds 33 of them: the two projection
-    // scales of the taps' view-space reconstruction (the residual step of fdiv_finite, twelve per slice), the viewport size and the level threshold.  With all five values
-    // in vector registers (72 registers, still seven waves per SIMD, same operations on the same values) the loop's static issue cost drops from 649 to 625 units -- and the
-    // kernel does not move: what DESIGN.md section 7 listed as the last untried instruction-level item is worth nothing here.
-    m44 projV = cam.proj;
-    asm volatile("" : "+v"(projV.m[0]), "+v"(projV.m[5]));
-    float vwV = cam.vw, vhV = cam.vh; // (the tap's pixel offset, twice per sample)
-    int   t0V = t0BitsBiased;         // (the tap's level, once per sample)
-    asm volatile("" : "+v"(vwV), "+v"(vhV), "+v"(t0V));
-#else
-    const m44& projV = cam.proj;
-    const float vwV = cam.vw, vhV = cam.vh;
-    const int   t0V = t0BitsBiased;
-#endif
+    // (Round 6, measured and not taken: the five scalar-register operands of the tap loop -- the two projection scales, the viewport size, the level threshold -- held in
+    //  vector registers, because a full-rate vector instruction with a scalar source issues at half rate in the microbenchmark: 209.7 us with, 209.4 us without,
+    //  profiles/r06_ab_a3_vgpr_scales.txt.)
 
     float visibility = 0.0f;
-#ifdef MIFX_A3_UNROLL
-#pragma unroll
-#endif
     for (int slice = 0; slice < SSAO_SLICE_COUNT; ++slice)
     {
         // (Measured in round 3 and not taken: the three directions from one sine / cosine pair and two rotations by 60 degrees -- a third of the slice set-up, every parity
@@ -261,14 +202,14 @@ template <int ALGO, bool ROLES = false> __global__ __launch_bounds__(256) MIFX_A
             const v2    offset = sample * sample * sampleDir;
             const v2    p0{positionSS.x + offset.x, positionSS.y + offset.y};
             const v2    p1{positionSS.x - offset.x, positionSS.y - offset.y};
-            const v2    offPx{offset.x * vwV, offset.y * vhV};
-            const int   mip = tap_mip_offset(dot(offPx, offPx), t0V, levels);
+            const v2    offPx{offset.x * cam.vw, offset.y * cam.vh};
+            const int   mip = tap_mip_offset(dot(offPx, offPx), t0BitsBiased, levels);
             const float z0 = sample_prefiltered_depth(camz, mip, p0.x, p0.y), z1 = sample_prefiltered_depth(camz, mip, p1.x, p1.y);
             // (the reconstruction itself stays bit-exact: d = s - positionVS is a cancelling difference for nearby taps.  Measured in round 2: multiplying by the
             //  reciprocals of the two projection scales instead of dividing -- an equally accurate rounding -- moved 0.2-0.7 % of the AO texels by up to 1e-2: the
             //  horizon angle is acos of a cosine that approaches 1 for taps beside the centre, where one ulp of the position is amplified without bound.)
-            const v3 s0 = screen_xy_camz_to_view_space(p0.x, p0.y, z0, projV);
-            const v3 s1 = screen_xy_camz_to_view_space(p1.x, p1.y, z1, projV);
+            const v3 s0 = screen_xy_camz_to_view_space(p0.x, p0.y, z0, cam.proj);
+            const v3 s1 = screen_xy_camz_to_view_space(p1.x, p1.y, z1, cam.proj);
 
             if (ALGO == MIFX_SSAO_ALGORITHM_VBAO)
             {
@@ -320,10 +261,8 @@ static const dim3 kBlock(64, 4, 1);
 mifx_status launch_ssao_compute_ao(hipStream_t s, const Pyr& depthPyr, const Pyr& camzPyr, Img normal, Img noiseZW, Img out, const CamK& cam, const mifx_ssao_attribs& a,
                                    bool halfResolution, bool halfPrecisionDepth)
 {
-#ifndef MIFX_A3_BLOCK
-#define MIFX_A3_BLOCK 256 // (measured: 64-thread workgroups, one 8x8 tile each, are 15 % slower)
-#endif
-    const dim3 grid(xcd_grid_x((out.w + MIFX_A3_BLOCK / 8 - 1) / (MIFX_A3_BLOCK / 8)), (window_rows(out) + 7) / 8, 1), kTiled(MIFX_A3_BLOCK, 1, 1);
+    constexpr int kA3Block = 256; // (measured: 64-thread workgroups, one 8x8 tile each, are 15 % slower)
+    const dim3 grid((out.w + kA3Block / 8 - 1) / (kA3Block / 8), (window_rows(out) + 7) / 8, 1), kTiled(kA3Block, 1, 1);
     const SsaoK k = make_k(a, halfResolution, halfPrecisionDepth);
     // the levels of the camera-z pyramid as offsets from their lowest address (mifx_ssao allocates them as one slab)
     HizSlab camzSlab{};
@@ -347,45 +286,11 @@ mifx_status launch_ssao_compute_ao(hipStream_t s, const Pyr& depthPyr, const Pyr
         MIFX_REQUIRE(l.w < (1 << 24) && l.h < (1 << 24) && l.pitch < (1 << 24), "camera-z pyramid: level %d too large", i);
         camzSlab.offset[i] = uint32_t(l.p - lo); camzSlab.pitch[i] = uint32_t(l.pitch); camzSlab.w[i] = uint32_t(l.w); camzSlab.h[i] = uint32_t(l.h);
     }
-    static const unsigned ldsPad = occupancy_pad_from_env("MIFX_A3_LDS_PAD"); // experiment knob, see launch_ssr_intersection
-    const CopyRole none{};
-    if (const char* e = std::getenv("MIFX_A3_COPY_ROLE")) // EXPERIMENT (see CopyRole): "k" or "k:megabytes" -- one copy workgroup per k A3 workgroups moves `megabytes` (default 847 = the composite's traffic, read + write)
-    {
-        const unsigned kk = unsigned(std::atoi(e));
-        if (kk >= 1u && a.Algorithm == MIFX_SSAO_ALGORITHM_GTAO && MIFX_A3_BLOCK == 256)
-        {
-            const char*  colon = std::strchr(e, ':');
-            const double mb    = colon ? std::atof(colon + 1) : 847.0;
-            CopyRole c{};
-            c.k            = kk;
-            c.copiesPerRow = (grid.x + kk - 1u) / kk; // (a trailing partial group gets a copy workgroup as well; its missing A3 workgroups fall outside the image)
-            const size_t nCopy = size_t(c.copiesPerRow) * grid.y;
-            size_t per = size_t(mb * 0.5e6 / 16.0 / double(nCopy)); // 16-byte elements per copy workgroup (half of the traffic is read, half written)
-            per        = (per + 256u * MIFX_A3_COPY_DEPTH - 1u) / (256u * MIFX_A3_COPY_DEPTH) * (256u * MIFX_A3_COPY_DEPTH);
-            c.perBlock = unsigned(per);
-            static void*  scratch = nullptr;
-            static size_t scratchBytes = 0;
-            const size_t need = per * nCopy * 16u;
-            if (scratchBytes < 2u * need)
-            {
-                if (scratch) (void)hipFree(scratch);
-                MIFX_HIP_CHECK(hipMalloc(&scratch, 2u * need));
-                MIFX_HIP_CHECK(hipMemset(scratch, 0, 2u * need));
-                scratchBytes = 2u * need;
-            }
-            c.src = static_cast<const mifx_f4*>(scratch);
-            c.dst = reinterpret_cast<mifx_f4*>(static_cast<unsigned char*>(scratch) + need);
-            const dim3 g2(c.copiesPerRow * (kk + 1u), grid.y, 1);
-            hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_GTAO, true>), g2, kTiled, ldsPad, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k, c);
-            MIFX_HIP_CHECK(hipGetLastError());
-            return MIFX_OK;
-        }
-    }
     switch (a.Algorithm)
     {
-        case MIFX_SSAO_ALGORITHM_GTAO: hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_GTAO>), grid, kTiled, ldsPad, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k, none); break;
-        case MIFX_SSAO_ALGORITHM_HBAO: hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_HBAO>), grid, kTiled, ldsPad, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k, none); break;
-        case MIFX_SSAO_ALGORITHM_VBAO: hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_VBAO>), grid, kTiled, ldsPad, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k, none); break;
+        case MIFX_SSAO_ALGORITHM_GTAO: hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_GTAO>), grid, kTiled, 0, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k); break;
+        case MIFX_SSAO_ALGORITHM_HBAO: hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_HBAO>), grid, kTiled, 0, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k); break;
+        case MIFX_SSAO_ALGORITHM_VBAO: hipLaunchKernelGGL((ssao_compute_ao_kernel<MIFX_SSAO_ALGORITHM_VBAO>), grid, kTiled, 0, s, depthPyr, camzSlab, normal, noiseZW, out, cam, k); break;
         default: set_error("unknown SSAO algorithm %u", a.Algorithm); return MIFX_ERR_INVALID_ARG;
     }
     MIFX_HIP_CHECK(hipGetLastError());

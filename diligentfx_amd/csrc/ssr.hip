@@ -158,10 +158,7 @@ static constexpr float c_ssr_poisson[8][3] = {{-0.4706069f, -0.4427112f, +0.6461
 //  vector L1 serves one tag look-up per clock, a wave64 load whose lanes touch >= 16 lines holds it for 64 clocks, and this pass' 57 M look-ups per launch are 93 of its
 //  144 us.  Result: 180.3 us against 144.2 us (profiles/r04_ab_r5_window.txt) -- the fill, its barrier and five resident workgroups per CU cost more than the look-ups
 //  they replace; the L1 is busy 65 % of this pass, not its limit.)
-#ifndef MIFX_R5_WAVES
-#define MIFX_R5_WAVES 5
-#endif
-template <bool HALF> __global__ __launch_bounds__(256) MIFX_WAVES_OPT(MIFX_R5_WAVES) void ssr_spatial_kernel(Img roughnessTex, Img normalTex, Img depthTex, Img dirPdfTex, Img specTex, Img mask, Img outRad, Img outVar,
+template <bool HALF> __global__ __launch_bounds__(256) MIFX_WAVES(5) void ssr_spatial_kernel(Img roughnessTex, Img normalTex, Img depthTex, Img dirPdfTex, Img specTex, Img mask, Img outRad, Img outVar,
                                                           Img outDepth, CamK cam, SsrK k)
 {
     int x, y;
@@ -175,7 +172,7 @@ template <bool HALF> __global__ __launch_bounds__(256) MIFX_WAVES_OPT(MIFX_R5_WA
     // Memory-level parallelism (round 3): the pass is a chain of dependent round trips -- mask, then the pixel's own depth / normal / roughness, then eight taps whose
     // positions follow from the roughness -- and the counters show its waves parked on s_waitcnt for 62 % of their cycles (profiles/r03_pmc_sq_*: 20 % of the VALU
     // issue roof).  The eight taps used to be eight round trips of their own: each tap's loads were issued, waited for and consumed behind a branch before the next
-    // tap's addresses existed.  Now the roughness comes first, the tap positions follow from it alone, and the ray / colour texels of MIFX_R5_BATCH taps are in flight
+    // tap's addresses existed.  Now the roughness comes first, the tap positions follow from it alone, and the ray / colour texels of all eight taps are in flight
     // together (and beside the pixel's depth and normal) before anything is consumed; the taps are then accumulated in the reference's order with the same
     // arithmetic -- the "no ray" case is a select instead of a branch -- so every value is what it was.
     const float rough = ld<rough_t>(roughnessTex, x, y);
@@ -195,14 +192,11 @@ template <bool HALF> __global__ __launch_bounds__(256) MIFX_WAVES_OPT(MIFX_R5_WA
         tapX[s] = HALF ? clampi(int(0.5f * (floorf(pos.x) + radius * xi.x) + 0.5f), 0, int(0.5f * cam.vw) - 1) : clampi(int(pos.x + radius * xi.x), 0, W - 1);
         tapY[s] = HALF ? clampi(int(0.5f * (floorf(pos.y) + radius * xi.y) + 0.5f), 0, int(0.5f * cam.vh) - 1) : clampi(int(pos.y + radius * xi.y), 0, H - 1);
     }
-#ifndef MIFX_R5_BATCH
-#define MIFX_R5_BATCH 8
-#endif
-    v4 rayTexel[MIFX_R5_BATCH], colTexel[MIFX_R5_BATCH];
+    v4 rayTexel[8], colTexel[8];
 #pragma unroll
-    for (int s = 0; s < MIFX_R5_BATCH; ++s) rayTexel[s] = ld<v4>(dirPdfTex, tapX[s], tapY[s]);
+    for (int s = 0; s < 8; ++s) rayTexel[s] = ld<v4>(dirPdfTex, tapX[s], tapY[s]);
 #pragma unroll
-    for (int s = 0; s < MIFX_R5_BATCH; ++s) colTexel[s] = ld<v4>(specTex, tapX[s], tapY[s]);
+    for (int s = 0; s < 8; ++s) colTexel[s] = ld<v4>(specTex, tapX[s], tapY[s]);
 
     const v3 camPos{cam.pos[0], cam.pos[1], cam.pos[2]};
     const v3 posWS  = inv_project_position(v3{pos.x * cam.ivw, pos.y * cam.ivh, depth}, cam.viewProjInv);
@@ -216,16 +210,9 @@ template <bool HALF> __global__ __launch_bounds__(256) MIFX_WAVES_OPT(MIFX_R5_WA
 #pragma unroll
     for (int s = 0; s < 8; ++s)
     {
-        if (MIFX_R5_BATCH < 8 && s > 0 && s % MIFX_R5_BATCH == 0) // (the next batch, when a batch holds fewer than eight taps)
-        {
-#pragma unroll
-            for (int t = 0; t < MIFX_R5_BATCH && s + t < 8; ++t) rayTexel[t] = ld<v4>(dirPdfTex, tapX[s + t], tapY[s + t]);
-#pragma unroll
-            for (int t = 0; t < MIFX_R5_BATCH && s + t < 8; ++t) colTexel[t] = ld<v4>(specTex, tapX[s + t], tapY[s + t]);
-        }
         const float ws = spatial_weight_const(c_ssr_poisson[s][2] * c_ssr_poisson[s][2], 0.9f);
         // ComputeWeightRayLength :60-88
-        const v4    dp  = rayTexel[s % MIFX_R5_BATCH];
+        const v4    dp  = rayTexel[s];
         const float len = length(xyz(dp));
         const bool  ray = !(len < 1e-6f);
         float wgt, rayLen;
@@ -242,7 +229,7 @@ template <bool HALF> __global__ __launch_bounds__(256) MIFX_WAVES_OPT(MIFX_R5_WA
             wgt    = ray ? fmaxf(brdf * q_rcp(fmaxf(dp.w, 1e-5f)), 1e-6f) : 1e-6f; // (no ray in the texel: the arithmetic above ran on a zero direction and is discarded)
             rayLen = ray ? len : 1e-6f;
         }
-        const v4 c = colTexel[s % MIFX_R5_BATCH];
+        const v4 c = colTexel[s];
         // ComputeWeightedVariance :90-100
         colorSum  = colorSum + wgt * c;
         weightSum += wgt;

@@ -57,9 +57,8 @@ MIFX_D v3 sdr_to_hdr(v3 c) { return c * (mk3(1.0f) / (mk3(1.0f) - c + mk3(5.9604
 //   3. a non-finite previous-depth tap: no difference here -- the nine taps feed comparisons only (depthFactor is 0 or 1 whatever they hold), as the
 //      reference's max() over them feeds one.
 // Measured, with the registers, the shares and the all-zero-motion case: profiles/taa_history_skip_ab.txt.
-// Measured and not taken (MIFX_TAA_SKIP_DISOCCLUDED): the same exit for a pixel with a motion factor but no similar previous depth (depthFactor = 0).  It makes the
-// 20 history taps of everybody else wait for the depth compare -- a fourth dependent round trip -- to spare the few pixels the first exit leaves: 120.9 us on the
-// orbit against 120.8 without (section 3 of that file).  Nothing gained, so it stays off.
+// Measured and not taken: the same exit for a pixel with a motion factor but no similar previous depth (depthFactor = 0) -- everybody else's history taps then wait for
+// the depth compare: 120.9 us on the orbit against 120.8 without (section 3 of that file).
 constexpr int kTaaBX = 32, kTaaBY = 8, kTaaTW = kTaaBX + 2, kTaaTH = kTaaBY + 2;
 // Round 5: the chain's composite (M1, with SSR's cleanup R7 inside: mifx_composite.h) evaluated HERE, for the 34 x 10 texels of the block's colour tile, instead of a
 // pass of its own that writes a plane this kernel is the only reader of.  COMPOSITE = false: `currColor` is read (the stand-alone effect, the chain with the fusion
@@ -76,10 +75,10 @@ struct TaaCompositeIn
     int   outW, outH;
     SsrCleanupIn r7;
 };
-template <bool GAUSS, bool BICUBIC, bool YCOCG, bool COMPOSITE>
 #ifndef MIFX_TAA_WAVES
 #define MIFX_TAA_WAVES 5
 #endif
+template <bool GAUSS, bool BICUBIC, bool YCOCG, bool COMPOSITE>
 __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img currColor, Img prevColor, Img motionTex, Img currDepth /*reprojected*/, Img prevDepth, Img out, CamK cur, CamK prev,
                                                   float stability, int reset, int skipRejection, int historySkip, TaaCompositeIn ci)
 {
@@ -164,14 +163,7 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
             tile[i0] = mk4(rgb_to_ycocg<YCOCG>(hdr_to_sdr(max3(xyz(raw0), 0.0f))), 0.0f);
             if (two) tile[i1] = mk4(rgb_to_ycocg<YCOCG>(hdr_to_sdr(max3(xyz(raw1), 0.0f))), 0.0f);
         }
-#ifdef MIFX_TAA_LDS_BARRIER
-        // the workgroup exchanges LDS data only: wait for this wave's LDS writes and meet the others -- __syncthreads() would also wait for every global load in flight
-        // (its workgroup-scope fence covers global memory), i.e. for the depth taps just requested
-        if (!COMPOSITE) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else __syncthreads();
-#else
         __syncthreads();
-#endif
         if (!COMPOSITE)
             for (int i = 0; i < 9; ++i) keep_here(dtap[i]); // (requested above: pinned here so that the loads are not sunk to their use)
     }
@@ -221,15 +213,6 @@ __global__ __launch_bounds__(256) MIFX_WAVES(MIFX_TAA_WAVES) void taa_kernel(Img
             }
     }
     const float depthFactor = similar ? 1.0f : 0.0f; // TAA_DEPTH_DISOCCLUSION_THRESHOLD = 0.9
-#ifdef MIFX_TAA_SKIP_DISOCCLUDED
-    // The same exit for a pixel without a similar previous depth (alpha = w * motionFactor * 0): its 20 history taps are not issued -- and everybody else's wait
-    // for the depth compare, one more dependent round trip.  Numbers in the header comment.
-    if (historySkip && !similar)
-    {
-        store_current_only();
-        return;
-    }
-#endif
     v4 prevRGBA;
     if (BICUBIC)
     {

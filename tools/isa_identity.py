@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Which kernels changed since a revision?  Compiles every diligentfx_amd/csrc/*.hip of <rev> (a temporary git worktree) and of the working tree to gfx950 assembly with
 the build's flags and compares the kernels instruction for instruction (comments and block numbers stripped).  What a GPU test run of <rev> still says about the working
-tree: everything whose kernels are identical.  No GPU needed.
+tree: everything whose kernels are identical.  A kernel whose signature (and so its mangled name) changed while its instructions did not is paired with its successor and
+listed as "renamed, identical".  No GPU needed.
 
     python tools/isa_identity.py 178790a > profiles/r04_isa_identity_v19_vs_final.txt"""
 import glob
@@ -59,9 +60,24 @@ def main():
                     continue
                 ka, kb = kernels(a), kernels(b)
                 diff = [k for k in ka if k in kb and ka[k] != kb[k]]
-                print(f"{name}: {sum(1 for k in ka if k in kb and ka[k] == kb[k])} kernels identical, {len(diff)} different, {len(set(kb) - set(ka))} new, {len(set(ka) - set(kb))} gone")
+                gone, new, renamed = [k for k in ka if k not in kb], [k for k in kb if k not in ka], []
+                for g in list(gone):  # a kernel whose signature changed and whose instructions did not (its own name in a directive aside)
+                    n = next((n for n in new if [t.replace(n, "@") for t in kb[n]] == [t.replace(g, "@") for t in ka[g]]), None)
+                    if n is not None:
+                        renamed.append((g, n))
+                        gone.remove(g)
+                        new.remove(n)
+                print(f"{name}: {sum(1 for k in ka if k in kb and ka[k] == kb[k])} kernels identical, {len(diff)} different, {len(new)} new, {len(gone)} gone"
+                      + (f", {len(renamed)} renamed" if renamed else ""))
+                short = lambda k: subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()[:160] or k
                 for k in diff:
-                    print("    different:", subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()[:160] or k)
+                    print("    different:", short(k))
+                for g, n in renamed:
+                    print("    renamed, identical:", short(g).split("(")[0], "->", short(n).split("(")[0])
+                for k in gone:
+                    print("    gone:", short(k).split("(")[0])
+                for k in new:
+                    print("    new:", short(k).split("(")[0])
         finally:
             subprocess.run(["git", "-C", ROOT, "worktree", "remove", "--force", old])
 

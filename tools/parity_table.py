@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Outlier fractions of the GPU parity suite, one row per comparison: the shipped build beside the strict build (exact division and square roots, no contraction,
-MIFX_R4_STRICT) -- what every deliberate deviation from the reference's arithmetic costs, in the unit the tests decide in.
+"""Outlier fractions of the GPU parity suite, one row per comparison: the shipped build beside the strict build (exact division and square roots, no contraction)
+-- what every deliberate deviation from the reference's arithmetic costs, in the unit the tests decide in.
 
     MIFX_PARITY_LOG=/tmp/shipped.jsonl python -m pytest tests -m gpu -q
-    MIFX_FMA_SOURCES=none: build_variant(..., ['-DMIFX_PRECISE_MATH=1', '-DMIFX_R4_STRICT=1']) -> MIFX_LIB_PATH=.../strict.so MIFX_PARITY_LOG=/tmp/strict.jsonl MIFX_PARITY_MEASURE=1 python -m pytest ...
+    MIFX_FMA_SOURCES=none: build_variant(..., ['-DMIFX_PRECISE_MATH=1']) -> MIFX_LIB_PATH=.../strict.so MIFX_PARITY_LOG=/tmp/strict.jsonl MIFX_PARITY_MEASURE=1 python -m pytest ...
     python tools/parity_table.py /tmp/shipped.jsonl /tmp/strict.jsonl
 
 Comparisons that differ only in a frame number are folded into one row (the worst frame)."""
