@@ -430,6 +430,106 @@ def pbr_shade_output(ctx: "PostFXContext", gbuffer: dict, layers, flags: int, ca
     return out_color, out_specular_ibl
 
 
+class TextureArray:
+    """A Texture2DArray of the material fetch (mifx_texture_array) in device memory.  mips: the chain as a list of numpy arrays, level k of shape (slices, max(1, h >> k),
+    max(1, w >> k), 4): float32 -> RGBA32_FLOAT, uint8 -> RGBA8_UNORM.  The levels of a slice are packed one behind the other."""
+
+    def __init__(self, mips, device):
+        import numpy as np
+
+        mips = [np.ascontiguousarray(m) for m in mips]
+        slices, h, w, c = mips[0].shape
+        assert c == 4 and mips[0].dtype in (np.float32, np.uint8) and all(m.dtype == mips[0].dtype for m in mips)
+        for k, m in enumerate(mips):
+            assert m.shape == (slices, max(1, h >> k), max(1, w >> k), 4), f"level {k} is {m.shape}"
+        self.mips_np = mips
+        self.data = torch.from_numpy(np.concatenate([m.reshape(slices, -1, 4) for m in mips], axis=1)).to(device)
+        fmt = B.NATIVE_FORMATS["RGBA8_UNORM" if mips[0].dtype == np.uint8 else "RGBA32_FLOAT"]
+        self.struct = B.TextureArray(self.data.data_ptr(), w, h, slices, len(mips), fmt, 0, self.data.stride(0) * self.data.element_size())
+
+    @classmethod
+    def from_level0(cls, level0, device, mips=None):
+        """The chain box-filtered from level 0 (slices, h, w, 4): each level averages the 2 x 2 (at an odd size: the first 2 * n) texels of the level above; uint8 levels are
+        rounded to nearest.  mips: the number of levels (default: down to 1 x 1)."""
+        import numpy as np
+
+        level0 = np.asarray(level0)
+        chain, cur = [level0], level0.astype(np.float32)
+        while (mips is None or len(chain) < mips) and max(cur.shape[1], cur.shape[2]) > 1:
+            h, w = max(1, cur.shape[1] // 2), max(1, cur.shape[2] // 2)
+            ys, xs = (2 if cur.shape[1] > 1 else 1), (2 if cur.shape[2] > 1 else 1)
+            cur = cur[:, :h * ys, :w * xs].reshape(cur.shape[0], h, ys, w, xs, 4).mean(axis=(2, 4), dtype=np.float32)
+            chain.append(np.clip(np.rint(cur), 0, 255).astype(np.uint8) if level0.dtype == np.uint8 else cur)
+        return cls(chain, device)
+
+
+def Material(basic=None, textures=None, fallback_color=(1.0, 1.0, 1.0, 1.0), sheen=(1.0, 1.0, 1.0, 1.0), anisotropy=(1.0, 0.0, 0.0, 0.0), iridescence=(1.0, 1.3, 100.0, 400.0),
+             transmission=(1.0, 0.0, 0.0, 0.0)) -> B.PBRMaterial:
+    """One record of the material table (mifx_pbr_material).  basic: binding.PBRMaterialBasicAttribs (default: metallic-roughness, every factor 1); textures: dict
+    slot (binding.PBR_TEXTURE_*) -> (index into the call's texture table, binding.PBRTextureAttribs or None for UV0 / wrap / slice 0); a slot that is missing has no map.
+    sheen: (colour factor rgb, roughness factor); anisotropy: (strength, rotation); iridescence: (factor, IOR, thickness minimum, maximum); transmission: (factor)."""
+    m = B.PBRMaterial()
+    if basic is None:
+        basic = B.PBRMaterialBasicAttribs((ctypes.c_float * 4)(1, 1, 1, 1), (ctypes.c_float * 3)(1, 1, 1), 1.0, (ctypes.c_float * 3)(1, 1, 1), 1.0, 0, 0, 0.5, 1.0, 1.0, 1.0, 1.0, 1.0,
+                                          (ctypes.c_float * 4)(0, 0, 0, 0))
+    m.basic = basic
+    m.sheen[:], m.anisotropy[:], m.iridescence[:], m.transmission[:] = list(sheen), list(anisotropy), list(iridescence), list(transmission)
+    m.fallback_color[:] = list(fallback_color)
+    for s in range(B.PBR_TEXTURE_COUNT):
+        m.texture[s] = -1
+        m.textures[s] = B.PBRTextureAttribs.make(uv_selector=-1)
+    for s, (index, attribs) in (textures or {}).items():
+        m.texture[s] = index
+        m.textures[s] = attribs if attribs is not None else B.PBRTextureAttribs.make()
+    return m
+
+
+MATERIAL_INTERPOLANTS = ("depth", "uv0", "uv1", "mesh_normal", "color", "face", "material_index")
+_MATERIAL_LAYER_OUTPUTS = (("clearcoat", B.PBR_LAYER_CLEAR_COAT, 4), ("sheen", B.PBR_LAYER_SHEEN, 4), ("anisotropy", B.PBR_LAYER_ANISOTROPY, 4),
+                           ("iridescence", B.PBR_LAYER_IRIDESCENCE, 4), ("transmission", B.PBR_LAYER_TRANSMISSION, 1))
+
+
+def pbr_material_fetch(ctx: "PostFXContext", interpolants: dict, materials, textures, camera: B.CameraAttribs, layer_flags=0, flags=0, mip_bias=0.0, gbuffer: dict = None,
+                       layers: dict = None, want_emissive=True, want_occlusion=True, check_only=False):
+    """The material fetch (mifx_pbr_material_fetch): the head of the reference's pixel shader over interpolant planes.  interpolants: dict with `depth` and any of uv0, uv1,
+    mesh_normal, color, face, material_index (MATERIAL_INTERPOLANTS); materials: sequence of binding.PBRMaterial (see Material()); textures: sequence of TextureArray.
+    gbuffer / layers: planes to write into (a pixel without a fragment keeps their texels); planes that are missing are allocated zeroed.  Returns (gbuffer, layers): the dicts
+    that pbr_shade_layers() and pbr_shade_output() take (gbuffer["depth"] is the interpolants' depth)."""
+    depth = interpolants["depth"]
+    h, w = depth.shape
+    new = lambda c: torch.zeros((h, w, 4) if c == 4 else (h, w), device=depth.device, dtype=B.storage_dtype() if c == 4 else torch.float32)  # noqa: E731
+    g, ly = dict(gbuffer or {}), dict(layers or {})
+    for k in ("base_color", "normal", "material"):
+        if g.get(k) is None:
+            g[k] = new(4)
+    if want_emissive and g.get("emissive") is None:
+        g["emissive"] = new(4)
+    if want_occlusion and g.get("occlusion") is None:
+        g["occlusion"] = new(1)
+    for k, bit, c in _MATERIAL_LAYER_OUTPUTS:
+        if (layer_flags & bit) and ly.get(k) is None:
+            ly[k] = new(c)
+    if (layer_flags & B.PBR_LAYER_CLEAR_COAT) and ly.get("clearcoat_normal") is None and any(m.texture[B.PBR_TEXTURE_CLEAR_COAT_NORMAL] >= 0 for m in materials):
+        ly["clearcoat_normal"] = new(4)
+    iimgs = {k: B.image(interpolants[k]) for k in MATERIAL_INTERPOLANTS if interpolants.get(k) is not None}
+    ip = B.MaterialInterpolants(*[ctypes.pointer(iimgs[k]) if k in iimgs else None for k in MATERIAL_INTERPOLANTS])
+    gimgs = {k: B.image(g[k]) for k in ("base_color", "normal", "material", "emissive", "occlusion") if g.get(k) is not None}
+    p = lambda k: ctypes.pointer(gimgs[k]) if k in gimgs else None  # noqa: E731
+    gs = B.GBuffer(p("base_color"), p("normal"), p("material"), None, p("emissive"), p("occlusion"))
+    limgs = {k: B.image(ly[k]) for k in B.PBR_LAYER_PLANES if ly.get(k) is not None}
+    ls = B.PBRLayers(layer_flags, 0.0, 0.0, 0, *[ctypes.pointer(limgs[k]) if k in limgs else None for k in B.PBR_LAYER_PLANES])
+    mats = (B.PBRMaterial * len(materials))(*materials)
+    texs = (B.TextureArray * max(len(textures), 1))(*[t.struct for t in textures])
+    desc = B.MaterialFetchDesc(mats, texs if textures else None, len(materials), len(textures), layer_flags, flags, mip_bias, (ctypes.c_uint32 * 3)(0, 0, 0))
+    if check_only:
+        B.check(ctx.lib.mifx_pbr_material_fetch_check(ctypes.byref(ip), ctypes.byref(desc), ctypes.byref(camera), ctypes.byref(gs), ctypes.byref(ls)))
+        return None
+    ctx.sync_stream()
+    B.check(ctx.lib.mifx_pbr_material_fetch(ctx.handle, ctypes.byref(ip), ctypes.byref(desc), ctypes.byref(camera), ctypes.byref(gs), ctypes.byref(ls)))
+    g["depth"] = depth
+    return g, ly
+
+
 PBR_TARGET_PLANES = ("normal", "base_color", "material", "ibl")
 
 

@@ -417,6 +417,8 @@ def load():
         _lib.mifx_storage_mode.restype = c_u
         assert bool(_lib.mifx_storage_mode()) == STORAGE_H4 or os.environ.get("MIFX_LIB_PATH"), "the loaded library is not the storage build MIFX_STORAGE asks for"
         _declare_oit(_lib)
+        if hasattr(_lib, "mifx_pbr_material_fetch"):  # (a library named by MIFX_LIB_PATH may be built from the host sources alone: the entries live beside their kernel)
+            declare_material_fetch(_lib)
     return _lib
 
 
@@ -505,6 +507,57 @@ class CommStats(ctypes.Structure):  # mifx_comm_stats
 
 
 SIZEOF_NAMES.update({"pbr_shade_output_desc": PBRShadeOutputDesc, "pbr_targets": PBRTargets, "shard_info": ShardInfo, "comm_stats": CommStats, "oit_slice": OITSlice, "oit_targets": OITTargets})
+
+
+# ---- the material fetch (include/mifx.h "material fetch")
+PBR_TEXTURE_SLOTS = ("BASE_COLOR", "PHYS_DESC", "NORMAL", "OCCLUSION", "EMISSIVE", "METALLIC", "ROUGHNESS", "CLEAR_COAT", "CLEAR_COAT_ROUGHNESS", "CLEAR_COAT_NORMAL", "SHEEN_COLOR",
+                     "SHEEN_ROUGHNESS", "ANISOTROPY", "IRIDESCENCE", "IRIDESCENCE_THICKNESS", "TRANSMISSION")
+for _i, _n in enumerate(PBR_TEXTURE_SLOTS):
+    globals()["PBR_TEXTURE_" + _n] = _i
+PBR_TEXTURE_COUNT = len(PBR_TEXTURE_SLOTS)
+MATERIAL_FETCH_FLAG_TEXTURE_ATLAS, MATERIAL_FETCH_FLAG_TEXCOORD_TRANSFORM, MATERIAL_FETCH_FLAG_SRGB_TO_LINEAR = 1, 2, 4
+TEXTURE_ADDRESS_WRAP, TEXTURE_ADDRESS_CLAMP = 1, 3
+
+
+class TextureArray(ctypes.Structure):  # mifx_texture_array
+    _fields_ = [("data", c_p), ("width", c_u), ("height", c_u), ("slices", c_u), ("mips", c_u), ("format", c_u), ("padding", c_u), ("slice_pitch_bytes", ctypes.c_uint64)]
+
+
+class PBRTextureAttribs(ctypes.Structure):  # PBRMaterialTextureAttribs, PBR_Structures.fxh:245-254 (48 bytes)
+    _fields_ = [("PackedProps", c_u), ("TextureSlice", c_f), ("UBias", c_f), ("VBias", c_f), ("UVScaleAndRotation", c_f * 4), ("AtlasUVScaleAndBias", c_f * 4)]
+
+    @classmethod
+    def make(cls, uv_selector=0, wrap_u=TEXTURE_ADDRESS_WRAP, wrap_v=TEXTURE_ADDRESS_WRAP, slice=0.0, bias=(0.0, 0.0), scale_rotation=(1.0, 0.0, 0.0, 1.0),
+             atlas=(1.0, 1.0, 0.0, 0.0)):
+        """GLTF::Material::TextureShaderAttribs: selector -1 = none, 0 = UV0, 1 = UV1; wrap modes are TEXTURE_ADDRESS_* values"""
+        packed = ((uv_selector + 1) & 7) | (((wrap_u - 1) & 7) << 3) | (((wrap_v - 1) & 7) << 6)
+        return cls(packed, slice, bias[0], bias[1], (c_f * 4)(*scale_rotation), (c_f * 4)(*atlas))
+
+
+class PBRMaterial(ctypes.Structure):  # mifx_pbr_material (1008 bytes)
+    _fields_ = [("basic", PBRMaterialBasicAttribs), ("sheen", c_f * 4), ("anisotropy", c_f * 4), ("iridescence", c_f * 4), ("transmission", c_f * 4), ("fallback_color", c_f * 4),
+                ("textures", PBRTextureAttribs * PBR_TEXTURE_COUNT), ("texture", c_i * PBR_TEXTURE_COUNT)]
+
+
+class MaterialInterpolants(ctypes.Structure):  # mifx_material_interpolants
+    _fields_ = [(n, PImage) for n in ("depth", "uv0", "uv1", "mesh_normal", "color", "face", "material_index")]
+
+
+class MaterialFetchDesc(ctypes.Structure):  # mifx_material_fetch_desc
+    _fields_ = [("materials", ctypes.POINTER(PBRMaterial)), ("textures", ctypes.POINTER(TextureArray)), ("material_count", c_u), ("texture_count", c_u), ("layer_flags", c_u),
+                ("flags", c_u), ("mip_bias", c_f), ("padding", c_u * 3)]
+
+
+SIZEOF_NAMES.update({"texture_array": TextureArray, "pbr_texture_attribs": PBRTextureAttribs, "pbr_material": PBRMaterial, "material_interpolants": MaterialInterpolants,
+                     "material_fetch_desc": MaterialFetchDesc})
+
+
+def declare_material_fetch(lib):
+    """Prototypes of the two material-fetch entries (any build of the library)"""
+    PM, PD, PC, PG, PL = ctypes.POINTER(MaterialInterpolants), ctypes.POINTER(MaterialFetchDesc), ctypes.POINTER(CameraAttribs), ctypes.POINTER(GBuffer), ctypes.POINTER(PBRLayers)
+    lib.mifx_pbr_material_fetch_check.argtypes, lib.mifx_pbr_material_fetch_check.restype = [PM, PD, PC, PG, PL], c_i
+    lib.mifx_pbr_material_fetch.argtypes, lib.mifx_pbr_material_fetch.restype = [c_p, PM, PD, PC, PG, PL], c_i
+    return lib
 
 
 class MifxError(RuntimeError):

@@ -245,6 +245,11 @@ uint32_t    mifx_sizeof(const char* n)
     MIFX_SZ("oit_slice", mifx_oit_slice);
     MIFX_SZ("oit_targets", mifx_oit_targets);
     MIFX_SZ("transparent_slice", mifx_transparent_slice);
+    MIFX_SZ("texture_array", mifx_texture_array);
+    MIFX_SZ("pbr_texture_attribs", mifx_pbr_texture_attribs);
+    MIFX_SZ("pbr_material", mifx_pbr_material);
+    MIFX_SZ("material_interpolants", mifx_material_interpolants);
+    MIFX_SZ("material_fetch_desc", mifx_material_fetch_desc);
 #undef MIFX_SZ
     return 0;
 }

@@ -743,6 +743,104 @@ MIFX_API mifx_status mifx_pbr_shade_targets(mifx_postfx* ctx, const mifx_gbuffer
                                             const mifx_pbr_shade_attribs* attribs, const mifx_ibl* ibl, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc* output,
                                             const float background[4], const mifx_image2d* out_color, const mifx_pbr_targets* targets);
 
+/* ------------------------------------------------------------------------------------------------ material fetch (the head of RenderPBR.psh `main`, :424-457 and GetSurfaceShadingInfo's fetches)
+ * The producer of the planes that mifx_gbuffer and mifx_pbr_layers describe: for every pixel with a fragment it runs the head of the reference's forward pixel shader -- the material
+ * textures through the texture system (Shaders/PBR/private/PBR_Textures.fxh:346-932, Shaders/Common/public/AtlasSampling.fxh:64-184), normal mapping from position and UV
+ * gradients (PBR_Shading.fxh:144-199, ShaderUtilities.fxh:43-69), ReadBaseLayerProperties up to PerturbNormal (RenderPBR.psh:138-184) and the fetches of the layer readers
+ * (:186-297, the clear coat's PerturbNormal :203-216 included) -- over interpolant planes (the VSOutput of the frame) that a visibility or attribute pass of the caller produced.
+ * One kernel, one launch.  An MI355X has no rasteriser and no texture unit, so two things the reference leaves to the graphics API are defined here:
+ *
+ * 1. Derivatives.  ddx / ddy are the FINE derivatives of the pixel's 2x2 quad (x & ~1, y & ~1): ddx = right - left of the pixel's row, ddy = bottom - top of its column, taken
+ *    of the very expressions the shader differentiates (UVInfo.UV after TransformUV, RenderPBR.psh:115-116; UV in SampleTexture, PBR_Textures.fxh:398-399,421; Pos,
+ *    PBR_Shading.fxh:159-160).  A pixel evaluates its quad partners' expressions from the PARTNERS' interpolants with ITS OWN material, as a rasteriser's helper lanes do: equal to
+ *    the reference bit for bit wherever a quad lies in one draw, and defined where it does not.  Partner coordinates are clamped to the frame (an odd last column / row and a 1x1
+ *    frame get a zero derivative along that axis); a partner without a fragment still lends its interpolants, so the planes must be finite everywhere.
+ * 2. Sampler.  Trilinear, WRAP addressing in u and v, no anisotropy ("Tex_sampler uses wrap", PBR_Textures.fxh:410).  Texel centres at (i + 0.5) / N, weights as
+ *    GetBilinearSamplingInfoUC (ShaderUtilities.fxh:126-142).  rho = max(length(dUVdx * dim0), length(dUVdy * dim0)), lod = log2(rho) + bias clamped to [0, mips - 1]: SampleBias
+ *    takes the quad's derivatives, SampleGrad the ones given, SampleLevel the lod given, CalculateLevelOfDetail returns the clamped value.  The sample is
+ *    a + (b - a) * frac(lod) of levels floor(lod) and floor(lod) + 1, in fp32.  The slice is fSlice rounded to nearest and clamped to [0, slices - 1].  No address depends on an
+ *    unclamped input: a coordinate that is NaN, infinite or beyond 2^30 texels falls on texel 0 with weight 0.
+ * One deviation: where the tangent frame of PerturbNormal degenerates to a non-finite normal (non-finite or overflowing gradients) the macro normal is stored instead.
+ * Not a deviation, but worth knowing: without mesh normals the macro normal is normalize(cross(ddx(Pos), ddy(Pos))); where a derivative is zero by rule 1 (an odd last column
+ * or row, a 1x1 frame) that is the reference's result for a zero gradient, a non-finite normal -- give such frames mesh normals.
+ * Out of scope: the chain (mifx_chain_set_*), row bands and sharding, the native-storage build (the entries are exported, make the same checks and return
+ * MIFX_ERR_NOT_IMPLEMENTED), ENABLE_VOLUME (GetVolumeThickness: no plane carries it), mirror addressing (the reference has none either), anisotropic filtering, block-compressed
+ * or sRGB-typed textures, explicit gradient planes, and PBR_ALPHA_MODE_MASK (it stays in mifx_pbr_shade_output, which reads base_color.a). */
+typedef struct mifx_texture_array /* a Texture2DArray with a full or partial mip chain (40 bytes) */
+{
+    const void* data;              /* device pointer; level k is max(1, width >> k) x max(1, height >> k) texels, the levels tightly packed one behind the other within a slice */
+    uint32_t    width, height, slices, mips;
+    uint32_t    format;            /* MIFX_NATIVE_FORMAT_RGBA32_FLOAT or MIFX_NATIVE_FORMAT_RGBA8_UNORM (decoded as formats.hip does: c / 255); sRGB stays in the shader text */
+    uint32_t    padding;
+    uint64_t    slice_pitch_bytes; /* slice k at data + k * slice_pitch_bytes; a multiple of the texel size, at least the bytes of the chain */
+} mifx_texture_array;
+typedef struct mifx_pbr_texture_attribs /* PBRMaterialTextureAttribs, Shaders/PBR/public/PBR_Structures.fxh:245-254 (48 bytes), byte for byte */
+{
+    uint32_t PackedProps; /* bits 0-2: UV selector + 1 (0 = none), bits 3-5: wrap U mode - 1, bits 6-8: wrap V mode - 1 (TEXTURE_ADDRESS_*: 1 WRAP, 3 CLAMP), :259-275 */
+    float    TextureSlice, UBias, VBias;
+    float    UVScaleAndRotation[4];
+    float    AtlasUVScaleAndBias[4];
+} mifx_pbr_texture_attribs;
+enum /* the slots of mifx_pbr_material::textures / ::texture */
+{
+    MIFX_PBR_TEXTURE_BASE_COLOR = 0, MIFX_PBR_TEXTURE_PHYS_DESC, MIFX_PBR_TEXTURE_NORMAL, MIFX_PBR_TEXTURE_OCCLUSION, MIFX_PBR_TEXTURE_EMISSIVE, MIFX_PBR_TEXTURE_METALLIC,
+    MIFX_PBR_TEXTURE_ROUGHNESS, MIFX_PBR_TEXTURE_CLEAR_COAT, MIFX_PBR_TEXTURE_CLEAR_COAT_ROUGHNESS, MIFX_PBR_TEXTURE_CLEAR_COAT_NORMAL, MIFX_PBR_TEXTURE_SHEEN_COLOR,
+    MIFX_PBR_TEXTURE_SHEEN_ROUGHNESS, MIFX_PBR_TEXTURE_ANISOTROPY, MIFX_PBR_TEXTURE_IRIDESCENCE, MIFX_PBR_TEXTURE_IRIDESCENCE_THICKNESS, MIFX_PBR_TEXTURE_TRANSMISSION,
+    MIFX_PBR_TEXTURE_COUNT /* 16 */
+};
+typedef struct mifx_pbr_material /* one record per material: PBRMaterialShaderInfo with every optional block present, PRIMITIVE.FallbackColor and the texture bindings (1008 bytes) */
+{
+    mifx_pbr_material_basic_attribs        basic;
+    mifx_pbr_material_sheen_attribs        sheen;
+    mifx_pbr_material_anisotropy_attribs   anisotropy;
+    mifx_pbr_material_iridescence_attribs  iridescence;
+    mifx_pbr_material_transmission_attribs transmission;
+    float                                  fallback_color[4];                 /* PRIMITIVE.FallbackColor (RenderPBR.psh:424) */
+    mifx_pbr_texture_attribs               textures[MIFX_PBR_TEXTURE_COUNT];
+    int32_t                                texture[MIFX_PBR_TEXTURE_COUNT];   /* index into mifx_material_fetch_desc::textures; -1 = the permutation without that USE_*_MAP.
+                                                                               * With PHYS_DESC present METALLIC and ROUGHNESS are not read (PBR_Textures.fxh:594-628) */
+} mifx_pbr_material;
+typedef struct mifx_material_interpolants /* the VSOutput of the frame; every plane has the frame's size (56 bytes) */
+{
+    const mifx_image2d* depth;          /* F32, required: WorldPos is InvProjectPosition of it, exactly as the shade reconstructs Shading.Pos */
+    const mifx_image2d* uv0;            /* F32X2, or NULL = the permutation without USE_TEXCOORD0 */
+    const mifx_image2d* uv1;            /* F32X2, or NULL = the permutation without USE_TEXCOORD1 */
+    const mifx_image2d* mesh_normal;    /* F32X4 xyz, or NULL = no USE_VERTEX_NORMALS (a zero vector: the normal comes from the position gradients) */
+    const mifx_image2d* color;          /* F32X4, or NULL = no USE_VERTEX_COLORS */
+    const mifx_image2d* face;           /* F32, >= 0 = front face (SV_IsFrontFace); NULL = every fragment faces front */
+    const mifx_image2d* material_index; /* F32 holding integers (the reference's MeshID target is a float); NULL = materials[0] everywhere */
+} mifx_material_interpolants;
+#define MIFX_MATERIAL_FETCH_FLAG_TEXTURE_ATLAS      1u /* USE_TEXTURE_ATLAS */
+#define MIFX_MATERIAL_FETCH_FLAG_TEXCOORD_TRANSFORM 2u /* ENABLE_TEXCOORD_TRANSFORM */
+#define MIFX_MATERIAL_FETCH_FLAG_SRGB_TO_LINEAR     4u /* TEX_COLOR_CONVERSION_MODE_SRGB_TO_LINEAR; unset = TEX_COLOR_CONVERSION_MODE_NONE */
+typedef struct mifx_material_fetch_desc /* (48 bytes) */
+{
+    const mifx_pbr_material*  materials;     /* host memory, material_count records */
+    const mifx_texture_array* textures;      /* host memory, texture_count descriptors (their `data` are device pointers) */
+    uint32_t                  material_count, texture_count;
+    uint32_t                  layer_flags;   /* MIFX_PBR_LAYER_*: a layer that is off writes nothing and reads nothing */
+    uint32_t                  flags;         /* MIFX_MATERIAL_FETCH_FLAG_* */
+    float                     mip_bias;      /* g_Frame.Renderer.MipBias */
+    uint32_t                  padding[3];
+} mifx_material_fetch_desc;
+/* Outputs: gbuffer->base_color (GetBaseColor), ->normal (Base.Normal, w = 0) and ->material are required, ->emissive (GetEmissive before EmissionScale, a = 0) and ->occlusion
+ * (GetOcclusion before OcclusionStrength) optional, ->depth ignored.  material = (PhysicalDesc.g, PhysicalDesc.b, 0, 0) after the factors and saturate of RenderPBR.psh:169-170
+ * for metallic-roughness, the sampled PhysicalDesc texel for specular-glossiness (the shade converts that plane from sRGB itself and applies no factor).  layers->clearcoat (x =
+ * GetClearcoatFactor, y = GetClearcoatRoughness), ->clearcoat_normal (PerturbNormal of GetClearcoatNormal), ->sheen, ->anisotropy (GetAnisotropy before the rotation),
+ * ->iridescence (x = GetIridescence, y = GetIridescenceThickness) and ->transmission are written when their layer is on in desc->layer_flags (layers->flags is not read; `layers`
+ * may be NULL when layer_flags is 0); ->clearcoat_normal only if some material has a CLEAR_COAT_NORMAL map, otherwise it must be NULL.  A pixel has a fragment when its depth is
+ * not the far plane (the shade's rule; the context's reversed-depth flag applies) and its material index is in [0, material_count); a pixel without one keeps the caller's texel
+ * in every output plane.  camera: mViewProjInv, f4ViewportSize and fHandness are read.
+ * Refused with MIFX_ERR_INVALID_ARG before the first device call (the lighting takes one workflow, one iridescence IOR and one anisotropy rotation per call): a table that mixes
+ * workflows; one that differs in Iridescence.IOR / Anisotropy.Rotation with that layer on; a specular-glossiness material whose specular factors are not 1;
+ * PBR_WORKFLOW_UNLIT (2) materials (an unlit material has a base colour only: describe it as metallic-roughness and shade it with mifx_pbr_shade_output's `unlit`); a texture index
+ * outside the table; with the atlas flag a region outside [0, 1]; a map present while both UV planes are NULL; mis-sized, mis-formatted or aliasing planes.
+ * mifx_pbr_material_fetch_check makes exactly these checks and no device call. */
+MIFX_API mifx_status mifx_pbr_material_fetch_check(const mifx_material_interpolants* interpolants, const mifx_material_fetch_desc* desc, const mifx_camera_attribs* camera,
+                                                   const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers);
+MIFX_API mifx_status mifx_pbr_material_fetch(mifx_postfx* ctx, const mifx_material_interpolants* interpolants, const mifx_material_fetch_desc* desc,
+                                             const mifx_camera_attribs* camera, const mifx_gbuffer* gbuffer, const mifx_pbr_layers* layers);
+
 /* IBL precompute == PBR_Renderer::PrecomputeBRDF (PBR_Renderer.cpp:548-622) and PBR_Renderer::PrecomputeCubemaps (:729-972).
  * The environment map is a float4 cube with a full (box-filtered) mip chain, as the reference expects of its input SRV. */
 /* The shade samples the IBL cube maps through a working copy with a one-texel apron per face, made at every call because the maps are the caller's memory (they may
