@@ -24,6 +24,22 @@ struct MaterialTexK // a mifx_texture_array as the kernel reads it (104 bytes)
     unsigned             pad;
     unsigned             levelOffset[16]; // first texel of level k within a slice
 };
+// the descriptor of a texture that has passed the checks of the entries (api_material.cpp: sizes, format, at most 15 levels): the levels of a slice lie one behind the other
+inline MaterialTexK make_material_texk(const mifx_texture_array& t)
+{
+    MaterialTexK o{};
+    o.data = static_cast<const unsigned char*>(t.data);
+    o.slicePitch = t.slice_pitch_bytes;
+    o.w = int(t.width); o.h = int(t.height); o.slices = int(t.slices); o.mips = int(t.mips);
+    o.rgba8 = t.format == MIFX_NATIVE_FORMAT_RGBA8_UNORM ? 1u : 0u;
+    unsigned texels = 0;
+    for (uint32_t l = 0; l < t.mips; ++l)
+    {
+        o.levelOffset[l] = texels;
+        texels += ((t.width >> l) > 1u ? (t.width >> l) : 1u) * ((t.height >> l) > 1u ? (t.height >> l) : 1u);
+    }
+    return o;
+}
 struct MaterialFetchK
 {
     Img depth, uv0, uv1, meshNormal, color, face, index; // p == nullptr: the permutation without it

@@ -73,7 +73,7 @@ struct mifx_postfx
     mifx::IblApronCache ibl_apron;
     // the intermediate array of the two-launch shadow conversion (shadows.hip), grown on demand; used on `stream` only, freed with the context
     mifx::DeviceScratch shadow_scratch;
-    // the material and texture tables of mifx_pbr_material_fetch (material.hip) as the kernel reads them, uploaded when they differ from `material_tables_host`
+    // the material and texture tables of mifx_pbr_material_fetch (api_material.cpp) as the kernel reads them, uploaded when they differ from `material_tables_host`
     mifx::DeviceScratch        material_tables;
     std::vector<unsigned char> material_tables_host;
 

@@ -72,6 +72,15 @@ class OitTargetsK(ctypes.Structure):  # mifx::OitTargetsK
     _fields_ = [("color", Img), ("base", Img), ("material", Img), ("ibl", Img)]
 
 
+class MaterialFetchK(ctypes.Structure):  # mifx::MaterialFetchK (mifx_material.h)
+    INPUTS = (("depth", 1), ("uv0", 2), ("uv1", 2), ("meshNormal", 4), ("color", 4), ("face", 1), ("index", 1))
+    OUTPUTS = (("outBaseColor", 4), ("outNormal", 4), ("outMaterial", 4), ("outEmissive", 4), ("outOcclusion", 1), ("outClearcoat", 4), ("outClearcoatNormal", 4), ("outSheen", 4),
+               ("outAnisotropy", 4), ("outIridescence", 4), ("outTransmission", 1))
+    _fields_ = [(n, Img) for n, _ in INPUTS + OUTPUTS] + [("materials", ctypes.c_void_p), ("textures", ctypes.c_void_p), ("materialCount", ctypes.c_int), ("textureCount", ctypes.c_int),
+                                                         ("layers", ctypes.c_uint), ("flags", ctypes.c_uint), ("mipBias", ctypes.c_float), ("handness", ctypes.c_float),
+                                                         ("workflow", ctypes.c_int)]
+
+
 class SelectionK(ctypes.Structure):  # mifx::SelectionK (mifx_selection.h)
     _fields_ = [("depth", Img), ("selectionDepth", Img), ("closest", Img), ("outline", ctypes.c_float * 3), ("occluded", ctypes.c_float * 3), ("desaturation", ctypes.c_float),
                 ("clearDepth", ctypes.c_float), ("outlineWidth", ctypes.c_float)]
@@ -953,6 +962,20 @@ class Device:
         self._oit_targets(blob(targets, OitTargetsK))
         self._shade_call(host_lib("shade_blend_host").mifx_host_oit_shade_blend_launch, (ctypes.c_void_p(k.p), ctypes.c_void_p(targets.p)), si["planes"] + [alpha], si, camera, attribs,
                          None, reversed_depth, ())
+
+    # ------------------------------------------------------------------------------------------------ the material fetch (material.hip)
+    def do_material_fetch(self, k, cam):
+        """material_fetch_kernel in place on the launcher's arguments (tests/host_kernels/material_fetch_host.cpp mifx_host_material_fetch_launch): the interpolant planes are
+        reads, the output planes that are there writes, the tables -- material records, then texture descriptors, one allocation of the context -- a raw read"""
+        K = blob(k, MaterialFetchK)
+        assert ctypes.sizeof(MaterialFetchK) == k.bytes, (ctypes.sizeof(MaterialFetchK), k.bytes)
+        for name, c in MaterialFetchK.INPUTS:
+            view(getattr(K, name), c)
+        for name, c in MaterialFetchK.OUTPUTS:
+            view(getattr(K, name), c, _write=True)
+        touch(K.materials)
+        rc = host_lib("material_fetch_host").mifx_host_material_fetch_launch(ctypes.c_void_p(k.p), ctypes.c_void_p(cam.p))
+        assert rc == 0, rc
 
     # ------------------------------------------------------------------------------------------------ the selection outline (selection.hip, composite.hip)
     def do_jump_flood(self, selection_depth, clear_depth, iterations, tmp0, tmp1, out, row_begin, row_end):

@@ -1054,6 +1054,70 @@ def main():
         for seed in range(int(sys.argv[2]), int(sys.argv[3])):
             chain_random(lib, seed, exact)
             print(f"cpu product: chain sequence OK: {seed}", flush=True)
+    elif what == "material_fetch":
+        # mifx_pbr_material_fetch (api_material.cpp) as shipped: ONE context through a sequence of fixture cases -- the same tables twice, other and larger tables, back
+        # again, a 1x1 frame -- each call into sentinel-filled planes, against the same compiled body run on the case's own arrays (material_fetch_util.run_on_host): both
+        # sides execute one body, so a difference is a difference of the host code -- the descriptors, which tables the context holds, when it uploads them
+        import material_fetch_util as M
+        import test_gpu_material_fetch as F
+        from util import blue_noise_tables
+
+        host = cpu_device.host_lib("material_fetch_host")
+        by_name = {c["name"]: c for c in M.cases()}
+        sequence = ("a_minified", "a_minified", "o_three_materials", "m_every_layer_rgba8", "a_minified", "p_frame_1x1")
+        ctx = api.PostFXContext(0)
+        inputs = {name: F.device_inputs(by_name[name], ctx.device) for name in set(sequence)}  # (made once a case: a repeated case hands the entry the very same tables)
+        syncs = []
+        rt_type = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)
+        cb = rt_type(lambda op, a, b, n: syncs.append(step) if op == 7 else None)  # (RT_STREAM_SYNC of stub_device.cpp: the wait in front of an upload)
+        lib.mifx_cpu_set_runtime_callback(cb)
+        start = len(dev.log)
+        for step, name in enumerate(sequence):
+            c = by_name[name]
+            interp, mats, textures = inputs[name]
+            g, ly = F.caller_planes(c, ctx.device)
+            g, ly = api.pbr_material_fetch(ctx, interp, mats, textures, B.camera_from_bytes(c["camera"].tobytes()), layer_flags=c["layers"], flags=c["flags"], mip_bias=c["mip_bias"],
+                                           gbuffer=g, layers=ly)
+            got = {**{k: v for k, v in g.items() if k != "depth"}, **ly}
+            want = M.run_on_host(host, c)
+            assert set(got) == set(want) == set(M.output_names(c)), (name, sorted(got), sorted(want))
+            frag = M.has_fragment(c)
+            for k, t in got.items():
+                a = np.ascontiguousarray(t.numpy())
+                assert np.array_equal(a.view(np.uint32), want[k].view(np.uint32)), f"call {step} ({name}), {k}: {(a.view(np.uint32) != want[k].view(np.uint32)).mean():.3e} of the words differ"
+                assert (a[~frag] == M.SENTINEL).all() and (frag.all() or (a[frag] != M.SENTINEL).any()), (step, name, k)
+        lib.mifx_cpu_set_runtime_callback(ctypes.cast(None, rt_type))
+        assert dev.log[start:] == ["material_fetch"] * len(sequence), dev.log[start:]
+        # the context waits for its stream and uploads exactly where the tables differ from the call before: not for the repeated case (call 1)
+        assert syncs == [s for s in range(len(sequence)) if s == 0 or sequence[s] != sequence[s - 1]], syncs
+        ctx.close()
+
+        def refusal(ctx, c, mats=None):
+            interp, m, textures = F.device_inputs(c, ctx.device)
+            try:
+                api.pbr_material_fetch(ctx, interp, mats(m, textures) if mats else m, textures, B.camera_from_bytes(c["camera"].tobytes()), flags=c["flags"])
+            except B.MifxError as e:
+                return str(e)
+            return "MIFX_OK"
+
+        c = by_name["a_minified"]
+        chain = api.Chain(0, *blue_noise_tables())
+        chain.set_row_band(4, 12, 0)
+        got = refusal(chain.postfx, c)
+        assert got == "MIFX_ERR_INVALID_ARG: mifx_pbr_material_fetch: not available inside a row band", got
+        chain.close()
+
+        def outside(m, textures):
+            m[0].texture[B.PBR_TEXTURE_BASE_COLOR] = len(textures)
+            return m
+
+        ctx = api.PostFXContext(0)
+        got = refusal(ctx, c, outside)
+        assert got == f"MIFX_ERR_INVALID_ARG: mifx_pbr_material_fetch: desc->materials[0].texture[BASE_COLOR] = {len(c['textures'])} is outside the texture table of {len(c['textures'])} entries", got
+        ctx.close()
+        assert dev.log[start:] == ["material_fetch"] * len(sequence)  # (a refused call launches nothing)
+        print(f"cpu product: scenario OK: the host-only build runs mifx_pbr_material_fetch: one context, {len(sequence)} calls ({', '.join(sequence)}) equal the body on each "
+              "case's own arrays bit for bit; refused inside a row band and for a texture index outside the table", flush=True)
     elif what == "unhandled":
         # a launcher without a handler in device.py fails loudly: the shadow maps' host code is linked and runs up to its first launch
         import shadows_util

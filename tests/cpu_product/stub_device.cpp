@@ -7,6 +7,7 @@
 // path of the product -- nothing in diligentfx_amd/ builds or loads it, and the library that ships fails without its HIP kernels and a device.
 #include "mifx_host.h"
 #include "mifx_grid_host.h"
+#include "mifx_material_host.h"
 #include "mifx_oit_host.h"
 #include "mifx_selection_host.h"
 #include "mifx_shadows_host.h"
@@ -410,6 +411,11 @@ mifx_status launch_copy_frame_grid(hipStream_t s, Img in, bool packedIn, Img dep
 {
     t_stream = s;
     return record("copy_frame_grid", in, packedIn, depth, out, attr, ave_log_lum, tonemap_flags, aveLum, cam, a, grid_flags);
+}
+mifx_status launch_material_fetch(hipStream_t s, const MaterialFetchK& k, const CamK& cam)
+{
+    t_stream = s;
+    return record("material_fetch", k, cam);
 }
 mifx_status launch_oit_clear(hipStream_t s, const OitK& k)
 {

@@ -13,9 +13,23 @@ using namespace mifx;
 extern "C" {
 struct host_plane { float* data; int w, h, c; int pitch_bytes; }; // pitch_bytes 0: tightly packed
 struct host_texture { const void* data; int w, h, slices, mips, rgba8; unsigned long long slice_pitch_bytes; };
+// One launch of material.hip on the launcher's own arguments (launch_material_fetch), in place on the memory they name: every pixel's stores are those of the kernel
+// (material_fetch_store: only a pixel with a fragment stores).  tests/cpu_product/device.py: the handler of the host-only build.
+int mifx_host_material_fetch_launch(const MaterialFetchK* k, const CamK* cam)
+{
+    const bool atlas = (k->flags & MIFX_MATERIAL_FETCH_FLAG_TEXTURE_ATLAS) != 0u;
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int y = 0; y < k->depth.h; ++y)
+        for (int x = 0; x < k->depth.w; ++x)
+        {
+            if (atlas) material_fetch_store<true>(x, y, *k, *cam);
+            else material_fetch_store<false>(x, y, *k, *cam);
+        }
+    return 0;
+}
 // interpolants: depth (c = 1), uv0, uv1 (c = 2), mesh normal, colour (c = 4), face, material index (c = 1); a null plane is the permutation without it
 // outputs: base colour, normal, material, emissive (c = 4), occlusion (c = 1), clear coat, its normal, sheen, anisotropy, iridescence (c = 4), transmission (c = 1); null = not written
-// materials: material_count records of mifx_pbr_material; the pixel's stores are those of the kernel (material_fetch_store): only a pixel with a fragment stores
+// materials: material_count records of mifx_pbr_material; textures: as the entry takes them once its checks have passed.  The launch above on these arguments.
 int mifx_host_material_fetch(const host_plane* interpolants, const host_plane* outputs, const mifx_pbr_material* materials, int material_count, const host_texture* textures,
                              int texture_count, unsigned layer_flags, unsigned flags, float mip_bias, const mifx_camera_attribs* camera, int reversed_depth)
 {
@@ -24,17 +38,8 @@ int mifx_host_material_fetch(const host_plane* interpolants, const host_plane* o
     for (int i = 0; i < texture_count; ++i)
     {
         const host_texture& t = textures[i];
-        MaterialTexK& o = tex[size_t(i)];
-        std::memset(&o, 0, sizeof(o));
-        o.data = static_cast<const unsigned char*>(t.data);
-        o.slicePitch = t.slice_pitch_bytes;
-        o.w = t.w; o.h = t.h; o.slices = t.slices; o.mips = t.mips; o.rgba8 = t.rgba8 ? 1u : 0u;
-        unsigned off = 0; // (check_material_fetch, material.hip)
-        for (int l = 0; l < t.mips; ++l)
-        {
-            o.levelOffset[l] = off;
-            off += unsigned((t.w >> l) > 1 ? (t.w >> l) : 1) * unsigned((t.h >> l) > 1 ? (t.h >> l) : 1);
-        }
+        tex[size_t(i)] = make_material_texk(mifx_texture_array{t.data, uint32_t(t.w), uint32_t(t.h), uint32_t(t.slices), uint32_t(t.mips),
+                                                               uint32_t(t.rgba8 ? MIFX_NATIVE_FORMAT_RGBA8_UNORM : MIFX_NATIVE_FORMAT_RGBA32_FLOAT), 0u, t.slice_pitch_bytes});
     }
     MaterialFetchK k;
     std::memset(&k, 0, sizeof(k));
@@ -51,14 +56,6 @@ int mifx_host_material_fetch(const host_plane* interpolants, const host_plane* o
     for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
     cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
     cam.reversedDepth = reversed_depth;
-    const bool atlas = (flags & MIFX_MATERIAL_FETCH_FLAG_TEXTURE_ATLAS) != 0u;
-#pragma omp parallel for schedule(dynamic, 4)
-    for (int y = 0; y < k.depth.h; ++y)
-        for (int x = 0; x < k.depth.w; ++x)
-        {
-            if (atlas) material_fetch_store<true>(x, y, k, cam);
-            else material_fetch_store<false>(x, y, k, cam);
-        }
-    return 0;
+    return mifx_host_material_fetch_launch(&k, &cam);
 }
 }

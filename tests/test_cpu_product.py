@@ -47,8 +47,8 @@ def test_the_launcher_stubs_are_what_the_generator_prints():
     marker = [i for i, line in enumerate(lines) if line.startswith("// ---") and "the launchers" in line]
     assert len(marker) == 1, marker
     assert "".join(lines[marker[0] + 1:]) == r.stdout, "stub_device.cpp: re-run tests/cpu_product/gen_stubs.py and paste its output below the marker"
-    assert r.stdout.count("mifx_status launch_") >= 69  # (the 56 launchers of mifx_host.h and the thirteen of the mifx_*_host.h headers)
-    assert "mifx_status launch_oit_shade_blend(" in r.stdout
+    assert r.stdout.count("mifx_status launch_") >= 70  # (the 56 launchers of mifx_host.h and the fourteen of the mifx_*_host.h headers)
+    assert "mifx_status launch_oit_shade_blend(" in r.stdout and "mifx_status launch_material_fetch(" in r.stdout
 
 
 def test_the_shadow_map_conversion_is_linked_and_refused_at_its_first_launch(cpu_lib):
@@ -268,3 +268,11 @@ def test_the_host_only_build_runs_the_shade_blend_entry(cpu_lib):
     plane, without and with two shadow-mapped lights."""
     assert "cpu product: feature values OK: the host-only build runs mifx_oit_shade_blend" in run(cpu_lib, "feature_values", "entry", timeout=900)
 
+
+
+def test_the_host_only_build_runs_the_material_fetch_entry(cpu_lib):
+    """mifx_pbr_material_fetch (api_material.cpp; its launcher is one of the generated stand-ins) as shipped, on ONE context through six fixture cases: the same tables twice,
+    other and larger tables, the first again, a 1x1 frame.  Every call's output planes equal the same compiled body run on the case's own arrays bit for bit, sentinels kept
+    where no fragment is; the context waits for its stream and uploads exactly where the tables differ from the call before.  Inside a row band and with a texture index
+    outside the table the entry answers with the status and the message it always had."""
+    assert "cpu product: scenario OK: the host-only build runs mifx_pbr_material_fetch" in run(cpu_lib, "material_fetch", timeout=900)

@@ -176,3 +176,37 @@ def test_refusals_reach_python_with_a_message(mifx_lib):
     with pytest.raises(B.MifxError, match="outside the texture table"):
         api.pbr_material_fetch(ctx, interp, mats, textures, cam)
     ctx.close()
+
+
+# the same tables twice, other and larger tables, the first again, a 1x1 frame (tests/cpu_product/run.py material_fetch runs the same sequence on the host code alone)
+SEQUENCE = ("a_minified", "a_minified", "o_three_materials", "m_every_layer_rgba8", "a_minified", "p_frame_1x1")
+
+
+def test_one_context_serves_calls_with_different_tables(mifx_lib):
+    """SEQUENCE on one context, every call into output planes of its own, queued without a host synchronisation in between (the entry itself waits for the stream before it
+    overwrites the tables a call queued earlier may still read) and one at the end: each call's planes equal the same case on a fresh context bit for bit -- the same kernel
+    on the same inputs, so the tables the context holds are all that could differ"""
+    from diligentfx_amd import api, binding as B
+
+    ctx = make_ctx(BY_NAME[SEQUENCE[0]])
+    inputs = {n: device_inputs(BY_NAME[n], ctx.device) for n in set(SEQUENCE)}  # (made once a case: a repeated case hands the entry the very same tables)
+    planes = [caller_planes(BY_NAME[n], ctx.device) for n in SEQUENCE]
+    got = []
+    for n, (g, ly) in zip(SEQUENCE, planes):
+        c = BY_NAME[n]
+        interp, mats, textures = inputs[n]
+        got.append(api.pbr_material_fetch(ctx, interp, mats, textures, B.camera_from_bytes(c["camera"].tobytes()), layer_flags=c["layers"], flags=c["flags"], mip_bias=c["mip_bias"],
+                                          gbuffer=g, layers=ly))
+    torch.cuda.synchronize()
+    want = {}
+    for n in set(SEQUENCE):
+        fresh = make_ctx(BY_NAME[n])
+        want[n] = fetch(fresh, BY_NAME[n])
+        fresh.close()
+    for step, (n, (g, ly)) in enumerate(zip(SEQUENCE, got)):
+        wg, wl = want[n]
+        assert set(g) == set(wg) and set(ly) == set(wl) and set(g) | set(ly) == set(M.output_names(BY_NAME[n])) | {"depth"}
+        for name, t in {**g, **ly}.items():
+            if name != "depth":
+                assert torch.equal(t.view(torch.int32), {**wg, **wl}[name].view(torch.int32)), f"call {step} ({n}): {name} differs from the run on a fresh context"
+    ctx.close()
