@@ -111,22 +111,6 @@ mifx_status to_img_wh(const mifx_image2d* im, uint32_t fmt, uint32_t w, uint32_t
     return MIFX_OK;
 }
 
-CamK make_camk(const mifx_camera_attribs& c, bool reversedDepth)
-{
-    CamK k;
-    std::memcpy(k.view.m, c.mView, 64);
-    std::memcpy(k.proj.m, c.mProj, 64);
-    std::memcpy(k.viewProj.m, c.mViewProj, 64);
-    std::memcpy(k.viewInv.m, c.mViewInv, 64);
-    std::memcpy(k.viewProjInv.m, c.mViewProjInv, 64);
-    k.pos[0] = c.f4Position[0]; k.pos[1] = c.f4Position[1]; k.pos[2] = c.f4Position[2];
-    k.vw = c.f4ViewportSize[0]; k.vh = c.f4ViewportSize[1]; k.ivw = c.f4ViewportSize[2]; k.ivh = c.f4ViewportSize[3];
-    k.jx = c.f2Jitter[0]; k.jy = c.f2Jitter[1];
-    k.frameIndex = c.uiFrameIndex;
-    k.reversedDepth = reversedDepth ? 1 : 0;
-    return k;
-}
-
 mifx_status Plane::alloc(uint32_t width, uint32_t height, uint32_t format)
 {
     format = storage_format(format);

@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstring>
+#include "mifx.h"
 
 namespace mifx
 {
@@ -223,6 +225,22 @@ struct CamK
     uint32_t frameIndex;
     int      reversedDepth; // PostFXContext::FEATURE_FLAG_REVERSED_DEPTH: near plane = depth 1, far plane / background = depth 0
 };
+// the one definition of the block: every launcher and every host compilation of a kernel body (tests/host_kernels) builds its CamK here
+inline CamK make_camk(const mifx_camera_attribs& c, bool reversedDepth = false)
+{
+    CamK k;
+    std::memcpy(k.view.m, c.mView, 64);
+    std::memcpy(k.proj.m, c.mProj, 64);
+    std::memcpy(k.viewProj.m, c.mViewProj, 64);
+    std::memcpy(k.viewInv.m, c.mViewInv, 64);
+    std::memcpy(k.viewProjInv.m, c.mViewProjInv, 64);
+    k.pos[0] = c.f4Position[0]; k.pos[1] = c.f4Position[1]; k.pos[2] = c.f4Position[2];
+    k.vw = c.f4ViewportSize[0]; k.vh = c.f4ViewportSize[1]; k.ivw = c.f4ViewportSize[2]; k.ivh = c.f4ViewportSize[3];
+    k.jx = c.f2Jitter[0]; k.jy = c.f2Jitter[1];
+    k.frameIndex = c.uiFrameIndex;
+    k.reversedDepth = reversedDepth ? 1 : 0;
+    return k;
+}
 
 // ------------------------------------------------------------------------------------------------ D3D/Vulkan conventions
 MIFX_HD v2 ndc_to_uv(v2 xy) { return v2{0.5f + 0.5f * xy.x, 0.5f - 0.5f * xy.y}; }   // NormalizedDeviceXYToTexUV

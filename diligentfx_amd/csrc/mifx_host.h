@@ -122,8 +122,6 @@ inline uint32_t storage_format(uint32_t fmt)
 mifx_status to_img(const mifx_image2d* im, uint32_t fmt, const char* what, Img& out);
 mifx_status to_img_wh(const mifx_image2d* im, uint32_t fmt, uint32_t w, uint32_t h, const char* what, Img& out);
 
-CamK make_camk(const mifx_camera_attribs& c, bool reversedDepth = false);
-
 // an owned pitched plane in HBM (row pitch aligned to 256 B)
 struct Plane
 {

@@ -421,5 +421,18 @@ struct ShadeK
     float background[4];
     int   workflow; // MIFX_PBR_WORKFLOW_*
 };
+// copies a.LightCount lights: the count must lie within MIFX_PBR_MAX_LIGHTS (the launchers' light check; the hit fetch makes none of its own and relies on that of
+// the shade of the same frame); background == nullptr: zeros
+inline ShadeK make_shadek(const mifx_pbr_shade_attribs& a, const float background[4])
+{
+    ShadeK k{};
+    k.iblScale[0] = a.IBLScale[0]; k.iblScale[1] = a.IBLScale[1]; k.iblScale[2] = a.IBLScale[2];
+    k.occlusionStrength = a.OcclusionStrength; k.emissionScale = a.EmissionScale; k.prefilteredCubeLastMip = a.PrefilteredCubeLastMip;
+    k.lightCount = a.LightCount;
+    k.workflow   = a.Workflow;
+    for (int i = 0; i < a.LightCount; ++i) k.lights[i] = a.Lights[i];
+    for (int i = 0; i < 4; ++i) k.background[i] = background ? background[i] : 0.0f;
+    return k;
+}
 
 } // namespace mifx

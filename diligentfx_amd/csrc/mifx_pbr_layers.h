@@ -8,6 +8,7 @@
 // Operations are written in the reference's order: the checker is the reference's own source.
 #pragma once
 #include "mifx_pbr.h"
+#include <cmath>
 
 namespace mifx
 {
@@ -207,6 +208,17 @@ struct LayersK
     Img      clearcoat, clearcoatNormal, sheen, anisotropy, tangent, iridescence, transmission;
     LutK     albedoScaling, charlie;
 };
+// the scalars of a layer set; those of a layer that is off stay as they are (zero in a fresh block: nothing reads them)
+inline void set_layer_scalars(LayersK& ly, unsigned flags, float iridescenceIor, float anisotropyRotation)
+{
+    ly.flags = flags;
+    if (flags & MIFX_PBR_LAYER_IRIDESCENCE) ly.iridescenceIor = iridescenceIor;
+    if (flags & MIFX_PBR_LAYER_ANISOTROPY)
+    {
+        ly.rotationCos = std::cos(anisotropyRotation); // float overloads: the shader's cos / sin of a per-material constant (RenderPBR.psh:263)
+        ly.rotationSin = std::sin(anisotropyRotation);
+    }
+}
 // One pixel of the shade with material layers (the body of pbr_shade_layers_kernel and of the sharded hit fetch pbr_hit_fetch_layers_kernel, pbr.hip): colour and
 // specular IBL of pixel (x, y), nothing stored.  APRON: the cube maps are the apron copies of cube_apron_kernel (the kernel);
 // false = plain face arrays (tests/host_kernels compiles this function for the host and runs it without the copies).

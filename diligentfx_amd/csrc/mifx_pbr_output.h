@@ -21,6 +21,23 @@ struct OutputK
     float    color0[3], color1[3];
     float    sceneNearZ, sceneFarZ; // g_Frame.Camera.fSceneNearZ / fSceneFarZ (:605-606)
 };
+// the block of a desc that has passed check_shade_output_desc (api_pbr.cpp: `renderer` is set); its two planes are the caller's to bind
+inline OutputK make_outputk(const mifx_pbr_shade_output_desc& d, const mifx_camera_attribs& camera, bool hasMotion, bool hasMeshNormal)
+{
+    const mifx_pbr_renderer_shader_parameters& r = *d.renderer;
+    OutputK o{};
+    o.debugView = d.debug_view; o.loadingAnimation = d.loading_animation; o.alphaMode = d.alpha_mode; o.unlit = d.unlit != 0;
+    o.srgb = (d.flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0u;
+    o.hasMotion = hasMotion; o.hasMeshNormal = hasMeshNormal;
+    o.alphaMaskCutoff = d.alpha_mask_cutoff;
+    o.tm = ToneMapK{r.MiddleGray, r.WhitePoint, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, r.AverageLogLum, 0};
+    for (int i = 0; i < 4; ++i) o.highlight[i] = r.HighlightColor[i];
+    o.time = r.Time; o.worldScale = r.LoadingAnimation.WorldScale; o.speed = r.LoadingAnimation.Speed;
+    o.factor = d.loading_animation == MIFX_PBR_LOADING_ANIMATION_TRANSITIONING ? r.LoadingAnimation.Factor : 1.0f; // RenderPBR.psh:617-622
+    for (int i = 0; i < 3; ++i) { o.color0[i] = r.LoadingAnimation.Color0[i]; o.color1[i] = r.LoadingAnimation.Color1[i]; }
+    o.sceneNearZ = camera.fSceneNearZ; o.sceneFarZ = camera.fSceneFarZ;
+    return o;
+}
 
 // GetLoadingAnimationColor (RenderPBR.psh:361-386)
 MIFX_D v4 loading_animation_color(v3 worldPos, float factor, const OutputK& o)

@@ -412,12 +412,7 @@ static mifx_status make_shade_constants(hipStream_t s, IblApronCache& cache, con
     MIFX_CHECK(make_lutk(ibl->brdf_lut, lut));
     MIFX_CHECK(make_cubek(ibl->irradiance, "ibl.irradiance", irr));
     MIFX_CHECK(make_cubek(ibl->prefiltered, "ibl.prefiltered", pre));
-    k.iblScale[0] = a.IBLScale[0]; k.iblScale[1] = a.IBLScale[1]; k.iblScale[2] = a.IBLScale[2];
-    k.occlusionStrength = a.OcclusionStrength; k.emissionScale = a.EmissionScale; k.prefilteredCubeLastMip = a.PrefilteredCubeLastMip;
-    k.lightCount = a.LightCount;
-    k.workflow   = a.Workflow;
-    for (int i = 0; i < a.LightCount; ++i) k.lights[i] = a.Lights[i];
-    for (int i = 0; i < 4; ++i) k.background[i] = background ? background[i] : 0.0f;
+    k = make_shadek(a, background);
     if (checkOnly) return MIFX_OK;
     // working copies with face aprons (8.3 MB for a 256^2 prefiltered cube: ~10 us per call, repaid many times over in the shade kernel)
     const size_t irrBytes = apron_bytes(irr.size, 1), preBytes = apron_bytes(pre.size, pre.mips);
@@ -465,18 +460,6 @@ static mifx_status make_shadowk(const mifx_pbr_shadows& shadows, ShadowK& sh)
     return MIFX_OK;
 }
 
-// the G-buffer planes of a W x H shade, and its specular-IBL target where there is one (the launchers of the fp32 planes share the checks and their order)
-static mifx_status bind_gbuffer(const mifx_gbuffer* g, const mifx_image2d* out_spec, uint32_t W, uint32_t H, Img& bc, Img& nrm, Img& mat, Img& depth, Img& emis, Img& occ, Img& outS)
-{
-    MIFX_CHECK(to_img_wh(g->base_color, MIFX_FORMAT_F32X4, W, H, "gbuffer.base_color", bc));
-    MIFX_CHECK(to_img_wh(g->normal, MIFX_FORMAT_F32X4, W, H, "gbuffer.normal", nrm));
-    MIFX_CHECK(to_img_wh(g->material, MIFX_FORMAT_F32X4, W, H, "gbuffer.material", mat));
-    MIFX_CHECK(to_img_wh(g->depth, MIFX_FORMAT_F32, W, H, "gbuffer.depth", depth));
-    if (g->emissive) MIFX_CHECK(to_img_wh(g->emissive, MIFX_FORMAT_F32X4, W, H, "gbuffer.emissive", emis));
-    if (g->occlusion) MIFX_CHECK(to_img_wh(g->occlusion, MIFX_FORMAT_F32, W, H, "gbuffer.occlusion", occ));
-    if (out_spec) MIFX_CHECK(to_img_wh(out_spec, MIFX_FORMAT_F32X4, W, H, "out_specular_ibl", outS));
-    return MIFX_OK;
-}
 // the lights of a shade; `entry` = what the message names as the way to hand shadow maps in
 static mifx_status check_lights(const mifx_pbr_shade_attribs& a, const mifx_pbr_shadows* shadows, const char* entry)
 {
@@ -491,40 +474,78 @@ static mifx_status check_lights(const mifx_pbr_shade_attribs& a, const mifx_pbr_
     return MIFX_OK;
 }
 
+// What every shade kernel of the fp32 planes is handed, bound in the order the launchers have always checked in: the planes (bind_shade_planes), the lights and the
+// shadow maps (bind_lights), then -- behind the layer planes of the layered launchers -- the IBL, the constant block and the camera (bind_shade_constants).
+struct ShadeInputs
+{
+    Img     bc, nrm, mat, depth, emis{}, occ{};
+    int     hasEmissive, hasAo;
+    LutK    lut;
+    CubeK   irr, pre;
+    ShadeK  k;
+    CamK    cam;
+    ShadowK sh{};
+};
+#define MIFX_SHADE_INPUTS(in) in.bc, in.nrm, in.mat, in.depth, in.emis, in.occ, in.lut, in.irr, in.pre // (the head of every shade kernel's argument list)
+// INSTANCE(E, A, S) with the three as constants: the kernels' HAS_EMISSIVE, HAS_AO and WRITE_SPEC
+#define MIFX_SHADE_DISPATCH(e, a, s, INSTANCE)             \
+    switch (((e) ? 4 : 0) | ((a) ? 2 : 0) | ((s) ? 1 : 0)) \
+    {                                                      \
+        case 0: INSTANCE(false, false, false); break;      \
+        case 1: INSTANCE(false, false, true); break;       \
+        case 2: INSTANCE(false, true, false); break;       \
+        case 3: INSTANCE(false, true, true); break;        \
+        case 4: INSTANCE(true, false, false); break;       \
+        case 5: INSTANCE(true, false, true); break;        \
+        case 6: INSTANCE(true, true, false); break;        \
+        default: INSTANCE(true, true, true); break;        \
+    }
+// the G-buffer planes of a W x H shade and its specular-IBL target where there is one
+static mifx_status bind_shade_planes(const mifx_gbuffer* g, const mifx_image2d* out_spec, uint32_t W, uint32_t H, ShadeInputs& in, Img& outS)
+{
+    MIFX_CHECK(to_img_wh(g->base_color, MIFX_FORMAT_F32X4, W, H, "gbuffer.base_color", in.bc));
+    MIFX_CHECK(to_img_wh(g->normal, MIFX_FORMAT_F32X4, W, H, "gbuffer.normal", in.nrm));
+    MIFX_CHECK(to_img_wh(g->material, MIFX_FORMAT_F32X4, W, H, "gbuffer.material", in.mat));
+    MIFX_CHECK(to_img_wh(g->depth, MIFX_FORMAT_F32, W, H, "gbuffer.depth", in.depth));
+    if (g->emissive) MIFX_CHECK(to_img_wh(g->emissive, MIFX_FORMAT_F32X4, W, H, "gbuffer.emissive", in.emis));
+    if (g->occlusion) MIFX_CHECK(to_img_wh(g->occlusion, MIFX_FORMAT_F32, W, H, "gbuffer.occlusion", in.occ));
+    if (out_spec) MIFX_CHECK(to_img_wh(out_spec, MIFX_FORMAT_F32X4, W, H, "out_specular_ibl", outS));
+    in.hasEmissive = g->emissive ? 1 : 0; in.hasAo = g->occlusion ? 1 : 0;
+    return MIFX_OK;
+}
+// the lights and the shadow maps (not the hit fetch's: the shade of the same frame has looked at them)
+static mifx_status bind_lights(const mifx_pbr_shade_attribs& a, const mifx_pbr_shadows* shadows, const char* entry, ShadowK& sh)
+{
+    MIFX_CHECK(check_lights(a, shadows, entry));
+    if (shadows != nullptr) MIFX_CHECK(make_shadowk(*shadows, sh));
+    return MIFX_OK;
+}
+static mifx_status bind_shade_constants(hipStream_t s, IblApronCache& iblApron, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4],
+                                        const mifx_camera_attribs& camera, bool reversedDepth, ShadeInputs& in, bool checkOnly = false)
+{
+    MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, in.lut, in.irr, in.pre, in.k, checkOnly));
+    in.cam = make_camk(camera, reversedDepth);
+    return MIFX_OK;
+}
+
 mifx_status launch_pbr_shade(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                              const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth,
                              const mifx_pbr_shadows* shadows, const SsrMaskOut* ssrMask)
 {
     MIFX_REQUIRE(ssrMask == nullptr || shadows == nullptr, "launch_pbr_shade: the SSR mask output is not combined with the shadowed permutation");
     const SsrMaskOut r2 = ssrMask ? *ssrMask : SsrMaskOut{};
-    Img bc, nrm, mat, depth, emis{}, occ{}, outR, outS{};
+    Img outR, outS{};
     MIFX_CHECK(to_img(out_radiance, MIFX_FORMAT_F32X4, "out_radiance", outR));
     outR = rows_of(outR, row_begin, row_end);
-    MIFX_CHECK(bind_gbuffer(g, out_spec, out_radiance->width, out_radiance->height, bc, nrm, mat, depth, emis, occ, outS));
-    MIFX_CHECK(check_lights(a, shadows, "mifx_pbr_shade_execute_with_shadows"));
-    ShadowK sh{};
-    if (shadows != nullptr) MIFX_CHECK(make_shadowk(*shadows, sh));
-    LutK lut;
-    CubeK irr, pre;
-    ShadeK k{};
-    MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k));
-    const CamK cam = make_camk(camera, reversedDepth);
+    ShadeInputs in;
+    MIFX_CHECK(bind_shade_planes(g, out_spec, out_radiance->width, out_radiance->height, in, outS));
+    MIFX_CHECK(bind_lights(a, shadows, "mifx_pbr_shade_execute_with_shadows", in.sh));
+    MIFX_CHECK(bind_shade_constants(s, iblApron, a, ibl, background, camera, reversedDepth, in));
     const dim3 block(64, 4, 1), grid = grid2d(outR, block);
-#define MIFX_SHADE(E, A, S)                                                                                                                                  \
-    if (shadows) hipLaunchKernelGGL((pbr_shade_shadowed_kernel<E, A, S>), grid, block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, outR, outS, cam, k, sh); \
-    else hipLaunchKernelGGL((pbr_shade_kernel<E, A, S>), grid, block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, outR, outS, cam, k, r2)
-    const int sel = (g->emissive ? 4 : 0) | (g->occlusion ? 2 : 0) | (out_spec ? 1 : 0);
-    switch (sel)
-    {
-        case 0: MIFX_SHADE(false, false, false); break;
-        case 1: MIFX_SHADE(false, false, true); break;
-        case 2: MIFX_SHADE(false, true, false); break;
-        case 3: MIFX_SHADE(false, true, true); break;
-        case 4: MIFX_SHADE(true, false, false); break;
-        case 5: MIFX_SHADE(true, false, true); break;
-        case 6: MIFX_SHADE(true, true, false); break;
-        default: MIFX_SHADE(true, true, true); break;
-    }
+#define MIFX_SHADE(E, A, S)                                                                                                                           \
+    if (shadows) hipLaunchKernelGGL((pbr_shade_shadowed_kernel<E, A, S>), grid, block, 0, s, MIFX_SHADE_INPUTS(in), outR, outS, in.cam, in.k, in.sh); \
+    else hipLaunchKernelGGL((pbr_shade_kernel<E, A, S>), grid, block, 0, s, MIFX_SHADE_INPUTS(in), outR, outS, in.cam, in.k, r2)
+    MIFX_SHADE_DISPATCH(in.hasEmissive, in.hasAo, out_spec, MIFX_SHADE)
 #undef MIFX_SHADE
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
@@ -544,36 +565,18 @@ static mifx_status make_lutk_r(const mifx_image2d* im, const char* what, LutK& k
     k.pitch_f = int(im->pitch_bytes / 4u);
     return MIFX_OK;
 }
-// output != nullptr: the shade's output stage behind the layered body (launch_pbr_shade_output; `out_radiance` is then PSOut.Color), with the footer's four planes where
-// `targets` is given (`out_spec` is then null); both validated by the entries (api_pbr.cpp).
-// oit != nullptr: one transparent draw shaded and blended (launch_oit_shade_blend): `g` is the draw's G-buffer, the frame is the OIT object's, nothing is written but the
-// four targets (`out_radiance`, `out_spec` are null); checkOnly stops behind the last argument check, in front of the first device call
-struct OitShadeBlend
-{
-    const OitK&         k;
-    const OitTargetsK&  targets;
-    const mifx_image2d* colorAlpha;
-    bool                checkOnly;
-};
-static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
-                                                const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance,
-                                                const mifx_image2d* out_spec, int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows,
-                                                const LayeredHitFetch* hit, const mifx_pbr_shade_output_desc* output, const mifx_pbr_targets* targets,
-                                                const OitShadeBlend* oit = nullptr)
+// The layered launchers refuse in one order: unknown layer flag bits, the plane written, (hit fetch) the frame limit, bind_shade_planes, bind_lights, bind_layers,
+// (OIT) the slice's colour alpha, bind_shade_constants, (output stage) its own planes.
+static mifx_status check_layer_flags(const mifx_pbr_layers& layers)
 {
     const uint32_t known = MIFX_PBR_LAYER_CLEAR_COAT | MIFX_PBR_LAYER_SHEEN | MIFX_PBR_LAYER_ANISOTROPY | MIFX_PBR_LAYER_IRIDESCENCE | MIFX_PBR_LAYER_TRANSMISSION;
     MIFX_REQUIRE((layers.flags & ~known) == 0u, "layers: unknown flag bits 0x%x", layers.flags & ~known);
-    Img bc, nrm, mat, depth, emis{}, occ{}, outR, outS{};
-    if (oit == nullptr) MIFX_CHECK(to_img(out_radiance, MIFX_FORMAT_F32X4, "out_radiance", outR)); // (hit fetch: the plane the band's rows were shaded into)
-    if (hit == nullptr && oit == nullptr) outR = rows_of(outR, row_begin, row_end);
-    const uint32_t W = oit ? uint32_t(oit->k.w) : out_radiance->width, H = oit ? uint32_t(oit->k.h) : out_radiance->height;
-    if (hit != nullptr) MIFX_REQUIRE(W <= 65536u && H <= 65536u, "launch_pbr_shade_layers: frame %ux%u exceeds the 16-bit hit coordinates", W, H);
-    MIFX_CHECK(bind_gbuffer(g, out_spec, W, H, bc, nrm, mat, depth, emis, occ, outS));
-    MIFX_CHECK(check_lights(a, shadows, "`shadows`"));
-    ShadowK sh{};
-    if (shadows != nullptr) MIFX_CHECK(make_shadowk(*shadows, sh));
-    LayersK ly{};
-    ly.flags = layers.flags;
+    return MIFX_OK;
+}
+// the planes, tables and scalars of a checked layer set for a W x H shade
+static mifx_status bind_layers(const mifx_pbr_layers& layers, uint32_t W, uint32_t H, LayersK& ly)
+{
+    set_layer_scalars(ly, layers.flags, layers.iridescence_ior, layers.anisotropy_rotation);
     if (layers.flags & MIFX_PBR_LAYER_CLEAR_COAT)
     {
         MIFX_CHECK(to_img_wh(layers.clearcoat, MIFX_FORMAT_F32X4, W, H, "layers.clearcoat", ly.clearcoat));
@@ -590,157 +593,162 @@ static mifx_status launch_pbr_shade_layers_impl(hipStream_t s, IblApronCache& ib
     {
         MIFX_CHECK(to_img_wh(layers.anisotropy, MIFX_FORMAT_F32X4, W, H, "layers.anisotropy", ly.anisotropy));
         if (layers.tangent) MIFX_CHECK(to_img_wh(layers.tangent, MIFX_FORMAT_F32X4, W, H, "layers.tangent", ly.tangent));
-        ly.hasTangent  = layers.tangent != nullptr;
-        ly.rotationCos = std::cos(layers.anisotropy_rotation); // float overloads: the shader's cos / sin of a per-material constant (RenderPBR.psh:263)
-        ly.rotationSin = std::sin(layers.anisotropy_rotation);
+        ly.hasTangent = layers.tangent != nullptr;
     }
     if (layers.flags & MIFX_PBR_LAYER_IRIDESCENCE)
     {
         MIFX_CHECK(to_img_wh(layers.iridescence, MIFX_FORMAT_F32X4, W, H, "layers.iridescence", ly.iridescence));
         MIFX_REQUIRE(layers.iridescence_ior > 0.0f, "layers.iridescence_ior %g", double(layers.iridescence_ior));
-        ly.iridescenceIor = layers.iridescence_ior;
     }
     if (layers.flags & MIFX_PBR_LAYER_TRANSMISSION) MIFX_CHECK(to_img_wh(layers.transmission, MIFX_FORMAT_F32, W, H, "layers.transmission", ly.transmission));
-    LutK lut;
-    CubeK irr, pre;
-    ShadeK k{};
-    Img alpha{};
-    if (oit != nullptr && oit->colorAlpha != nullptr) MIFX_CHECK(to_img_wh(oit->colorAlpha, MIFX_FORMAT_F32, W, H, "slice color_alpha", alpha));
-    MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k, oit != nullptr && oit->checkOnly));
-    if (oit != nullptr && oit->checkOnly) return MIFX_OK;
-    const CamK cam = make_camk(camera, reversedDepth);
-    const dim3 block(64, 4, 1);
-    if (oit != nullptr)
-    {
-#ifndef MIFX_STORAGE_H4
-        const OitShadeSliceK slice{bc, nrm, mat, depth, emis, occ, alpha, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, oit->colorAlpha ? 1 : 0};
-        hipLaunchKernelGGL(shadows ? oit_shade_blend_kernel<true> : oit_shade_blend_kernel<false>, grid2d(int(W), int(H), block), block, 0, s, slice, lut, irr, pre, cam, k, ly, sh, oit->k,
-                           oit->targets);
-#else
-        MIFX_REQUIRE(false, "mifx_oit_shade_blend: not part of the native-storage build");
-#endif
-    }
-    else if (output != nullptr)
-    {
-#ifndef MIFX_STORAGE_H4
-        Img motion{}, meshNormal{};
-        if (output->motion) MIFX_CHECK(to_img_wh(output->motion, MIFX_FORMAT_F32X2, W, H, "output.motion", motion));
-        if (output->mesh_normal) MIFX_CHECK(to_img_wh(output->mesh_normal, MIFX_FORMAT_F32X4, W, H, "output.mesh_normal", meshNormal));
-        const mifx_pbr_renderer_shader_parameters& r = *output->renderer;
-        OutputK o{};
-        o.debugView = output->debug_view; o.loadingAnimation = output->loading_animation; o.alphaMode = output->alpha_mode; o.unlit = output->unlit != 0;
-        o.srgb = (output->flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0u;
-        o.hasMotion = output->motion != nullptr; o.hasMeshNormal = output->mesh_normal != nullptr;
-        o.alphaMaskCutoff = output->alpha_mask_cutoff;
-        o.tm = ToneMapK{r.MiddleGray, r.WhitePoint, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, r.AverageLogLum, 0};
-        for (int i = 0; i < 4; ++i) o.highlight[i] = r.HighlightColor[i];
-        o.time = r.Time; o.worldScale = r.LoadingAnimation.WorldScale; o.speed = r.LoadingAnimation.Speed;
-        o.factor = output->loading_animation == MIFX_PBR_LOADING_ANIMATION_TRANSITIONING ? r.LoadingAnimation.Factor : 1.0f; // RenderPBR.psh:617-622
-        for (int i = 0; i < 3; ++i) { o.color0[i] = r.LoadingAnimation.Color0[i]; o.color1[i] = r.LoadingAnimation.Color1[i]; }
-        o.sceneNearZ = camera.fSceneNearZ; o.sceneFarZ = camera.fSceneFarZ;
-#define MIFX_OUTPUT_INSTANCE(TM)                                                                                                                                                     \
-    hipLaunchKernelGGL((shadows ? pbr_shade_output_kernel<TM, true> : pbr_shade_output_kernel<TM, false>), grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, \
-                       outR, outS, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, out_spec ? 1 : 0, sh, o, motion, meshNormal)
-#define MIFX_TARGETS_INSTANCE(TM)                                                                                                                                                      \
-    hipLaunchKernelGGL((shadows ? pbr_shade_targets_kernel<TM, true> : pbr_shade_targets_kernel<TM, false>), grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, \
-                       outR, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, sh, o, motion, meshNormal, tg)
-        if (targets != nullptr)
-        {
-            TargetsK tg{};
-            MIFX_CHECK(to_img_wh(targets->normal, MIFX_FORMAT_F32X4, W, H, "targets.normal", tg.normal));
-            MIFX_CHECK(to_img_wh(targets->base_color, MIFX_FORMAT_F32X4, W, H, "targets.base_color", tg.baseColor));
-            MIFX_CHECK(to_img_wh(targets->material, MIFX_FORMAT_F32X4, W, H, "targets.material", tg.material));
-            MIFX_CHECK(to_img_wh(targets->ibl, MIFX_FORMAT_F32X4, W, H, "targets.ibl", tg.ibl));
-            tg.animationFactor = r.LoadingAnimation.Factor;
-            MIFX_TONEMAP_DISPATCH(output->tone_mapping_mode, MIFX_TARGETS_INSTANCE)
-        }
-        else
-        {
-            MIFX_TONEMAP_DISPATCH(output->tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
-        }
-#undef MIFX_TARGETS_INSTANCE
-#undef MIFX_OUTPUT_INSTANCE
-#else
-        MIFX_REQUIRE(false, "mifx_pbr_shade_output: the output stage is not part of the native-storage build");
-#endif
-    }
-    else if (hit != nullptr)
-    {
-        const HitOut out{hit->rays, hit->coords, outR, hit->shadedBegin, hit->shadedEnd};
-        hipLaunchKernelGGL(shadows ? pbr_hit_fetch_layers_kernel<true> : pbr_hit_fetch_layers_kernel<false>, grid2d(hit->rays, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr,
-                           pre, out, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0, sh);
-    }
-    else
-    {
-        // each single layer and all five have an instance of their own; any other set takes the run-time one (MIFX_LAYERS_GENERIC=1 forces it: A/B, tests)
-        static const bool generic = [] { const char* e = std::getenv("MIFX_LAYERS_GENERIC"); return e && std::atoi(e) != 0; }();
-#define MIFX_LAYERS_INSTANCE(SET) (shadows ? pbr_shade_layers_kernel<SET, true> : pbr_shade_layers_kernel<SET, false>)
-        auto* kernel = MIFX_LAYERS_INSTANCE(kLayersRuntime);
-        if (!generic) switch (layers.flags)
-        {
-            case MIFX_PBR_LAYER_CLEAR_COAT: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_CLEAR_COAT); break;
-            case MIFX_PBR_LAYER_SHEEN: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_SHEEN); break;
-            case MIFX_PBR_LAYER_ANISOTROPY: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_ANISOTROPY); break;
-            case MIFX_PBR_LAYER_IRIDESCENCE: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_IRIDESCENCE); break;
-            case MIFX_PBR_LAYER_TRANSMISSION: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_TRANSMISSION); break;
-            case 31u: kernel = MIFX_LAYERS_INSTANCE(31u); break;
-            default: break;
-        }
-#undef MIFX_LAYERS_INSTANCE
-        hipLaunchKernelGGL(kernel, grid2d(outR, block), block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, outR, outS, cam, k, ly, g->emissive ? 1 : 0, g->occlusion ? 1 : 0,
-                           out_spec ? 1 : 0, sh);
-    }
-    MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
 }
 
+// launch_pbr_shade_layers over the rows of a frame (its other tail, the hit fetch, is one launch)
+static mifx_status launch_layers_frame(hipStream_t s, const ShadeInputs& in, const LayersK& ly, Img outR, Img outS, int writeSpec, bool shadows)
+{
+    // each single layer and all five have an instance of their own; any other set takes the run-time one (MIFX_LAYERS_GENERIC=1 forces it: A/B, tests)
+    static const bool generic = [] { const char* e = std::getenv("MIFX_LAYERS_GENERIC"); return e && std::atoi(e) != 0; }();
+#define MIFX_LAYERS_INSTANCE(SET) (shadows ? pbr_shade_layers_kernel<SET, true> : pbr_shade_layers_kernel<SET, false>)
+    auto* kernel = MIFX_LAYERS_INSTANCE(kLayersRuntime);
+    if (!generic) switch (ly.flags)
+    {
+        case MIFX_PBR_LAYER_CLEAR_COAT: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_CLEAR_COAT); break;
+        case MIFX_PBR_LAYER_SHEEN: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_SHEEN); break;
+        case MIFX_PBR_LAYER_ANISOTROPY: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_ANISOTROPY); break;
+        case MIFX_PBR_LAYER_IRIDESCENCE: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_IRIDESCENCE); break;
+        case MIFX_PBR_LAYER_TRANSMISSION: kernel = MIFX_LAYERS_INSTANCE(MIFX_PBR_LAYER_TRANSMISSION); break;
+        case 31u: kernel = MIFX_LAYERS_INSTANCE(31u); break;
+        default: break;
+    }
+#undef MIFX_LAYERS_INSTANCE
+    const dim3 block(64, 4, 1);
+    hipLaunchKernelGGL(kernel, grid2d(outR, block), block, 0, s, MIFX_SHADE_INPUTS(in), outR, outS, in.cam, in.k, ly, in.hasEmissive, in.hasAo, writeSpec, in.sh);
+    MIFX_HIP_CHECK(hipGetLastError());
+    return MIFX_OK;
+}
 mifx_status launch_pbr_shade_layers(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers& layers, const mifx_camera_attribs& camera,
                                     const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_radiance, const mifx_image2d* out_spec,
                                     int row_begin, int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const LayeredHitFetch* hit)
 {
-    return launch_pbr_shade_layers_impl(s, iblApron, g, layers, camera, a, ibl, background, out_radiance, out_spec, row_begin, row_end, reversedDepth, shadows, hit, nullptr, nullptr);
+    MIFX_CHECK(check_layer_flags(layers));
+    Img outR, outS{};
+    MIFX_CHECK(to_img(out_radiance, MIFX_FORMAT_F32X4, "out_radiance", outR)); // (hit fetch: the plane the band's rows were shaded into)
+    const uint32_t W = out_radiance->width, H = out_radiance->height;
+    if (hit != nullptr) MIFX_REQUIRE(W <= 65536u && H <= 65536u, "launch_pbr_shade_layers: frame %ux%u exceeds the 16-bit hit coordinates", W, H);
+    ShadeInputs in;
+    LayersK     ly{};
+    MIFX_CHECK(bind_shade_planes(g, out_spec, W, H, in, outS));
+    MIFX_CHECK(bind_lights(a, shadows, "`shadows`", in.sh));
+    MIFX_CHECK(bind_layers(layers, W, H, ly));
+    MIFX_CHECK(bind_shade_constants(s, iblApron, a, ibl, background, camera, reversedDepth, in));
+    if (hit == nullptr) return launch_layers_frame(s, in, ly, rows_of(outR, row_begin, row_end), outS, out_spec ? 1 : 0, shadows != nullptr);
+    const HitOut out{hit->rays, hit->coords, outR, hit->shadedBegin, hit->shadedEnd};
+    const dim3   block(64, 4, 1);
+    hipLaunchKernelGGL(shadows ? pbr_hit_fetch_layers_kernel<true> : pbr_hit_fetch_layers_kernel<false>, grid2d(hit->rays, block), block, 0, s, MIFX_SHADE_INPUTS(in), out, in.cam, in.k, ly,
+                       in.hasEmissive, in.hasAo, in.sh);
+    MIFX_HIP_CHECK(hipGetLastError());
+    return MIFX_OK;
 }
 
+// (`output`, `targets`: validated by the entries, api_pbr.cpp; `out_color` is PSOut.Color; with `targets` -- the footer's four planes -- `out_spec` is null)
 mifx_status launch_pbr_shade_output(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_pbr_layers* layers, const mifx_camera_attribs& camera,
                                     const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, const float background[4], const mifx_image2d* out_color, const mifx_image2d* out_spec, int row_begin,
                                     int row_end, bool reversedDepth, const mifx_pbr_shadows* shadows, const mifx_pbr_shade_output_desc& output, const mifx_pbr_targets* targets)
 {
-    const mifx_pbr_layers none{};
-    return launch_pbr_shade_layers_impl(s, iblApron, g, layers ? *layers : none, camera, a, ibl, background, out_color, out_spec, row_begin, row_end, reversedDepth, shadows, nullptr, &output, targets);
+#ifdef MIFX_STORAGE_H4 // (no entry gets here: mifx_pbr_shade_output and mifx_pbr_shade_targets answer MIFX_ERR_NOT_IMPLEMENTED first)
+    set_error("mifx_pbr_shade_output: the output stage is not part of the native-storage build");
+    return MIFX_ERR_INVALID_ARG;
+#else
+    const mifx_pbr_layers none{}, &set = layers ? *layers : none;
+    MIFX_CHECK(check_layer_flags(set));
+    Img outC, outS{};
+    MIFX_CHECK(to_img(out_color, MIFX_FORMAT_F32X4, "out_radiance", outC));
+    outC = rows_of(outC, row_begin, row_end);
+    const uint32_t W = out_color->width, H = out_color->height;
+    ShadeInputs in;
+    LayersK     ly{};
+    MIFX_CHECK(bind_shade_planes(g, out_spec, W, H, in, outS));
+    MIFX_CHECK(bind_lights(a, shadows, "`shadows`", in.sh));
+    MIFX_CHECK(bind_layers(set, W, H, ly));
+    MIFX_CHECK(bind_shade_constants(s, iblApron, a, ibl, background, camera, reversedDepth, in));
+    Img motion{}, meshNormal{};
+    if (output.motion) MIFX_CHECK(to_img_wh(output.motion, MIFX_FORMAT_F32X2, W, H, "output.motion", motion));
+    if (output.mesh_normal) MIFX_CHECK(to_img_wh(output.mesh_normal, MIFX_FORMAT_F32X4, W, H, "output.mesh_normal", meshNormal));
+    const OutputK o = make_outputk(output, camera, output.motion != nullptr, output.mesh_normal != nullptr);
+    const dim3    block(64, 4, 1), grid = grid2d(outC, block);
+#define MIFX_OUTPUT_INSTANCE(TM)                                                                                                                                                \
+    hipLaunchKernelGGL((shadows ? pbr_shade_output_kernel<TM, true> : pbr_shade_output_kernel<TM, false>), grid, block, 0, s, MIFX_SHADE_INPUTS(in), outC, outS, in.cam, in.k, ly, \
+                       in.hasEmissive, in.hasAo, out_spec ? 1 : 0, in.sh, o, motion, meshNormal)
+#define MIFX_TARGETS_INSTANCE(TM)                                                                                                                                           \
+    hipLaunchKernelGGL((shadows ? pbr_shade_targets_kernel<TM, true> : pbr_shade_targets_kernel<TM, false>), grid, block, 0, s, MIFX_SHADE_INPUTS(in), outC, in.cam, in.k, ly, \
+                       in.hasEmissive, in.hasAo, in.sh, o, motion, meshNormal, tg)
+    if (targets != nullptr)
+    {
+        TargetsK tg{};
+        MIFX_CHECK(to_img_wh(targets->normal, MIFX_FORMAT_F32X4, W, H, "targets.normal", tg.normal));
+        MIFX_CHECK(to_img_wh(targets->base_color, MIFX_FORMAT_F32X4, W, H, "targets.base_color", tg.baseColor));
+        MIFX_CHECK(to_img_wh(targets->material, MIFX_FORMAT_F32X4, W, H, "targets.material", tg.material));
+        MIFX_CHECK(to_img_wh(targets->ibl, MIFX_FORMAT_F32X4, W, H, "targets.ibl", tg.ibl));
+        tg.animationFactor = output.renderer->LoadingAnimation.Factor;
+        MIFX_TONEMAP_DISPATCH(output.tone_mapping_mode, MIFX_TARGETS_INSTANCE)
+    }
+    else
+    {
+        MIFX_TONEMAP_DISPATCH(output.tone_mapping_mode, MIFX_OUTPUT_INSTANCE)
+    }
+#undef MIFX_TARGETS_INSTANCE
+#undef MIFX_OUTPUT_INSTANCE
+    MIFX_HIP_CHECK(hipGetLastError());
+    return MIFX_OK;
+#endif
 }
 
+// `g` is the draw's G-buffer, the frame is the OIT object's (`k`), nothing is written but the four targets; check_only stops behind the last argument check, in front of
+// the first device call
 mifx_status launch_oit_shade_blend(hipStream_t s, IblApronCache& iblApron, const OitK& k, const OitTargetsK& targets, const mifx_gbuffer* g, const mifx_pbr_layers* layers,
                                    const mifx_image2d* color_alpha, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl, bool reversedDepth,
                                    const mifx_pbr_shadows* shadows, bool check_only)
 {
-    const mifx_pbr_layers none{};
-    const OitShadeBlend   oit{k, targets, color_alpha, check_only};
-    return launch_pbr_shade_layers_impl(s, iblApron, g, layers ? *layers : none, camera, a, ibl, nullptr, nullptr, nullptr, 0, 0, reversedDepth, shadows, nullptr, nullptr, nullptr, &oit);
+#ifdef MIFX_STORAGE_H4 // (no entry gets here: api_oit.cpp answers MIFX_ERR_NOT_IMPLEMENTED first)
+    set_error("mifx_oit_shade_blend: not part of the native-storage build");
+    return MIFX_ERR_INVALID_ARG;
+#else
+    const mifx_pbr_layers none{}, &set = layers ? *layers : none;
+    MIFX_CHECK(check_layer_flags(set));
+    const uint32_t W = uint32_t(k.w), H = uint32_t(k.h);
+    ShadeInputs in;
+    LayersK     ly{};
+    Img         noSpec{}, alpha{};
+    MIFX_CHECK(bind_shade_planes(g, nullptr, W, H, in, noSpec));
+    MIFX_CHECK(bind_lights(a, shadows, "`shadows`", in.sh));
+    MIFX_CHECK(bind_layers(set, W, H, ly));
+    if (color_alpha != nullptr) MIFX_CHECK(to_img_wh(color_alpha, MIFX_FORMAT_F32, W, H, "slice color_alpha", alpha));
+    MIFX_CHECK(bind_shade_constants(s, iblApron, a, ibl, nullptr, camera, reversedDepth, in, check_only));
+    if (check_only) return MIFX_OK;
+    const OitShadeSliceK slice{in.bc, in.nrm, in.mat, in.depth, in.emis, in.occ, alpha, in.hasEmissive, in.hasAo, color_alpha ? 1 : 0};
+    const dim3           block(64, 4, 1);
+    hipLaunchKernelGGL(shadows ? oit_shade_blend_kernel<true> : oit_shade_blend_kernel<false>, grid2d(int(W), int(H), block), block, 0, s, slice, in.lut, in.irr, in.pre, in.cam, in.k, ly,
+                       in.sh, k, targets);
+    MIFX_HIP_CHECK(hipGetLastError());
+    return MIFX_OK;
+#endif
 }
 
 mifx_status launch_pbr_hit_fetch(hipStream_t s, IblApronCache& iblApron, const mifx_gbuffer* g, const mifx_camera_attribs& camera, const mifx_pbr_shade_attribs& a, const mifx_ibl* ibl,
                                  const float background[4], Img rays, Img hitCoords, const mifx_image2d* radiance, int shadedBegin, int shadedEnd, bool reversedDepth)
 {
-    Img bc, nrm, mat, depth, emis{}, occ{}, rad, noSpec{};
+    Img rad, noSpec{};
     MIFX_CHECK(to_img(radiance, MIFX_FORMAT_F32X4, "radiance", rad));
     const uint32_t W = radiance->width, H = radiance->height;
     MIFX_REQUIRE(W <= 65536u && H <= 65536u, "launch_pbr_hit_fetch: frame %ux%u exceeds the 16-bit hit coordinates", W, H);
-    MIFX_CHECK(bind_gbuffer(g, nullptr, W, H, bc, nrm, mat, depth, emis, occ, noSpec));
-    LutK lut;
-    CubeK irr, pre;
-    ShadeK k{};
-    MIFX_CHECK(make_shade_constants(s, iblApron, a, ibl, background, lut, irr, pre, k));
-    const CamK cam = make_camk(camera, reversedDepth);
+    ShadeInputs in;
+    MIFX_CHECK(bind_shade_planes(g, nullptr, W, H, in, noSpec));
+    MIFX_CHECK(bind_shade_constants(s, iblApron, a, ibl, background, camera, reversedDepth, in));
     const HitOut out{rays, hitCoords, rad, shadedBegin, shadedEnd};
     const dim3 block(64, 4, 1), grid = grid2d(rays, block);
-#define MIFX_FETCH(E, A) hipLaunchKernelGGL((pbr_hit_fetch_kernel<E, A>), grid, block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, out, cam, k)
-    switch ((g->emissive ? 2 : 0) | (g->occlusion ? 1 : 0))
-    {
-        case 0: MIFX_FETCH(false, false); break;
-        case 1: MIFX_FETCH(false, true); break;
-        case 2: MIFX_FETCH(true, false); break;
-        default: MIFX_FETCH(true, true); break;
-    }
+#define MIFX_FETCH(E, A, S) hipLaunchKernelGGL((pbr_hit_fetch_kernel<E, A>), grid, block, 0, s, MIFX_SHADE_INPUTS(in), out, in.cam, in.k)
+    MIFX_SHADE_DISPATCH(in.hasEmissive, in.hasAo, false, MIFX_FETCH) // (nothing but the colour is written: no S)
 #undef MIFX_FETCH
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;
@@ -784,18 +792,7 @@ mifx_status launch_pbr_shade_native(hipStream_t s, IblApronCache& iblApron, cons
         if (out_spec) hipLaunchKernelGGL((pbr_shade_native_kernel<false, false, true, true>), grid, block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, outR, outS, cam, k);
         else hipLaunchKernelGGL((pbr_shade_native_kernel<false, false, false, true>), grid, block, 0, s, bc, nrm, mat, depth, emis, occ, lut, irr, pre, outR, outS, cam, k);
     }
-    else
-    switch ((g->emissive ? 4 : 0) | (g->occlusion ? 2 : 0) | (out_spec ? 1 : 0))
-    {
-        case 0: MIFX_SHADE(false, false, false); break;
-        case 1: MIFX_SHADE(false, false, true); break;
-        case 2: MIFX_SHADE(false, true, false); break;
-        case 3: MIFX_SHADE(false, true, true); break;
-        case 4: MIFX_SHADE(true, false, false); break;
-        case 5: MIFX_SHADE(true, false, true); break;
-        case 6: MIFX_SHADE(true, true, false); break;
-        default: MIFX_SHADE(true, true, true); break;
-    }
+    else MIFX_SHADE_DISPATCH(g->emissive, g->occlusion, out_spec, MIFX_SHADE)
 #undef MIFX_SHADE
     MIFX_HIP_CHECK(hipGetLastError());
     return MIFX_OK;

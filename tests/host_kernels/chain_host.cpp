@@ -16,18 +16,6 @@
 
 using namespace mifx;
 
-static CamK host_camk(const mifx_camera_attribs* c) // make_camk (mifx_core.cpp)
-{
-    CamK k{};
-    std::memcpy(k.view.m, c->mView, 64); std::memcpy(k.proj.m, c->mProj, 64); std::memcpy(k.viewProj.m, c->mViewProj, 64);
-    std::memcpy(k.viewInv.m, c->mViewInv, 64); std::memcpy(k.viewProjInv.m, c->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) k.pos[i] = c->f4Position[i];
-    k.vw = c->f4ViewportSize[0]; k.vh = c->f4ViewportSize[1]; k.ivw = c->f4ViewportSize[2]; k.ivh = c->f4ViewportSize[3];
-    k.jx = c->f2Jitter[0]; k.jy = c->f2Jitter[1];
-    k.frameIndex = c->uiFrameIndex;
-    return k;
-}
-
 extern "C" {
 // in / out: w x h float4 texels, tightly packed
 int mifx_host_tonemap(const float* in, float* out, int w, int h, const mifx_tone_mapping_attribs* attribs, float ave_log_lum, int srgb)
@@ -78,11 +66,7 @@ int mifx_host_composite(const float* color, const float* specular_ibl, const flo
     auto img = [&](const float* p, int c) { return p ? Img{reinterpret_cast<unsigned char*>(const_cast<float*>(p)), w, h, w * c * 4, 0, 0} : Img{}; };
     const Img c0 = img(color, 4), sibl = img(specular_ibl, 4), refl = img(ssr, 4), ao = img(ssao, 1), nrm = img(normal, 4), bc = img(base_color, 4), mat = img(material, 4);
     const LutK lutk{lut, lw, lh, lw * lc, lc};
-    CamK cam{}; // make_camk (mifx_core.cpp)
-    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
-    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
-    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
+    const CamK cam = make_camk(*camera);
     const SsrCleanupIn r7{img(depth, 1), img(roughness, 1), img(radiance, 4), img(variance, 1), img(mask, 1), roughness_threshold, spatial_sigma_factor, alpha_interpolation, 0};
     const ToneMapK tm{};
 #pragma omp parallel for schedule(dynamic, 4)
@@ -106,7 +90,7 @@ int mifx_host_ssr_temporal(const float* motion, const float* hit_depth, const fl
     auto img = [&](const float* p, int c) { return Img{reinterpret_cast<unsigned char*>(const_cast<float*>(p)), w, h, w * c * 4, 0, 0}; };
     const Img mo = img(motion, 2), hd = img(hit_depth, 1), rd = img(reprojected_depth, 1), cr = img(curr_radiance, 4), cv = img(curr_variance, 1), pd = img(prev_depth, 1),
               pr = img(prev_radiance, 4), pv = img(prev_variance, 1), mk = img(mask, 1), orad = img(out_radiance, 4), ovar = img(out_variance, 1);
-    const CamK cur = host_camk(camera), prev = host_camk(prev_camera);
+    const CamK cur = make_camk(*camera), prev = make_camk(*prev_camera);
     const SsrK k = make_k(*attribs, false);
 #pragma omp parallel for schedule(dynamic, 4)
     for (int y = 0; y < h; ++y)

@@ -7,8 +7,6 @@
 #undef __device__
 #define __device__ __attribute__((host)) __attribute__((device))
 #include "mifx_pbr_layers.h"
-#include <cmath>
-#include <cstring>
 #include <type_traits>
 
 using namespace mifx;
@@ -27,10 +25,7 @@ int mifx_host_pbr_shade_layers(const host_plane* planes, const host_plane* layer
     auto lutk = [](const host_plane& p) { return LutK{p.data, p.w, p.h, p.w * p.c, p.c}; };
     const Img bc = img(planes[0]), nrm = img(planes[1]), mat = img(planes[2]), depth = img(planes[3]), emis = img(planes[4]), occ = img(planes[5]), outR = img(planes[6]), outS = img(planes[7]);
     LayersK ly{};
-    ly.flags = flags;
-    ly.iridescenceIor = iridescence_ior;
-    ly.rotationCos = std::cos(anisotropy_rotation);
-    ly.rotationSin = std::sin(anisotropy_rotation);
+    set_layer_scalars(ly, flags, iridescence_ior, anisotropy_rotation);
     ly.clearcoat = img(layers[0]); ly.clearcoatNormal = img(layers[1]); ly.sheen = img(layers[2]); ly.anisotropy = img(layers[3]); ly.tangent = img(layers[4]);
     ly.iridescence = img(layers[5]); ly.transmission = img(layers[6]);
     ly.hasClearcoatNormal = layers[1].data != nullptr;
@@ -38,18 +33,8 @@ int mifx_host_pbr_shade_layers(const host_plane* planes, const host_plane* layer
     const LutK lut = lutk(luts[0]);
     if (luts[1].data) ly.albedoScaling = lutk(luts[1]);
     if (luts[2].data) ly.charlie = lutk(luts[2]);
-    ShadeK k{};
-    k.iblScale[0] = a->IBLScale[0]; k.iblScale[1] = a->IBLScale[1]; k.iblScale[2] = a->IBLScale[2];
-    k.occlusionStrength = a->OcclusionStrength; k.emissionScale = a->EmissionScale; k.prefilteredCubeLastMip = a->PrefilteredCubeLastMip;
-    k.lightCount = a->LightCount; k.workflow = a->Workflow;
-    for (int i = 0; i < a->LightCount; ++i) k.lights[i] = a->Lights[i];
-    for (int i = 0; i < 4; ++i) k.background[i] = background[i];
-    CamK cam{}; // make_camk (mifx_core.cpp)
-    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
-    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
-    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
-    cam.reversedDepth = reversed_depth;
+    const ShadeK k = make_shadek(*a, background);
+    const CamK cam = make_camk(*camera, reversed_depth != 0);
     ShadowK sh{};
     if (shadow_slices != nullptr)
     {

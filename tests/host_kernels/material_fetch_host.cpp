@@ -50,12 +50,7 @@ int mifx_host_material_fetch(const host_plane* interpolants, const host_plane* o
     k.outTransmission = img(outputs[10]);
     k.materials = materials; k.textures = tex.data(); k.materialCount = material_count; k.textureCount = texture_count;
     k.layers = layer_flags; k.flags = flags; k.mipBias = mip_bias; k.handness = camera->fHandness; k.workflow = materials[0].basic.Workflow;
-    CamK cam{}; // make_camk (mifx_core.cpp)
-    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
-    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
-    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
-    cam.reversedDepth = reversed_depth;
+    const CamK cam = make_camk(*camera, reversed_depth != 0);
     return mifx_host_material_fetch_launch(&k, &cam);
 }
 }

@@ -7,8 +7,6 @@
 #undef __device__
 #define __device__ __attribute__((host)) __attribute__((device))
 #include "mifx_oit_shade.h"
-#include <cmath>
-#include <cstring>
 
 using namespace mifx;
 
@@ -30,17 +28,8 @@ int mifx_host_transparency(int K, int W, int H, int L, const host_tslice* slices
     const OitK k{bytes(layers), bytes(tail), opaque.data ? bytes(opaque.data) : nullptr, W, H, K, W * 8, opaque.pitch, make_oitcamk(*camera)};
     const OitTargetsK t{img(targets[0]), img(targets[1]), img(targets[2]), img(targets[3])};
     const LutK lut{lut_plane->data, lut_plane->w, lut_plane->h, lut_plane->w * lut_plane->c, lut_plane->c};
-    ShadeK sk{};
-    sk.iblScale[0] = a->IBLScale[0]; sk.iblScale[1] = a->IBLScale[1]; sk.iblScale[2] = a->IBLScale[2];
-    sk.occlusionStrength = a->OcclusionStrength; sk.emissionScale = a->EmissionScale; sk.prefilteredCubeLastMip = a->PrefilteredCubeLastMip;
-    sk.lightCount = a->LightCount; sk.workflow = a->Workflow;
-    for (int i = 0; i < a->LightCount; ++i) sk.lights[i] = a->Lights[i];
-    CamK cam{}; // make_camk (mifx_core.cpp)
-    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
-    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
-    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
-    cam.reversedDepth = reversed_depth;
+    const ShadeK sk = make_shadek(*a, nullptr);
+    const CamK cam = make_camk(*camera, reversed_depth != 0);
     const LayersK ly{};
     const ShadowK sh{};
     const v4* pref[12] = {};
@@ -77,10 +66,7 @@ int mifx_host_oit_shade_blend_launch(const OitK* k, const OitTargetsK* t, const 
     const OitShadeSliceK slice{img(planes[0]), img(planes[1]), img(planes[2]), img(planes[3]), img(planes[4]), img(planes[5]), img(planes[6]),
                                planes[4].data != nullptr, planes[5].data != nullptr, planes[6].data != nullptr};
     LayersK ly{};
-    ly.flags = flags;
-    ly.iridescenceIor = iridescence_ior;
-    ly.rotationCos = std::cos(anisotropy_rotation);
-    ly.rotationSin = std::sin(anisotropy_rotation);
+    set_layer_scalars(ly, flags, iridescence_ior, anisotropy_rotation);
     ly.clearcoat = img(layers[0]); ly.clearcoatNormal = img(layers[1]); ly.sheen = img(layers[2]); ly.anisotropy = img(layers[3]); ly.tangent = img(layers[4]);
     ly.iridescence = img(layers[5]); ly.transmission = img(layers[6]);
     ly.hasClearcoatNormal = layers[1].data != nullptr;
@@ -88,17 +74,8 @@ int mifx_host_oit_shade_blend_launch(const OitK* k, const OitTargetsK* t, const 
     const LutK lut = lutk(luts[0]);
     if (luts[1].data) ly.albedoScaling = lutk(luts[1]);
     if (luts[2].data) ly.charlie = lutk(luts[2]);
-    ShadeK sk{};
-    sk.iblScale[0] = a->IBLScale[0]; sk.iblScale[1] = a->IBLScale[1]; sk.iblScale[2] = a->IBLScale[2];
-    sk.occlusionStrength = a->OcclusionStrength; sk.emissionScale = a->EmissionScale; sk.prefilteredCubeLastMip = a->PrefilteredCubeLastMip;
-    sk.lightCount = a->LightCount; sk.workflow = a->Workflow;
-    for (int i = 0; i < a->LightCount; ++i) sk.lights[i] = a->Lights[i];
-    CamK cam{}; // make_camk (mifx_core.cpp)
-    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
-    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
-    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
-    cam.reversedDepth = reversed_depth;
+    const ShadeK sk = make_shadek(*a, nullptr);
+    const CamK cam = make_camk(*camera, reversed_depth != 0);
     ShadowK sh{};
     if (shadow_slices != nullptr)
     {

@@ -5,8 +5,6 @@
 #undef __device__
 #define __device__ __attribute__((host)) __attribute__((device))
 #include "mifx_pbr_output.h"
-#include <cmath>
-#include <cstring>
 #include <type_traits>
 
 using namespace mifx;
@@ -27,10 +25,7 @@ int mifx_host_pbr_shade_targets(const host_plane* planes, const host_plane* laye
     const Img tgN = img(planes[10]), tgB = img(planes[11]), tgM = img(planes[12]), tgI = img(planes[13]);
     const Img motion = img(planes[8]), meshNormal = img(planes[9]);
     LayersK ly{};
-    ly.flags = flags;
-    ly.iridescenceIor = iridescence_ior;
-    ly.rotationCos = std::cos(anisotropy_rotation);
-    ly.rotationSin = std::sin(anisotropy_rotation);
+    set_layer_scalars(ly, flags, iridescence_ior, anisotropy_rotation);
     ly.clearcoat = img(layers[0]); ly.clearcoatNormal = img(layers[1]); ly.sheen = img(layers[2]); ly.anisotropy = img(layers[3]); ly.tangent = img(layers[4]);
     ly.iridescence = img(layers[5]); ly.transmission = img(layers[6]);
     ly.hasClearcoatNormal = layers[1].data != nullptr;
@@ -38,18 +33,8 @@ int mifx_host_pbr_shade_targets(const host_plane* planes, const host_plane* laye
     const LutK lut = lutk(luts[0]);
     if (luts[1].data) ly.albedoScaling = lutk(luts[1]);
     if (luts[2].data) ly.charlie = lutk(luts[2]);
-    ShadeK k{};
-    k.iblScale[0] = a->IBLScale[0]; k.iblScale[1] = a->IBLScale[1]; k.iblScale[2] = a->IBLScale[2];
-    k.occlusionStrength = a->OcclusionStrength; k.emissionScale = a->EmissionScale; k.prefilteredCubeLastMip = a->PrefilteredCubeLastMip;
-    k.lightCount = a->LightCount; k.workflow = a->Workflow;
-    for (int i = 0; i < a->LightCount; ++i) k.lights[i] = a->Lights[i];
-    for (int i = 0; i < 4; ++i) k.background[i] = background[i];
-    CamK cam{}; // make_camk (mifx_core.cpp)
-    std::memcpy(cam.view.m, camera->mView, 64); std::memcpy(cam.proj.m, camera->mProj, 64); std::memcpy(cam.viewProj.m, camera->mViewProj, 64);
-    std::memcpy(cam.viewInv.m, camera->mViewInv, 64); std::memcpy(cam.viewProjInv.m, camera->mViewProjInv, 64);
-    for (int i = 0; i < 3; ++i) cam.pos[i] = camera->f4Position[i];
-    cam.vw = camera->f4ViewportSize[0]; cam.vh = camera->f4ViewportSize[1]; cam.ivw = camera->f4ViewportSize[2]; cam.ivh = camera->f4ViewportSize[3];
-    cam.reversedDepth = reversed_depth;
+    const ShadeK k = make_shadek(*a, background);
+    const CamK cam = make_camk(*camera, reversed_depth != 0);
     ShadowK sh{};
     if (shadow_slices != nullptr)
     {
@@ -61,20 +46,8 @@ int mifx_host_pbr_shade_targets(const host_plane* planes, const host_plane* laye
     }
     const v4* pref[12] = {};
     for (int l = 0; l < pref_levels && l < 12; ++l) pref[l] = reinterpret_cast<const v4*>(prefiltered[l].data);
-    // the constants of launch_pbr_shade_layers' output stage (pbr.hip)
     const mifx_pbr_shade_output_desc& d = *desc;
-    const mifx_pbr_renderer_shader_parameters& r = *d.renderer;
-    OutputK o{};
-    o.debugView = d.debug_view; o.loadingAnimation = d.loading_animation; o.alphaMode = d.alpha_mode; o.unlit = d.unlit != 0;
-    o.srgb = (d.flags & MIFX_PBR_SHADE_OUTPUT_FLAG_CONVERT_OUTPUT_TO_SRGB) != 0u;
-    o.hasMotion = motion.p != nullptr; o.hasMeshNormal = meshNormal.p != nullptr;
-    o.alphaMaskCutoff = d.alpha_mask_cutoff;
-    o.tm = ToneMapK{r.MiddleGray, r.WhitePoint, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, r.AverageLogLum, 0};
-    for (int i = 0; i < 4; ++i) o.highlight[i] = r.HighlightColor[i];
-    o.time = r.Time; o.worldScale = r.LoadingAnimation.WorldScale; o.speed = r.LoadingAnimation.Speed;
-    o.factor = d.loading_animation == MIFX_PBR_LOADING_ANIMATION_TRANSITIONING ? r.LoadingAnimation.Factor : 1.0f;
-    for (int i = 0; i < 3; ++i) { o.color0[i] = r.LoadingAnimation.Color0[i]; o.color1[i] = r.LoadingAnimation.Color1[i]; }
-    o.sceneNearZ = camera->fSceneNearZ; o.sceneFarZ = camera->fSceneFarZ;
+    const OutputK o = make_outputk(d, *camera, motion.p != nullptr, meshNormal.p != nullptr);
 
     auto run = [&](auto tm_tag, auto shadow_tag) {
         constexpr int  TM = decltype(tm_tag)::value;
@@ -86,7 +59,7 @@ int mifx_host_pbr_shade_targets(const host_plane* planes, const host_plane* laye
                 v4 color;
                 ShadeTargets t;
                 pbr_shade_targets_pixel<false, SHADOWS, TM>(x, y, bc, nrm, mat, depth, emis, occ, lut, reinterpret_cast<const v4*>(irradiance->data), irradiance->w, pref, prefiltered[0].w,
-                                                            pref_levels, cam, k, ly, emis.p != nullptr, occ.p != nullptr, sh, o, r.LoadingAnimation.Factor, motion, meshNormal, color, t);
+                                                            pref_levels, cam, k, ly, emis.p != nullptr, occ.p != nullptr, sh, o, d.renderer->LoadingAnimation.Factor, motion, meshNormal, color, t);
                 st<v4>(outC, x, y, color);
                 st<v4>(tgN, x, y, t.normal);
                 st<v4>(tgB, x, y, t.baseColor);
